@@ -23,7 +23,17 @@ payload moves during decode (blocks are independent units).  --schedule queue
 replaces the fixed shards by the dynamic work queue (multigpu.WorkQueue: ranks
 pull chunks of --queue-blocks blocks from one counter on the job's store).
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]
+A plain run does only what the headline needs: it writes the stream, warms up, times
+--steps steps, checks the last step's plaintext bit for bit against the generator and
+prints the line (`value`, `ms_per_step` = milliseconds per timed step, the roofline of
+the timed kernel from the committed counts).  --full adds everything else the bench
+measures: the 1-thread CPU baseline of the same stream and, on one GPU, host_to_host,
+the all-core CPU figures, the other BASELINE-shaped configurations and the method
+streams; it also writes the unabridged line to --full-json.  --dump-outputs DIR writes
+what the last timed step returned (see dump_outputs); the inputs are the same from run
+to run, so two builds can be compared output for output.
+
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
   N>1:   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
              --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 Prints ONE JSON line on rank 0.
@@ -106,12 +116,18 @@ def parse_args():
     ap.add_argument("--kind", default=None, help="plaintext generator T | X | R (default T, X for +e8e9)")
     ap.add_argument("--blocks", type=int, default=256, help="blocks per GPU")
     ap.add_argument("--block-bytes", type=int, default=4 << 20)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: cpu_baseline and, N=1, the extra figures (--no-extras)")
+    ap.add_argument("--full-json", default=os.path.join(ROOT, "bench_out", "bench_full.json"),
+                    help="--full: where the unabridged line is written")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned to DIR/*.npy (dump_outputs)")
     ap.add_argument("--cpu-sample-blocks", type=int, default=None,
-                    help="blocks decoded by the CPU oracle for cpu_baseline (default: ~15 s of work)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="blocks decoded by the CPU oracle for cpu_baseline (--full; default: ~15 s of work)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra figures of the N=1 line (host_to_host, all-core CPU, configs[2] / [4] shaped runs)")
+                    help="--full without the extra figures of the N=1 line (host_to_host, all-core CPU, configs[2] / [4] shaped runs)")
     ap.add_argument("--extras-block-bytes", type=int, default=4 << 20,
                     help="block size of the configs[2] / configs[4] shaped extra runs (256 blocks each; BASELINE size = 4194304)")
     ap.add_argument("--extras-distinct", type=int, default=64,
@@ -127,7 +143,10 @@ def parse_args():
     ap.add_argument("--dist-backend", default="nccl", help="nccl (RCCL; the real thing) | gloo (rehearsal of the N>1 path)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal only: ranks share the visible GPUs round-robin (needs --dist-backend gloo)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def make_stream(synth, model, model_name, kind, nb, bs, first_block, threads, cache_dir):
@@ -366,7 +385,7 @@ def _r(x, n=2):
 def compact_line(line):
     """The ONE line bench.py prints, kept under 8 KB (the driver records the last 8 KB of the output): the contract's keys in full,
     roofline and cpu_baseline without their prose, and every other measured configuration as one short record — the
-    per-config summary comes LAST.  The unabridged line is written to gpurun_out/bench_full.json."""
+    per-config summary comes LAST.  With --full, the unabridged line is written to --full-json."""
     def roof(r):
         iss = r.get("issue") or {}
         return {"bound": r["bound"], "achieved": _r(r["achieved"], 3), "peak": r["peak"], "unit": r["unit"], "frac": _r(r["frac"], 5),
@@ -414,6 +433,43 @@ def compact_line(line):
             oc.append(rec)
         out["other_configs"] = oc
     return out
+
+
+DUMP_SAMPLE_BYTES = 8 << 20             # plaintext bytes --dump-outputs keeps (float32: 32 MB of the 64 MB it may take)
+DUMP_SEED = 0x5A50
+
+
+def verify_blocks(got, where, kind, bs, threads):
+    """Every block b this rank decoded (`where`: global id -> slot of `got`) equals the generator's plaintext of block b."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from zpaqsharp_amd import synth
+
+    def same(item):                                          # the generator and the compare release the GIL
+        b, j = item
+        return np.array_equal(got[j * bs:(j + 1) * bs], synth.plain(kind, b, bs))
+    with ThreadPoolExecutor(max_workers=threads) as pool:
+        return all(pool.map(same, sorted(where.items())))
+
+
+def dump_outputs(out_dir, table, got, where, bs):
+    """--dump-outputs: what the last timed step returned to its caller, as float32 / float64 .npy files.
+    block_table.npy   [n_blocks, 2] float64: the per-block {status, out_len} table of every block of the stream;
+    plaintext_sample.npy  float32: decoded plaintext bytes of the blocks this rank decoded (`where`: global id -> slot of
+                      `got`), taken in block order at DUMP_SAMPLE_BYTES positions drawn with the fixed seed DUMP_SEED
+                      (sorted; all of it when it is smaller), so the same arguments sample the same bytes."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "block_table.npy"), np.asarray(table[:, :2], np.float64))
+    ids = sorted(where)
+    total = len(ids) * bs
+    if total <= DUMP_SAMPLE_BYTES:
+        pos = np.arange(total, dtype=np.int64)
+    else:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_SAMPLE_BYTES, dtype=np.int64))
+    slot = np.array([where[b] for b in ids], np.int64)
+    src = slot[pos // bs] * bs + pos % bs
+    assert src.size == 0 or int(src.max()) < got.size
+    np.save(os.path.join(out_dir, "plaintext_sample.npy"), got[src].astype(np.float32))
 
 
 def main():
@@ -516,18 +572,15 @@ def main():
 
     # ---- bit-exact check of the last (queue: the fresh) pass's output against the generator's plaintext (global block ids)
     ok = bool((table[:, 0] == 0).all() and (table[:, 1] == bs).all())
+    if dynamic:
+        mine = [b for ids in job.pulled for b in ids]        # what this rank decoded in the last pass, at its global place
+        where = {b: b for b in mine}
+    else:
+        where = {b: j for j, b in enumerate(mine)}
+    got = None
     if not args.no_verify:
         got = d_out.cpu().numpy()
-        if dynamic:
-            mine = [b for ids in job.pulled for b in ids]    # what this rank decoded in the last pass, at its global place
-            where = {b: b for b in mine}
-        else:
-            where = {b: j for j, b in enumerate(mine)}
-        for b in mine:
-            j = where[b]
-            if not np.array_equal(got[j * bs:(j + 1) * bs], synth.plain(kind, b, bs)):
-                ok = False
-                break
+        ok = ok and verify_blocks(got, where, kind, bs, max(1, min(16, usable_cores)))
     coded_bytes = int(sum(s.data_len for s in job.sc.segments))
     total_plain = n_glob * bs
     if world > 1:
@@ -548,12 +601,16 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = total_plain * args.steps / elapsed / 1e6
     kms = float(np.mean(kernel_ms))
+    progress(f"timed region done: {value:.1f} MB/s")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, table, got if got is not None else d_out.cpu().numpy(), where, bs)
+    del got
 
     cpu = None
     extras = {}
     block_start = [int(b.tag_off) for b in job.sc.blocks] + [job.stream_len]
-    progress(f"timed region done: {value:.1f} MB/s; cpu baseline")
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
+        progress("cpu baseline")
         import oracle
         # bounded sample of the SAME stream: first S blocks, one host thread.
         per_block_guess = bs / 9e6 if base == "l1" else bs / 1.5e6
@@ -577,7 +634,7 @@ def main():
             extras["cpu_share"] = share
             extras["cpu_all_cores_sweep"] = cpu_sweep(oracle, pieces, bs, sweep_counts(share))
 
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # host buffer -> host buffer through zpaqhip_decompress (scan + H2D + kernel + D2H), pinned memory
         progress("host to host")
         h_in = torch.from_numpy(job.h_stream).pin_memory()
@@ -662,12 +719,13 @@ def main():
     if not ok:
         line["value"] = 0.0
         line["error"] = "GPU output is not bit-exact"
-    try:                                                    # everything, for the builder: profiles/ keeps copies of this file
-        os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-        with open(os.path.join(ROOT, "gpurun_out", "bench_full.json"), "w") as f:
-            json.dump(line, f)
-    except OSError:
-        pass
+    if args.full:
+        try:                                                # everything, for the builder: profiles/ keeps copies of this file
+            os.makedirs(os.path.dirname(os.path.abspath(args.full_json)), exist_ok=True)
+            with open(args.full_json, "w") as f:
+                json.dump(line, f)
+        except OSError:
+            pass
     print(json.dumps(compact_line(line), separators=(",", ":")))
     if world > 1:
         dist.destroy_process_group()

@@ -21,5 +21,5 @@ done
 python3 tools/pmc_summary.py "$OUT" "$MODEL" "$NB" "$BS"
 # the bench line last: with the PMC summary of THESE sources in place (profiles/$ROUND/), bench.py fills roofline.traffic
 ROUND=${ROUND:-r03}; mkdir -p profiles/$ROUND; cp "$OUT"/pmc_*KiB.json profiles/$ROUND/
-echo "== bench"; python3 bench.py $ARGS > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; exit 1; }
+echo "== bench"; python3 bench.py $ARGS --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"

@@ -115,16 +115,20 @@ typedef struct zpaqhip_opts {
   uint32_t struct_size;       /* = sizeof(zpaqhip_opts) */
   uint32_t verify_sha1;       /* 1: check stored SHA-1 of every segment (Decompresser.cs:183-191 contract); hashed on the GPU */
   uint32_t max_concurrent;    /* blocks in flight per launch; 0 = auto (memory-bound) */
-  uint32_t kernel;            /* 0 auto; 1 force the generic (one-lane) kernel; 2 / 6: single-CM blocks one / two per workgroup
-                                 (auto: two when a launch has more than 256 of them); 3 prefer the lane-per-component kernel;
-                                 4 lane-per-component without model specialisation; 5 the run-time-level form of the
-                                 lane-per-component kernel also for the built-in min/mid/max models (cross-check);
-                                 7 / 8: ignored (= auto) by the product build; a library built with `make EXPERIMENTS=1` runs the
-                                 measured-and-not-kept three-wave form of mid/max there (tools/experiments/zh_chain3.hip);
-                                 9: the built-in min / mid models on the bit-at-a-time kernels of rounds 2-4 (zh_chain2.hip) instead of
-                                 the nibble-at-a-time ones (zh_nibble.hip): cross-check and A/B runs.  The models LibZPAQ.makeConfig
-                                 writes for levels 3 / 4 (`ci1`, `...,1c0,0,511i2`, `ci1,1,1,1,2am`, `...2awm`) are known to
-                                 zh_nibble.hip only: under 4, 5 and 9 they run on the lane-per-component kernel */
+  uint32_t kernel;            /* which kernel decodes a block (cross-checks and A/B runs; 0 for production):
+                                   0 auto: stored -> zh_store; single CM -> zh_cm, two blocks per workgroup when a launch has
+                                     more than 256 of them; min / mid and the models LibZPAQ.makeConfig writes for levels 3 / 4
+                                     (`ci1`, `...,1c0,0,511i2`, `ci1,1,1,1,2am`, `...2awm`) -> zh_nibble; max -> zh_chain2;
+                                     other models that fit the lane-per-component kernel -> zh_chain (level walk at run time);
+                                     the rest -> zh_generic (one lane);
+                                   1 every block on zh_generic;
+                                   2 / 6 single-CM blocks one / two per workgroup;
+                                   3 single-CM blocks on zh_chain;
+                                   4 every block that auto sends to zh_nibble, zh_chain2 or zh_store on zh_chain, without model
+                                     specialisation (stored blocks included);
+                                   5 min / mid / max on zh_chain's forms of the built-in models; the level 3 / 4 models on zh_chain;
+                                   9 min / mid on zh_chain2 (bit at a time) instead of zh_nibble; the level 3 / 4 models on zh_chain;
+                                   7 / 8 and any other value: as 0 */
   uint64_t zpaql_budget;      /* runaway-program guard, per run() call: max ZPAQL instructions on the interpreter, max backward
                                  jumps in an ahead-of-time translated program (a translation checks where it can loop);
                                  0 = default (1<<32).  Exceeding it ends the block with ZPAQHIP_E_BUDGET */

@@ -7,7 +7,7 @@ SRC=$1; MAC=$2; shift 2
 cd "$(dirname "$0")/../zpaqsharp_amd/csrc"
 mkdir -p ../../build/ab
 make -s -j8
-OBJS=$(ls *.o | grep -v "^${SRC%.hip}.o$" | grep -v zh_chain3.o)
+OBJS=$(ls *.o | grep -v "^${SRC%.hip}.o$")
 for v in "$@"; do
   ( /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -D$MAC=$v $EXTRA --offload-arch=gfx950 -c $SRC -o /tmp/${SRC%.hip}_$MAC$v$TAG.o 2>/dev/null &&
     /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../../build/ab/lib$MAC$v$TAG.so $OBJS /tmp/${SRC%.hip}_$MAC$v$TAG.o && echo built $MAC$v$TAG ) &

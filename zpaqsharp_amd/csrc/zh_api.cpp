@@ -33,10 +33,6 @@ extern "C" int zh_chain2_has(uint32_t spec);
 extern "C" hipError_t zh_launch_nibble(const ZhLaunch *L, uint32_t grid, hipStream_t stream, uint32_t spec, int prof);
 extern "C" int zh_nibble_has(uint32_t spec);
 static size_t pool_trim_device(int device, size_t keep);   // idle contexts of zpaqhip_decompress_multi's pool (below)
-#ifdef ZH_WITH_CHAIN3   // make EXPERIMENTS=1: tools/experiments/zh_chain3.hip (three-wave form, measured slower; not in the product build)
-extern "C" hipError_t zh_launch_chain3(const ZhLaunch *L, uint32_t grid, hipStream_t stream, uint32_t spec, int variant);
-extern "C" int zh_chain3_has(uint32_t spec);
-#endif
 extern "C" hipError_t zh_launch_store(const ZhLaunch *L, uint32_t grid, hipStream_t stream);
 
 
@@ -105,6 +101,36 @@ zpaqhip_opts resolve_opts(const zpaqhip_opts *o) {
   if (o) memcpy(&r, o, std::min<size_t>(sizeof r, o->struct_size ? o->struct_size : sizeof r));
   if (!r.zpaql_budget) r.zpaql_budget = 1ull << 32;
   return r;
+}
+
+// ---- which kernel decodes a block (the table is include/zpaqhip.h's): the one place that reads opts.kernel, but for zh_cm's
+// one / two blocks per workgroup, decided in decode_launch where the group's size is known.  `group` is the block's family
+// after opts.kernel's overrides (its work-queue head, arena region, stream and launch order); `spec` the kernel's specialisation
+enum class ZhKernel { Generic, Store, Cm, Chain, Chain2, Nibble };
+struct ZhRoute { uint32_t group; ZhKernel kernel; uint32_t spec; };
+
+ZhRoute route_block(const ZhModel &m, const zpaqhip_opts &o, bool pp_only) {
+  const uint32_t K = o.kernel, hk = (m.kind >> 8) & 255u;
+  uint32_t f = m.kind & 255u;
+  // the method models of min's / mid's shape (zh_framing.cpp) are known to zh_nibble.hip only: the older kernels of these
+  // families carry the built-in HCOMP programs
+  const bool method = hk == ZH_NATIVE_HCOMP_M4 || hk == ZH_NATIVE_HCOMP_M3 || hk == ZH_NATIVE_HCOMP_M2 || hk == ZH_NATIVE_HCOMP_M2E;
+  if (K == 1 || (f == ZH_FAM_STORE && pp_only)) f = ZH_FAM_GENERIC;
+  if (K == 3 && f == ZH_FAM_CM1) f = ZH_FAM_CHAIN;
+  if (K == 4 && f > ZH_FAM_CHAIN) f = ZH_FAM_CHAIN;                  // stored blocks included
+  if ((K == 5 || K == 9) && ((f > ZH_FAM_CHAIN && f < ZH_FAM_STORE && method) || f == ZH_FAM_CHAIN_MID8 || f == ZH_FAM_CHAIN_MIN1))
+    f = ZH_FAM_CHAIN;
+  switch (f) {
+    case ZH_FAM_GENERIC: return {f, ZhKernel::Generic, 0};
+    case ZH_FAM_CM1: return {f, ZhKernel::Cm, 0};
+    case ZH_FAM_STORE: return {f, ZhKernel::Store, 0};
+    case ZH_FAM_CHAIN_MID8: return {f, ZhKernel::Nibble, 5};           // mid's shape, eight mixer inputs
+    case ZH_FAM_CHAIN_MIN1: return {f, ZhKernel::Nibble, 6};           // one ICM on min's loop
+  }
+  const uint32_t spec = f - ZH_FAM_CHAIN;                              // 0: level walk at run time; 1 / 2 / 3: min / mid / max
+  if (spec && zh_nibble_has(spec) && K != 5 && K != 9) return {f, ZhKernel::Nibble, spec};   // 9: the bit-at-a-time form
+  if (spec && zh_chain2_has(spec) && K != 5) return {f, ZhKernel::Chain2, spec};
+  return {f, ZhKernel::Chain, spec};
 }
 
 }  // namespace
@@ -319,24 +345,16 @@ static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, 
   for (size_t k = 0; k < sel.size(); ++k)
     for (uint32_t i = 0; i < bd[k].n_seg; ++i) weight[k] += sd[bd[k].first_seg + i].in_len;
 
-  // ---- kernel family per block (opts.kernel == 1 forces the generic kernel)
-  auto family = [&](size_t k) -> uint32_t {
-    uint32_t f = models[bd[k].model].kind & 255u;
-    if (opts.kernel == 1) f = ZH_FAM_GENERIC;              // force the generic kernel
-    if (f == ZH_FAM_STORE && (opts.reserved[0] == kPpOnlyMagic)) f = ZH_FAM_GENERIC;
-    if (opts.kernel == 3 && f == ZH_FAM_CM1) f = ZH_FAM_CHAIN;   // force the lane-per-component kernel
-    if (opts.kernel == 4 && f > ZH_FAM_CHAIN) f = ZH_FAM_CHAIN;  // lane-per-component kernel without model specialisation
-    // the method models of min's / mid's shape (zh_framing.cpp) are known to zh_nibble.hip only: the older kernels of these
-    // families carry the built-in HCOMP programs
-    if ((opts.kernel == 9 || opts.kernel == 7 || opts.kernel == 8 || opts.kernel == 5) && f > ZH_FAM_CHAIN && f < ZH_FAM_STORE) {
-      const uint32_t hk = (models[bd[k].model].kind >> 8) & 255u;
-      if (hk == ZH_NATIVE_HCOMP_M4 || hk == ZH_NATIVE_HCOMP_M3 || hk == ZH_NATIVE_HCOMP_M2 || hk == ZH_NATIVE_HCOMP_M2E) f = ZH_FAM_CHAIN;
-    }
-    if ((opts.kernel == 9 || opts.kernel == 7 || opts.kernel == 8 || opts.kernel == 5 || opts.kernel == 4) && (f == ZH_FAM_CHAIN_MID8 || f == ZH_FAM_CHAIN_MIN1)) f = ZH_FAM_CHAIN;
-    return f;
-  };
+  // ---- blocks grouped by route (route_block): one group, one kernel
+  const bool pp_only = opts.reserved[0] == kPpOnlyMagic;
+  const bool prof = getenv("ZPAQHIP_PROF") != nullptr;   // diagnostic build with in-kernel stamps
   std::vector<std::vector<uint32_t>> groups(ZH_NFAM_HOST);
-  for (size_t k = 0; k < sel.size(); ++k) groups[family(k)].push_back((uint32_t)k);
+  ZhRoute route_of[ZH_NFAM_HOST] = {};
+  for (size_t k = 0; k < sel.size(); ++k) {
+    const ZhRoute r = route_block(models[bd[k].model], opts, pp_only);
+    route_of[r.group] = r;
+    groups[r.group].push_back((uint32_t)k);
+  }
 
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
@@ -388,7 +406,7 @@ static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, 
     uint32_t want = opts.max_concurrent ? opts.max_concurrent : 256u;   // one block per CU by default
     // single-CM blocks beyond one per CU: two per workgroup (zh_decode_cm_x2: 32 LDS windows each instead of 64), so a stream
     // of many blocks uses all four SIMDs of a CU; opts.kernel == 6 forces that form, 2 the one-block form (A/B runs, tests)
-    cm_x2[g] = g == ZH_FAM_CM1 && !getenv("ZPAQHIP_PROF") && opts.kernel != 2 &&
+    cm_x2[g] = route_of[g].kernel == ZhKernel::Cm && !prof && opts.kernel != 2 &&
                (opts.kernel == 6 || (!opts.max_concurrent && groups[g].size() > 256));
     if (cm_x2[g]) want = opts.max_concurrent ? opts.max_concurrent : 512u;
     slots_of[g] = (uint32_t)std::min<uint64_t>({(uint64_t)want, max_slots, (uint64_t)groups[g].size()});
@@ -445,44 +463,41 @@ static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, 
     L.queue = (uint32_t *)c->queue.p + 8 * g;           // one work-queue head per launch
     L.n_blocks = (uint32_t)groups[g].size();
     L.budget = opts.zpaql_budget;
-    L.flags = opts.reserved[0] == kPpOnlyMagic ? ZH_LAUNCH_PP_ONLY : 0u;
-    const bool prof = getenv("ZPAQHIP_PROF") != nullptr;   // diagnostic build with in-kernel stamps
+    L.flags = pp_only ? ZH_LAUNCH_PP_ONLY : 0u;
     if (prof) L.debug = (uint64_t *)((uint8_t *)c->queue.p + kQueueBytes);
-    if (g == ZH_FAM_STORE) {
-      HIPCHK(zh_launch_store(&L, slots_of[g], stream));
-      P.has_store = true; P.store_launch = L; P.store_base = base_of[g]; P.store_count = groups[g].size(); P.store_slots = slots_of[g];
+    const ZhRoute &r = route_of[g];
+    switch (r.kernel) {
+      case ZhKernel::Generic: HIPCHK(zh_launch_generic(&L, slots_of[g], stream)); break;
+      case ZhKernel::Store:
+        HIPCHK(zh_launch_store(&L, slots_of[g], stream));
+        P.has_store = true; P.store_launch = L; P.store_base = base_of[g]; P.store_count = groups[g].size(); P.store_slots = slots_of[g];
+        break;
+      case ZhKernel::Cm:
+        if (prof) HIPCHK(zh_launch_cm_prof(&L, slots_of[g], stream));
+        else if (cm_x2[g]) HIPCHK(zh_launch_cm_x2(&L, slots_of[g] / 2, stream));
+        else HIPCHK(zh_launch_cm(&L, slots_of[g], stream));
+        break;
+      case ZhKernel::Chain: {
+        int pcall = 0;                                   // any model with PCOMP memory: the variant with translated post-processors
+        for (uint32_t k : groups[g]) pcall |= (models[bd[k].model].ph | models[bd[k].model].pm) != 0;
+        HIPCHK(zh_launch_chain(&L, slots_of[g], stream, r.spec, prof, pcall));
+        break;
+      }
+      case ZhKernel::Chain2: HIPCHK(zh_launch_chain2(&L, slots_of[g], stream, r.spec, prof)); break;   // per-model bit loop
+      case ZhKernel::Nibble: HIPCHK(zh_launch_nibble(&L, slots_of[g], stream, r.spec, prof)); break;   // a nibble at a time
     }
-    else if (g == ZH_FAM_CM1 && prof) HIPCHK(zh_launch_cm_prof(&L, slots_of[g], stream));
-    else if (g == ZH_FAM_CM1 && cm_x2[g]) HIPCHK(zh_launch_cm_x2(&L, slots_of[g] / 2, stream));
-    else if (g == ZH_FAM_CM1) HIPCHK(zh_launch_cm(&L, slots_of[g], stream));
-    else if (g == ZH_FAM_CHAIN_MID8) HIPCHK(zh_launch_nibble(&L, slots_of[g], stream, 5, prof));   // mid's shape, eight mixer inputs
-    else if (g == ZH_FAM_CHAIN_MIN1) HIPCHK(zh_launch_nibble(&L, slots_of[g], stream, 6, prof));   // one ICM on min's loop
-#ifdef ZH_WITH_CHAIN3
-    else if (g > ZH_FAM_CHAIN && zh_chain3_has(g - ZH_FAM_CHAIN) && (opts.kernel == 7 || opts.kernel == 8))   // decoder ‖ model ‖ helper wave: experiment build only
-      HIPCHK(zh_launch_chain3(&L, slots_of[g], stream, g - ZH_FAM_CHAIN, prof ? 2 : opts.kernel == 7));
-#endif
-    else if (g > ZH_FAM_CHAIN && zh_nibble_has(g - ZH_FAM_CHAIN) && opts.kernel != 9 && opts.kernel != 5)   // min / mid a nibble at a time (zh_nibble.hip); 9: the bit-at-a-time form below
-      HIPCHK(zh_launch_nibble(&L, slots_of[g], stream, g - ZH_FAM_CHAIN, prof));
-    else if (g > ZH_FAM_CHAIN && zh_chain2_has(g - ZH_FAM_CHAIN) && opts.kernel != 5)   // per-model bit loop (zh_chain2.hip)
-      HIPCHK(zh_launch_chain2(&L, slots_of[g], stream, g - ZH_FAM_CHAIN, prof));
-    else if (g >= ZH_FAM_CHAIN) {
-      int pcall = 0;                                     // any model with PCOMP memory: the variant with translated post-processors
-      for (uint32_t k : groups[g]) pcall |= (models[bd[k].model].ph | models[bd[k].model].pm) != 0;
-      HIPCHK(zh_launch_chain(&L, slots_of[g], stream, g - ZH_FAM_CHAIN, prof, pcall));
-    }
-    else HIPCHK(zh_launch_generic(&L, slots_of[g], stream));
     if (side_by_side) {                                  // join: the launch stream goes on when every family is done
       HIPCHK(hipEventRecord(c->fam_ev[g], stream));
       HIPCHK(hipStreamWaitEvent(launch_stream, c->fam_ev[g], 0));
     }
     ++launches;
     slots = std::max(slots, slots_of[g]);
-    kind_used = std::max(kind_used, g == ZH_FAM_STORE ? 1u : std::min(g, (uint32_t)ZH_FAM_CHAIN) + 1);
+    kind_used = std::max(kind_used, r.kernel == ZhKernel::Generic || r.kernel == ZhKernel::Store ? 1u : r.kernel == ZhKernel::Cm ? 2u : 3u);
   }
   HIPCHK(hipEventRecord(c->ev1, stream));
   P.total_in = total_in; P.total_model = total_model;
   P.launches = launches; P.slots = slots; P.kind_used = kind_used;
-  P.prof = getenv("ZPAQHIP_PROF") != nullptr;
+  P.prof = prof;
   P.active = true;
   return ZPAQHIP_OK;
 }
@@ -1182,18 +1197,19 @@ int zpaqhip_block_costs(const uint8_t *in, size_t in_len, const zpaqhip_block *b
       zpaqhip_err e2{};
       uint64_t w = 6000;                                  // a header the model builder refuses costs nothing real; keep it finite
       if (build_model(in + B.hdr_off, B.hdr_len, m, code, &e2) == ZPAQHIP_OK) {
-        const uint32_t fam = m.kind & 255u;
+        const ZhRoute r = route_block(m, resolve_opts(nullptr), false);
         const bool pcomp = (m.ph | m.pm) != 0;
         // measured cycles of the owning workgroup per plaintext byte (profiles/r03: 256 x 4 MiB, one block per CU), rounded;
         // estimates for the fallback kernels
-        w = fam == ZH_FAM_STORE ? (pcomp ? 120u : 30u)                // zh_store.hip: wave-wide copy / LZ77 / inverse BWT
-            : fam == ZH_FAM_CM1 ? kCm1Marker                         // zh_cm.hip: by coded / plain ratio, below
-            : fam == ZH_FAM_CHAIN + 1 ? 3800u : fam == ZH_FAM_CHAIN + 2 ? 6800u : fam == ZH_FAM_CHAIN + 3 ? 16600u   // zh_nibble.hip min / mid, zh_chain2.hip max (profiles/r05)
-            : fam == ZH_FAM_CHAIN_MID8 ? 7000u                        // zh_nibble.hip, eight mixer inputs
-            : fam == ZH_FAM_CHAIN_MIN1 ? 3800u                        // zh_nibble.hip, one ICM on min's loop
-            : fam == ZH_FAM_CHAIN ? 4000u + 2200u * m.n               // zh_chain.hip: level walk at run time
-            : 10000u + 16000u * m.n;                                  // zh_generic.hip: one lane, tables in HBM
-        if (pcomp && fam != ZH_FAM_STORE) w += w == kCm1Marker ? (uint64_t)-1 : 1500u;       // (marker - 1: single CM with a post-processor)
+        switch (r.kernel) {
+          case ZhKernel::Store: w = pcomp ? 120u : 30u; break;          // zh_store.hip: wave-wide copy / LZ77 / inverse BWT
+          case ZhKernel::Cm: w = kCm1Marker; break;                      // zh_cm.hip: by coded / plain ratio, below
+          case ZhKernel::Nibble: w = r.spec == 2 ? 6800u : r.spec == 5 ? 7000u : 3800u; break;   // zh_nibble.hip: mid, mid8; min, min1 (profiles/r05)
+          case ZhKernel::Chain2: w = 16600u; break;                      // zh_chain2.hip: max (profiles/r05)
+          case ZhKernel::Chain: w = 4000u + 2200u * m.n; break;          // zh_chain.hip: level walk at run time
+          case ZhKernel::Generic: w = 10000u + 16000u * m.n; break;      // zh_generic.hip: one lane, tables in HBM
+        }
+        if (pcomp && r.kernel != ZhKernel::Store) w += w == kCm1Marker ? (uint64_t)-1 : 1500u;   // (marker - 1: single CM with a post-processor)
       }
       it = per_byte.emplace(key, w).first;
     }

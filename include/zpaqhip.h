@@ -274,6 +274,39 @@ int zpaqhip_read_device_tables(zpaqhip_ctx *ctx, uint16_t *squash, int16_t *stre
 int zpaqhip_block_pcomp(zpaqhip_ctx *ctx, const uint8_t *in, size_t in_len, uint32_t block,
                         uint8_t *out, size_t out_cap, size_t *out_len, zpaqhip_err *err);
 
+/* ---- compression: the other half of the reference's public surface ----------------------------------------------
+ * LibZPAQ.compress / Compressor / Encoder (Compressor.cs:27-299, Encoder.cs:26-104) at the Compressor level: the caller
+ * gives the model (header and optional PCOMP), no method strings.  Every coded byte comes out of a HIP kernel. */
+typedef struct zpaqhip_compress_opts {
+  uint32_t struct_size;     /* = sizeof(zpaqhip_compress_opts) */
+  uint32_t flags;           /* bit0: store SHA-1 (253 + digest, else 254); bit1: write the 13-byte tag; NULL opts = 3 */
+  uint32_t kernel;          /* 0 auto: single-CM models of the `a<<= K  *d=a  halt` shape (K >= 9) on the window-parallel
+                               encoder, the rest on the generic one; 1 every block on the generic encoder (cross-check) */
+  uint32_t reserved0;
+  uint64_t batch_blocks;    /* blocks per device batch; 0 = sized from free device memory */
+  uint64_t slot_bytes;      /* test knob: device bytes reserved per block for coded data before the overflow path; 0 = auto
+                               (coded bytes + 1/8 + 4096).  A block that does not fit is coded again with a worst-case slot:
+                               the output never changes */
+  uint64_t reserved[2];
+} zpaqhip_compress_opts;
+
+/* Compressor.startBlock(hcomp) + startSegment(filename, size) + postProcess(pcomp) + compress() + endSegment(sha1) +
+ * endBlock() for each of n_blocks blocks (LibZPAQ.cs:296-323 framing, one segment per block).  `hdr` is the block header
+ * as the stream carries it (hsize lo, hsize hi, hh hm ph pm n, components, 0, HCOMP, 0); `pcomp` the PCOMP program as
+ * Compressor.postProcess sends it (NULL / 0 = PASS).  Block i codes in[in_off[i], in_off[i+1]); its size comment and
+ * SHA-1 describe orig[orig_off[i], orig_off[i+1]) (NULL = the coded bytes); filenames[i] (NULL, or a NULL entry = empty)
+ * is its segment's name.  out receives the blocks in order; block_off[0..n_blocks] (optional) their offsets.
+ * ZPAQHIP_E_OUTPUT_FULL with *out_len = the exact size needed when out_cap is short.  Modelled headers only (n >= 1):
+ * n == 0 gives ZPAQHIP_E_ARG.  zpaqhip_last_stats: kernel_ms = both encoder passes (and any re-encoding of overflowed
+ * blocks), init_ms = the model pass of the window-parallel CM encoder alone (part of kernel_ms; the rest is its coder pass
+ * and the generic encoder), launches = encoder launches (one more per batch with an overflowed block), in_bytes =
+ * plaintext, out_bytes = the stream, kernel_kind = 2 when a block ran on the window-parallel CM encoder, else 1. */
+int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
+                            const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
+                            const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
+                            uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
+                            const zpaqhip_compress_opts *opts, zpaqhip_err *err);
+
 #ifdef __cplusplus
 }
 #endif

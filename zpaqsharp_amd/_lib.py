@@ -52,6 +52,11 @@ class Stats(C.Structure):
                 ("kernel_kind", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class CompressOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("kernel", C.c_uint32), ("reserved0", C.c_uint32),
+                ("batch_blocks", C.c_uint64), ("slot_bytes", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+
 READ_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_int)
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_int)
 
@@ -59,7 +64,8 @@ WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_int)
 SYMBOLS = ("zpaqhip_version", "zpaqhip_strerror", "zpaqhip_device_count", "zpaqhip_ctx_create",
            "zpaqhip_ctx_destroy", "zpaqhip_last_stats", "zpaqhip_scan", "zpaqhip_decompress",
            "zpaqhip_decompress_segments", "zpaqhip_decompress_cb", "zpaqhip_decode_blocks_device", "zpaqhip_read_device_tables",
-           "zpaqhip_block_pcomp", "zpaqhip_decompress_multi", "zpaqhip_decompress_multi_stats", "zpaqhip_block_costs", "zpaqhip_multi_trim")
+           "zpaqhip_block_pcomp", "zpaqhip_decompress_multi", "zpaqhip_decompress_multi_stats", "zpaqhip_block_costs", "zpaqhip_multi_trim",
+           "zpaqhip_compress_blocks")
 
 _lib = None
 
@@ -104,5 +110,7 @@ def load():
                                                  C.POINTER(Stats), errp]
     L.zpaqhip_block_costs.argtypes = [vp, sz, C.POINTER(Block), sz, C.POINTER(Segment), sz, vp, errp]
     L.zpaqhip_multi_trim.restype = None
+    L.zpaqhip_compress_blocks.argtypes = [vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, sz, C.POINTER(sz), vp,
+                                          C.POINTER(CompressOpts), errp]
     _lib = L
     return L

@@ -12,7 +12,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import Block, Err, Opts, SegResult, Segment, Stats, UINT64_MAX
+from ._lib import Block, CompressOpts, Err, Opts, SegResult, Segment, Stats, UINT64_MAX
 
 
 class ZpaqError(RuntimeError):
@@ -190,6 +190,69 @@ class Context:
         if rc:
             _raise(err, rc)
         return sq, st, dt, dt2k, ns
+
+    def compress_blocks(self, model, blocks, *, pre=None, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 0,
+                        batch_blocks: int = 0, slot_bytes: int = 0) -> bytes:
+        """Compressor.startBlock .. endBlock for each block (LibZPAQ.cs:296-323 framing, one segment per block), coded on
+        the GPU: the same bytes the CPU stream writer (synth.compress_block) produces.  `model` is a models name or a
+        zpaql.Model.  A `+e8e9` model codes the forward E8E9 transform of each block; a `+lz77` model needs `pre`, the
+        pre-processed bytes of each block (size comment and SHA-1 still describe `blocks`)."""
+        from . import e8e9, models
+        m = models.get(model) if isinstance(model, str) else model
+        plain = [_as_u8(b) for b in blocks]
+        coded, orig = plain, None
+        if pre is not None:
+            if len(pre) != len(plain):
+                raise ValueError("pre needs one entry per block")
+            coded, orig = [_as_u8(p) for p in pre], plain
+        elif m.pcomp_cmd.startswith("e8e9"):
+            coded, orig = [e8e9.forward(b) for b in plain], plain
+        elif m.pcomp_cmd.startswith("lz77"):
+            raise ValueError("a +lz77 model needs the pre-processed blocks (pre=)")
+        flags = (1 if sha1 else 0) | (2 if tag else 0)
+        return self._compress(m.header, m.pcomp or b"", coded, orig, filenames, flags, kernel, batch_blocks, slot_bytes)[0]
+
+    def _compress(self, header: bytes, pcomp: bytes, coded, orig, filenames, flags: int, kernel: int, batch_blocks: int,
+                  slot_bytes: int, out_cap: Optional[int] = None):
+        """zpaqhip_compress_blocks on lists of blocks: (stream bytes, block offsets, status of the first call)."""
+        def cat(parts):
+            offs = np.zeros(len(parts) + 1, np.uint64)
+            offs[1:] = np.cumsum([p.size for p in parts], dtype=np.uint64) if parts else []
+            buf = np.concatenate(parts) if parts and offs[-1] else np.zeros(1, np.uint8)
+            return np.ascontiguousarray(buf), offs
+        n = len(coded)
+        cbuf, coffs = cat(coded)
+        obuf, ooffs = cat(orig) if orig is not None else (None, None)
+        names = None
+        if filenames is not None:
+            if len(filenames) != n:
+                raise ValueError("filenames needs one entry per block")
+            names = (C.c_char_p * max(1, n))(*[(f.encode() if isinstance(f, str) else f) for f in filenames])
+        o = CompressOpts()
+        o.struct_size = C.sizeof(CompressOpts)
+        o.flags, o.kernel, o.batch_blocks, o.slot_bytes = flags, kernel, batch_blocks, slot_bytes
+        hdr = _as_u8(header)
+        pc = _as_u8(pcomp) if pcomp else None
+        boffs = np.zeros(n + 1, np.uint64)
+        if out_cap is None:
+            out_cap = int(coffs[-1]) + int(coffs[-1]) // 8 + n * (len(header) + 128 + 4096) + 4096
+        first = None
+        for _ in range(2):
+            out = np.empty(max(1, out_cap), np.uint8)
+            err, got = Err(), C.c_size_t(0)
+            rc = self._L.zpaqhip_compress_blocks(self._h, hdr.ctypes.data, hdr.size, pc.ctypes.data if pc is not None else None,
+                                                 pc.size if pc is not None else 0, cbuf.ctypes.data, coffs.ctypes.data, n,
+                                                 obuf.ctypes.data if obuf is not None else None,
+                                                 ooffs.ctypes.data if ooffs is not None else None, names, out.ctypes.data, out_cap,
+                                                 C.byref(got), boffs.ctypes.data, C.byref(o), C.byref(err))
+            first = rc if first is None else first
+            if rc == -20 and got.value > out_cap:    # ZPAQHIP_E_OUTPUT_FULL: now the exact size is known
+                out_cap = got.value
+                continue
+            if rc:
+                _raise(err, rc)
+            return out[:got.value].tobytes(), boffs, first
+        _raise(err, rc)
 
     def decompress(self, stream, out_cap: Optional[int] = None, **opt) -> np.ndarray:
         """LibZPAQ.decompress(Reader, Writer) (LibZPAQ.cs:65-79) on host buffers."""

@@ -1,0 +1,46 @@
+"""LibZPAQ.compress(Reader, Writer, ...) (LibZPAQ.cs:84-108, 296-323) on the GPU, with a model in place of a method string.
+
+The input is cut into blocks of `block_size` bytes; each becomes one block with one segment (size comment, SHA-1), coded by
+Context.compress_blocks.  Method strings, LZ77 / BWT pre-processing and match finders are not part of this path: a model
+that needs a pre-processor other than E8E9 is refused there.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+from . import api
+from .decompresser import Reader, Writer
+
+
+def compress(reader: Reader, writer: Writer, model="l1", block_size: int = 1 << 22, context: Optional[api.Context] = None,
+             batch_blocks: int = 64) -> None:
+    if block_size < 1:
+        raise ValueError("block_size must be positive")
+    ctx = context or api.Context(0)
+    try:
+        blocks = []
+
+        def flush():
+            if blocks:
+                writer.write(ctx.compress_blocks(model, blocks))
+                blocks.clear()
+
+        # A Reader may return fewer bytes than asked before its end (Reader.cs:14-25): only an empty read ends the input,
+        # as in LibZPAQ.compress (LibZPAQ.cs:84-108).  Short reads are gathered into whole blocks.
+        cur = bytearray()
+        while True:
+            b = reader.read(block_size - len(cur))
+            if not b:
+                break
+            cur += b
+            if len(cur) == block_size:
+                blocks.append(bytes(cur))
+                cur.clear()
+                if len(blocks) >= batch_blocks:
+                    flush()
+        if cur:
+            blocks.append(bytes(cur))
+        flush()
+    finally:
+        if context is None:
+            ctx.close()

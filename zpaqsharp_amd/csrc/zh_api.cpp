@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 
+#include "zh_ctx_view.h"
 #include "zh_host.h"
 #include "zh_zpaql_native.h"
 
@@ -1506,3 +1507,8 @@ int zpaqhip_decompress_cb(zpaqhip_ctx *c, zpaqhip_read_fn read_fn, zpaqhip_write
 }
 
 }  // extern "C"
+
+// zh_compress.cpp works on a context through this view (zh_ctx_view.h)
+zh::CtxView zh::ctx_view(zpaqhip_ctx *c) {
+  return zh::CtxView{c->device, c->stream, c->ev0, c->ev1, (const ZhTables *)c->tables.p, &c->stats, c->mem_share};
+}

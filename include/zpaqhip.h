@@ -276,7 +276,8 @@ int zpaqhip_block_pcomp(zpaqhip_ctx *ctx, const uint8_t *in, size_t in_len, uint
 
 /* ---- compression: the other half of the reference's public surface ----------------------------------------------
  * LibZPAQ.compress / Compressor / Encoder (Compressor.cs:27-299, Encoder.cs:26-104) at the Compressor level: the caller
- * gives the model (header and optional PCOMP), no method strings.  Every coded byte comes out of a HIP kernel. */
+ * gives the model (header and optional PCOMP); zpaqhip_compress_method_blocks below takes a method's numbers instead.
+ * Every coded byte comes out of a HIP kernel. */
 typedef struct zpaqhip_compress_opts {
   uint32_t struct_size;     /* = sizeof(zpaqhip_compress_opts) */
   uint32_t flags;           /* bit0: store SHA-1 (253 + digest, else 254); bit1: write the 13-byte tag; NULL opts = 3 */
@@ -306,6 +307,35 @@ int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len
                             const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
                             uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
                             const zpaqhip_compress_opts *opts, zpaqhip_err *err);
+
+/* ---- compression with a method: LibZPAQ.compressBlock (LibZPAQ.cs:296-323) with the pre-processing of LZBuffer and E8E9 ----
+ * args are the nine numbers of an expanded method string as LibZPAQ.makeConfig reads them (LibZPAQ.cs:394-416; what
+ * zpaqsharp_amd.method.parse_args returns).  level = args[1] & 3; 4 <= args[1] <= 7 applies forward E8E9 (LibZPAQ.cs:372-384)
+ * first.  Level 1 writes LZBuffer's bit-packed codes, level 2 its byte-aligned ones (LZBuffer.cs:96-112), with a greedy
+ * parse: key k = max(4, args[2]) (level 1) or max(args[2], 3) (level 2); position i starts a match iff the nearest earlier
+ * position with the same k bytes lies within 2^23 - 1 (level 1) or 2^24 - 1 (level 2); the match takes as many bytes as
+ * match, up to 2^16 (level 1) or args[2] + 319 (level 2).  Everything runs on the GPU (zh_pre_lz.hip).
+ * Refused with ZPAQHIP_E_ARG: level 3 (BWT); level 2 with args[2] outside 1..64; at level 1 or 2 a block longer than
+ * 2^(args[0] + 20) bytes (its offsets would wrap the PCOMP's M) or than 2^31 - 1 bytes. */
+
+/* The pre-processed bytes of each block in[in_off[i], in_off[i+1]), back to back in out; out_off[0..n_blocks] (optional)
+ * their offsets.  ZPAQHIP_E_OUTPUT_FULL with *out_len = the exact size needed when out_cap is short.
+ * zpaqhip_last_stats: kernel_ms = init_ms = the pre-processing kernels. */
+int zpaqhip_preprocess_blocks(zpaqhip_ctx *ctx, const int32_t args[9], const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
+                              uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off, zpaqhip_err *err);
+
+/* compressBlock of a method for each block, one segment per block, framing as zpaqhip_compress_blocks.  hdr / pcomp are
+ * the block header and PCOMP of makeConfig's text for the method; the size comment and SHA-1 (zh_sha1_dev) describe the
+ * plaintext.  n >= 1 headers: the pre-processed bytes stay in device memory and go to the encoders of
+ * zpaqhip_compress_blocks, whose opts (kernel, batch_blocks, slot_bytes) apply.  n == 0 headers: the store layout of
+ * Encoder.compress without a model (selector or PCOMP header, then the bytes, in 4-byte big-endian length-prefixed chunks
+ * of 65 536 bytes, then four zero bytes) in a level 2 block (Compressor.cs:92-96); opts.batch_blocks applies.
+ * zpaqhip_last_stats: init_ms = the pre-processing alone, kernel_ms = pre-processing and encoder passes, kernel_kind as
+ * for zpaqhip_compress_blocks for modelled blocks and 0 when every block is unmodelled. */
+int zpaqhip_compress_method_blocks(zpaqhip_ctx *ctx, const int32_t args[9], const uint8_t *hdr, size_t hdr_len,
+                                   const uint8_t *pcomp, size_t pcomp_len, const uint8_t *in, const uint64_t *in_off,
+                                   size_t n_blocks, const char *const *filenames, uint8_t *out, size_t out_cap, size_t *out_len,
+                                   uint64_t *block_off, const zpaqhip_compress_opts *opts, zpaqhip_err *err);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,14 @@ def _as_u8(data) -> np.ndarray:
     return np.frombuffer(bytes(data) if not isinstance(data, (bytes, bytearray, memoryview)) else data, dtype=np.uint8)
 
 
+def _cat(parts):
+    """Blocks back to back, and their offsets (len(parts) + 1 of them)."""
+    offs = np.zeros(len(parts) + 1, np.uint64)
+    offs[1:] = np.cumsum([p.size for p in parts], dtype=np.uint64) if parts else []
+    buf = np.concatenate(parts) if parts and offs[-1] else np.zeros(1, np.uint8)
+    return np.ascontiguousarray(buf), offs
+
+
 def version() -> int:
     return _lib.load().zpaqhip_version()
 
@@ -212,17 +220,53 @@ class Context:
         flags = (1 if sha1 else 0) | (2 if tag else 0)
         return self._compress(m.header, m.pcomp or b"", coded, orig, filenames, flags, kernel, batch_blocks, slot_bytes)[0]
 
+    def preprocess_blocks(self, method: str, blocks) -> List[bytes]:
+        """What LibZPAQ.compressBlock feeds the coder for `method` (LibZPAQ.cs:296-311: E8E9, LZBuffer levels 1 / 2), computed
+        on the GPU for each block: equal to tools.methods.preprocess.  Useful on its own as `pre=` of compress_blocks."""
+        from . import method as mth
+        args = mth.parse_args(method)[1]
+        plain = [_as_u8(b) for b in blocks]
+        mth.check_blocks(args, [p.size for p in plain])
+        buf, offs = _cat(plain)
+        a = (C.c_int32 * 9)(*args)
+        cap = sum(mth.pre_bound(args, p.size) for p in plain)
+        oo = np.zeros(len(plain) + 1, np.uint64)
+        for _ in range(2):
+            out = np.empty(max(1, cap), np.uint8)
+            err, got = Err(), C.c_size_t(0)
+            rc = self._L.zpaqhip_preprocess_blocks(self._h, a, buf.ctypes.data, offs.ctypes.data, len(plain), out.ctypes.data, cap,
+                                                   C.byref(got), oo.ctypes.data, C.byref(err))
+            if rc == -20 and got.value > cap:
+                cap = got.value
+                continue
+            if rc:
+                _raise(err, rc)
+            return [out[int(oo[i]):int(oo[i + 1])].tobytes() for i in range(len(plain))]
+        _raise(err, rc)
+
+    def compress_method(self, method: str, blocks, *, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 0,
+                        batch_blocks: int = 0, slot_bytes: int = 0) -> bytes:
+        """LibZPAQ.compressBlock(method) for each block (LibZPAQ.cs:296-323, one segment per block) on the GPU: the bytes
+        tools.methods.compress_block writes.  Levels 0, 1 and 2 with or without E8E9; the model of an n >= 1 method codes
+        the pre-processed bytes on the encoders of compress_blocks (kernel, batch_blocks, slot_bytes as there), an n = 0
+        method stores them.  ValueError, before the device is touched, for level 3, a level 2 `m` outside 1..64 and a
+        block longer than 2^(args[0] + 20) bytes at level 1 or 2."""
+        from . import method as mth
+        args = mth.parse_args(method)[1]
+        plain = [_as_u8(b) for b in blocks]
+        mth.check_blocks(args, [p.size for p in plain])
+        model, _ = mth.model_of(method)
+        cap = sum(mth.pre_bound(args, p.size) for p in plain) + len(plain) * (len(model.header) + 2 * len(model.pcomp) + 4096) + 4096
+        return self._compress(model.header, model.pcomp or b"", plain, None, filenames, (1 if sha1 else 0) | (2 if tag else 0),
+                              kernel, batch_blocks, slot_bytes, out_cap=cap, args=args)[0]
+
     def _compress(self, header: bytes, pcomp: bytes, coded, orig, filenames, flags: int, kernel: int, batch_blocks: int,
-                  slot_bytes: int, out_cap: Optional[int] = None):
-        """zpaqhip_compress_blocks on lists of blocks: (stream bytes, block offsets, status of the first call)."""
-        def cat(parts):
-            offs = np.zeros(len(parts) + 1, np.uint64)
-            offs[1:] = np.cumsum([p.size for p in parts], dtype=np.uint64) if parts else []
-            buf = np.concatenate(parts) if parts and offs[-1] else np.zeros(1, np.uint8)
-            return np.ascontiguousarray(buf), offs
+                  slot_bytes: int, out_cap: Optional[int] = None, args: Optional[List[int]] = None):
+        """zpaqhip_compress_blocks (zpaqhip_compress_method_blocks with `args`: `coded` is then the plaintext) on lists of
+        blocks: (stream bytes, block offsets, status of the first call)."""
         n = len(coded)
-        cbuf, coffs = cat(coded)
-        obuf, ooffs = cat(orig) if orig is not None else (None, None)
+        cbuf, coffs = _cat(coded)
+        obuf, ooffs = _cat(orig) if orig is not None else (None, None)
         names = None
         if filenames is not None:
             if len(filenames) != n:
@@ -240,11 +284,17 @@ class Context:
         for _ in range(2):
             out = np.empty(max(1, out_cap), np.uint8)
             err, got = Err(), C.c_size_t(0)
-            rc = self._L.zpaqhip_compress_blocks(self._h, hdr.ctypes.data, hdr.size, pc.ctypes.data if pc is not None else None,
-                                                 pc.size if pc is not None else 0, cbuf.ctypes.data, coffs.ctypes.data, n,
-                                                 obuf.ctypes.data if obuf is not None else None,
-                                                 ooffs.ctypes.data if ooffs is not None else None, names, out.ctypes.data, out_cap,
-                                                 C.byref(got), boffs.ctypes.data, C.byref(o), C.byref(err))
+            if args is not None:
+                rc = self._L.zpaqhip_compress_method_blocks(
+                    self._h, (C.c_int32 * 9)(*args), hdr.ctypes.data, hdr.size, pc.ctypes.data if pc is not None else None,
+                    pc.size if pc is not None else 0, cbuf.ctypes.data, coffs.ctypes.data, n, names, out.ctypes.data, out_cap,
+                    C.byref(got), boffs.ctypes.data, C.byref(o), C.byref(err))
+            else:
+                rc = self._L.zpaqhip_compress_blocks(self._h, hdr.ctypes.data, hdr.size, pc.ctypes.data if pc is not None else None,
+                                                     pc.size if pc is not None else 0, cbuf.ctypes.data, coffs.ctypes.data, n,
+                                                     obuf.ctypes.data if obuf is not None else None,
+                                                     ooffs.ctypes.data if ooffs is not None else None, names, out.ctypes.data,
+                                                     out_cap, C.byref(got), boffs.ctypes.data, C.byref(o), C.byref(err))
             first = rc if first is None else first
             if rc == -20 and got.value > out_cap:    # ZPAQHIP_E_OUTPUT_FULL: now the exact size is known
                 out_cap = got.value

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "zh_compress.h"
 #include "zh_ctx_view.h"
 #include "zh_enc.h"
 
@@ -73,6 +74,17 @@ extern "C" int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, siz
                                        const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
                                        uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
                                        const zpaqhip_compress_opts *opts, zpaqhip_err *err) {
+  return compress_impl(ctx, hdr, hdr_len, pcomp, pcomp_len, in, in_off, n_blocks, orig, orig_off, filenames, out, out_cap, out_len,
+                       block_off, opts, nullptr, err);
+}
+
+// `pre` (the method path): block i's coded bytes are pre-processed on the device from its plaintext in[in_off[i], in_off[i+1]),
+// which the size comment and SHA-1 describe; orig is then NULL.
+int zh::compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
+                      const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
+                      const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
+                      uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
+                      const zpaqhip_compress_opts *opts, PreStage *pre, zpaqhip_err *err) {
   if (!ctx || !hdr || !out_len || (!out && out_cap) || (n_blocks && !in_off) || (orig && !orig_off) || (pcomp_len && !pcomp) ||
       pcomp_len > 65535) {
     set_err(err, ZPAQHIP_E_ARG, -1, -1);
@@ -132,11 +144,11 @@ extern "C" int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, siz
   const uint64_t budget = (free_b > (2ull << 30) ? free_b - (1ull << 30) : free_b / 2) / std::max(1u, v.mem_share);
   const uint64_t arena_stride = align_up(M.arena_bytes, 256);
 
-  auto coded_len = [&](size_t i) { return np + (in_off[i + 1] - in_off[i]); };
+  auto coded_len = [&](size_t i) { return np + (pre ? pre->bound(i) : in_off[i + 1] - in_off[i]); };   // (an upper bound with pre)
   auto plain_len = [&](size_t i) { return orig ? orig_off[i + 1] - orig_off[i] : in_off[i + 1] - in_off[i]; };
   auto block_cost = [&](size_t i) {
     const uint64_t n = coded_len(i);
-    uint64_t c = n + (o.slot_bytes ? o.slot_bytes : auto_slot(n)) + 64 + (orig && want_sha ? plain_len(i) : 0);
+    uint64_t c = n + (o.slot_bytes ? o.slot_bytes : auto_slot(n)) + 64 + (orig && want_sha ? plain_len(i) : 0) + (pre ? pre->scratch(i) : 0);
     if (route_encode(M, o, n) == EncKernel::Cm) c += 24 * n + 4 * (ZH_ENC_CM_KEYS + 1);
     return c;
   };
@@ -151,22 +163,49 @@ extern "C" int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, siz
       while (b1 < n_blocks && b1 - b0 < 4096 && cost + block_cost(b1) <= budget / 2) cost += block_cost(b1++);
     const size_t nb = b1 - b0;
 
+    // the coded sequences in block order (with pre, each in room for its bound), filled from the host or on the device
+    std::vector<uint64_t> boff(nb), blen(nb), sha_off;
+    const uint8_t *sha_base = nullptr;
+    uint64_t in_total = 0;
+    for (size_t j = 0; j < nb; ++j) {
+      boff[j] = in_total;
+      blen[j] = coded_len(b0 + j);
+      in_total += align_up(blen[j], 16);
+    }
+    DevMem d_in, d_slots, d_desc, d_res, d_queue, d_arena, d_la, d_lb, d_bases, d_P, d_orig, d_seg, d_dig;
+    HIPCHK(d_in.alloc(in_total));
+    float pre_ms = 0;
+    if (pre) {
+      std::vector<uint64_t> len;
+      rc = pre->run(v, b0, b1, d_in.as<uint8_t>(), boff, prefix, len, &sha_base, sha_off, pre_ms, err);
+      if (rc) return rc;
+      for (size_t j = 0; j < nb; ++j) blen[j] = np + len[j];
+      st.init_ms += pre_ms;
+      st.kernel_ms += pre_ms;
+    } else {
+      std::vector<uint8_t> h_in(in_total);
+      for (size_t j = 0; j < nb; ++j) {
+        memcpy(h_in.data() + boff[j], prefix.data(), np);
+        if (blen[j] > np) memcpy(h_in.data() + boff[j] + np, in + in_off[b0 + j], blen[j] - np);
+      }
+      HIPCHK(hipMemcpy(d_in.p, h_in.data(), in_total, hipMemcpyHostToDevice));
+    }
+
     // layout: CM blocks first (blockIdx = index), then the generic ones (work queue)
     std::vector<size_t> order;
-    for (size_t i = b0; i < b1; ++i) if (route_encode(M, o, coded_len(i)) == EncKernel::Cm) order.push_back(i);
+    for (size_t i = b0; i < b1; ++i) if (route_encode(M, o, blen[i - b0]) == EncKernel::Cm) order.push_back(i);
     const size_t n_cm = order.size();
-    for (size_t i = b0; i < b1; ++i) if (route_encode(M, o, coded_len(i)) != EncKernel::Cm) order.push_back(i);
+    for (size_t i = b0; i < b1; ++i) if (route_encode(M, o, blen[i - b0]) != EncKernel::Cm) order.push_back(i);
     any_cm |= n_cm > 0;
     std::vector<ZhEncBlock> desc(nb);
     std::vector<size_t> slot_of(nb);              // batch-relative block -> index in order
-    uint64_t in_total = 0, slot_total = 0, scr_total = 0, orig_total = 0;
+    uint64_t slot_total = 0, scr_total = 0, orig_total = 0;
     for (size_t k = 0; k < nb; ++k) {
       const size_t i = order[k];
       slot_of[i - b0] = k;
       ZhEncBlock &d = desc[k];
-      d.n = coded_len(i);
-      d.in_off = in_total;
-      in_total += align_up(d.n, 16);
+      d.n = blen[i - b0];
+      d.in_off = boff[i - b0];
       d.slot_cap = o.slot_bytes ? o.slot_bytes : auto_slot(d.n);
       d.slot_off = slot_total;
       slot_total += align_up(d.slot_cap, 256);
@@ -174,23 +213,12 @@ extern "C" int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, siz
       if (k < n_cm) scr_total += align_up(d.n, 4);
       if (orig && want_sha) orig_total += align_up(plain_len(i), 16);
     }
-    std::vector<uint8_t> h_in(in_total);
-    for (size_t k = 0; k < nb; ++k) {
-      const size_t i = order[k];
-      memcpy(h_in.data() + desc[k].in_off, prefix.data(), np);
-      if (in_off[i + 1] > in_off[i]) memcpy(h_in.data() + desc[k].in_off + np, in + in_off[i], in_off[i + 1] - in_off[i]);
-    }
-    DevMem d_in, d_slots, d_desc, d_res, d_queue, d_arena, d_la, d_lb, d_bases, d_P, d_orig, d_seg, d_dig;
-    HIPCHK(d_in.alloc(in_total));
     HIPCHK(d_slots.alloc(slot_total));
     HIPCHK(d_desc.alloc(nb * sizeof(ZhEncBlock)));
     HIPCHK(d_res.alloc(nb * sizeof(ZhEncResult)));
     HIPCHK(d_queue.alloc(256));
-    HIPCHK(hipMemcpy(d_in.p, h_in.data(), in_total, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_desc.p, desc.data(), nb * sizeof(ZhEncBlock), hipMemcpyHostToDevice));
     HIPCHK(hipMemset(d_queue.p, 0, 256));
-    h_in.clear();
-    h_in.shrink_to_fit();
 
     ZhEncLaunch L;
     memset(&L, 0, sizeof L);
@@ -239,7 +267,10 @@ extern "C" int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, siz
     if (want_sha) {                               // SHA-1 of what the size comment describes (Compressor.endSegment)
       std::vector<uint64_t> seg(2 * nb);
       const uint8_t *base = d_in.as<uint8_t>();
-      if (orig) {
+      if (pre) {
+        for (size_t k = 0; k < nb; ++k) { seg[2 * k] = sha_off[order[k] - b0]; seg[2 * k + 1] = plain_len(order[k]); }
+        base = sha_base;
+      } else if (orig) {
         std::vector<uint8_t> h_orig(orig_total);
         uint64_t off = 0;
         for (size_t k = 0; k < nb; ++k) {
@@ -264,7 +295,7 @@ extern "C" int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, siz
     HIPCHK(hipEventElapsedTime(&ms, v.ev0, v.ev1));
     HIPCHK(hipEventElapsedTime(&ms_model, v.ev0, ev_model.e));
     st.kernel_ms += ms;
-    st.init_ms += ms_model;
+    if (!pre) st.init_ms += ms_model;
     if (want_sha) HIPCHK(hipMemcpy(digest.data(), d_dig.p, nb * 20, hipMemcpyDeviceToHost));
     std::vector<ZhEncResult> res(nb);
     HIPCHK(hipMemcpy(res.data(), d_res.p, nb * sizeof(ZhEncResult), hipMemcpyDeviceToHost));

@@ -280,7 +280,8 @@ int zpaqhip_block_pcomp(zpaqhip_ctx *ctx, const uint8_t *in, size_t in_len, uint
  * Every coded byte comes out of a HIP kernel. */
 typedef struct zpaqhip_compress_opts {
   uint32_t struct_size;     /* = sizeof(zpaqhip_compress_opts) */
-  uint32_t flags;           /* bit0: store SHA-1 (253 + digest, else 254); bit1: write the 13-byte tag; NULL opts = 3 */
+  uint32_t flags;           /* bit0: store SHA-1 (253 + digest, else 254); bit1: write the 13-byte tag; bit2 (zpaqhip_compress_method_blocks
+                               only): accept level 3 (BWT) methods; NULL opts = 3 */
   uint32_t kernel;          /* 0 auto: single-CM models of the `a<<= K  *d=a  halt` shape (K >= 9) on the window-parallel
                                encoder, the rest on the generic one; 1 every block on the generic encoder (cross-check) */
   uint32_t reserved0;
@@ -314,15 +315,25 @@ int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len
  * first.  Level 1 writes LZBuffer's bit-packed codes, level 2 its byte-aligned ones (LZBuffer.cs:96-112), with a greedy
  * parse: key k = max(4, args[2]) (level 1) or max(args[2], 3) (level 2); position i starts a match iff the nearest earlier
  * position with the same k bytes lies within 2^23 - 1 (level 1) or 2^24 - 1 (level 2); the match takes as many bytes as
- * match, up to 2^16 (level 1) or args[2] + 319 (level 2).  Everything runs on the GPU (zh_pre_lz.hip).
- * Refused with ZPAQHIP_E_ARG: level 3 (BWT); level 2 with args[2] outside 1..64; at level 1 or 2 a block longer than
- * 2^(args[0] + 20) bytes (its offsets would wrap the PCOMP's M) or than 2^31 - 1 bytes. */
+ * match, up to 2^16 (level 1) or args[2] + 319 (level 2).  Level 3 writes LZBuffer's Burrows-Wheeler transform
+ * (LZBuffer.cs:228-240: n + 5 bytes for n, the end of the block sorting below every byte) from a suffix array built by
+ * prefix doubling (zh_pre_bwt.hip); it is an opt-in: zpaqhip_compress_method_blocks takes it with bit2 of opts.flags,
+ * zpaqhip_bwt_blocks always.  Everything runs on the GPU (zh_pre_lz.hip, zh_pre_bwt.hip).
+ * Refused with ZPAQHIP_E_ARG: level 3 (BWT) without the opt-in (zpaqhip_preprocess_blocks: always); level 2 with args[2]
+ * outside 1..64; at level 1 or 2 a block longer than 2^(args[0] + 20) bytes (its offsets would wrap the PCOMP's M), at
+ * level 3 than 2^(args[0] + 20) - 4096 bytes (LibZPAQ.cs:289), or than 2^31 - 1 bytes. */
 
 /* The pre-processed bytes of each block in[in_off[i], in_off[i+1]), back to back in out; out_off[0..n_blocks] (optional)
  * their offsets.  ZPAQHIP_E_OUTPUT_FULL with *out_len = the exact size needed when out_cap is short.
  * zpaqhip_last_stats: kernel_ms = init_ms = the pre-processing kernels. */
 int zpaqhip_preprocess_blocks(zpaqhip_ctx *ctx, const int32_t args[9], const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
                               uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off, zpaqhip_err *err);
+
+/* LZBuffer's level 3 (BWT) of each block in[in_off[i], in_off[i+1]), after forward E8E9 when doe8 is not 0: n + 5 bytes per
+ * block, back to back in out; out_off, capacity and statistics as for zpaqhip_preprocess_blocks.  The only size limit is
+ * 2^31 - 1 bytes per block. */
+int zpaqhip_bwt_blocks(zpaqhip_ctx *ctx, int doe8, const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
+                       uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off, zpaqhip_err *err);
 
 /* compressBlock of a method for each block, one segment per block, framing as zpaqhip_compress_blocks.  hdr / pcomp are
  * the block header and PCOMP of makeConfig's text for the method; the size comment and SHA-1 (zh_sha1_dev) describe the

@@ -1,6 +1,6 @@
 """Compression rate of Context.compress_blocks (or, with --method, Context.compress_method) against the CPU stream writer.
 
-    python3 tools/compress_rate.py [--blocks 256] [--block-size 4194304] [--kinds T,R] [--model l1] [--method M]
+    python3 tools/compress_rate.py [--blocks 256] [--block-size 4194304] [--kinds T,R] [--model l1] [--method M] [--bwt]
 
 Per kind: plaintext MB/s from wall time, the time of each pass (zpaqhip_last_stats: init_ms = model pass, kernel_ms -
 init_ms = coder pass), and the CPU writer
@@ -8,7 +8,8 @@ init_ms = coder pass), and the CPU writer
 
 --method M: Context.compress_method(M) against synth.method_stream (16 host threads, its own greedy hash parse, so the
 ratios are compared, not the bytes); pre_ms = the device pre-processing (init_ms), encoder_ms = the rest of kernel_ms.
-The GPU stream is checked by a round trip through Context.decompress(verify_sha1=True).
+The GPU stream is checked by a round trip through Context.decompress(verify_sha1=True).  --bwt passes bwt=True, the
+opt-in a level 3 method needs (its transform is unique, but the CPU writer is still compared by ratio only).
 """
 import argparse
 import json
@@ -28,9 +29,9 @@ def run_method(ctx, a):
     for kind in a.kinds.split(","):
         blocks = [synth.plain(kind, i, a.block_size) for i in range(a.blocks)]
         mb = a.blocks * a.block_size / 1e6
-        ctx.compress_method(a.method, blocks[:1])                         # warm-up
+        ctx.compress_method(a.method, blocks[:1], bwt=a.bwt)              # warm-up
         t = time.perf_counter()
-        got = ctx.compress_method(a.method, blocks)
+        got = ctx.compress_method(a.method, blocks, bwt=a.bwt)
         gpu_s = time.perf_counter() - t
         st = ctx.stats()
         t = time.perf_counter()
@@ -53,6 +54,7 @@ def main():
     ap.add_argument("--kinds", default="T,R")
     ap.add_argument("--model", default="l1")
     ap.add_argument("--method", default=None)
+    ap.add_argument("--bwt", action="store_true", help="accept a level 3 (BWT) method")
     a = ap.parse_args()
     with z.Context(0) as ctx:
         if a.method:

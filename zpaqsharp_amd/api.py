@@ -244,21 +244,42 @@ class Context:
             return [out[int(oo[i]):int(oo[i + 1])].tobytes() for i in range(len(plain))]
         _raise(err, rc)
 
+    def bwt_blocks(self, blocks, e8e9: bool = False) -> List[bytes]:
+        """LZBuffer's level 3 (LZBuffer.cs:228-240) of each block on the GPU (zpaqhip_bwt_blocks): the Burrows-Wheeler
+        transform from a suffix array in which the end of the block sorts first, n + 5 bytes for n; with `e8e9`, of the
+        forward E8E9 transform of the block.  Equal to tools.methods.preprocess for `x0,3` / `x0,7`."""
+        plain = [_as_u8(b) for b in blocks]
+        for i, p in enumerate(plain):
+            if p.size > (1 << 31) - 1:
+                raise ValueError(f"block {i} has {p.size} bytes; a BWT block holds at most 2^31 - 1")
+        buf, offs = _cat(plain)
+        cap = sum(p.size + 5 for p in plain)
+        oo = np.zeros(len(plain) + 1, np.uint64)
+        out = np.empty(max(1, cap), np.uint8)
+        err, got = Err(), C.c_size_t(0)
+        rc = self._L.zpaqhip_bwt_blocks(self._h, int(bool(e8e9)), buf.ctypes.data, offs.ctypes.data, len(plain), out.ctypes.data, cap,
+                                        C.byref(got), oo.ctypes.data, C.byref(err))
+        if rc:
+            _raise(err, rc)
+        return [out[int(oo[i]):int(oo[i + 1])].tobytes() for i in range(len(plain))]
+
     def compress_method(self, method: str, blocks, *, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 0,
-                        batch_blocks: int = 0, slot_bytes: int = 0) -> bytes:
+                        batch_blocks: int = 0, slot_bytes: int = 0, bwt: bool = False) -> bytes:
         """LibZPAQ.compressBlock(method) for each block (LibZPAQ.cs:296-323, one segment per block) on the GPU: the bytes
-        tools.methods.compress_block writes.  Levels 0, 1 and 2 with or without E8E9; the model of an n >= 1 method codes
-        the pre-processed bytes on the encoders of compress_blocks (kernel, batch_blocks, slot_bytes as there), an n = 0
-        method stores them.  ValueError, before the device is touched, for level 3, a level 2 `m` outside 1..64 and a
-        block longer than 2^(args[0] + 20) bytes at level 1 or 2."""
+        tools.methods.compress_block writes.  Levels 0, 1 and 2 with or without E8E9, and with `bwt=True` level 3; the
+        model of an n >= 1 method codes the pre-processed bytes on the encoders of compress_blocks (kernel, batch_blocks,
+        slot_bytes as there), an n = 0 method stores them.  ValueError, before the device is touched, for level 3 without
+        `bwt=True`, a level 2 `m` outside 1..64 and a block longer than 2^(args[0] + 20) bytes at level 1 or 2 (4096
+        less at level 3)."""
         from . import method as mth
         args = mth.parse_args(method)[1]
         plain = [_as_u8(b) for b in blocks]
-        mth.check_blocks(args, [p.size for p in plain])
+        mth.check_blocks(args, [p.size for p in plain], bwt=bwt)
         model, _ = mth.model_of(method)
         cap = sum(mth.pre_bound(args, p.size) for p in plain) + len(plain) * (len(model.header) + 2 * len(model.pcomp) + 4096) + 4096
-        return self._compress(model.header, model.pcomp or b"", plain, None, filenames, (1 if sha1 else 0) | (2 if tag else 0),
-                              kernel, batch_blocks, slot_bytes, out_cap=cap, args=args)[0]
+        return self._compress(model.header, model.pcomp or b"", plain, None, filenames,
+                              (1 if sha1 else 0) | (2 if tag else 0) | (4 if bwt else 0), kernel, batch_blocks, slot_bytes, out_cap=cap,
+                              args=args)[0]
 
     def _compress(self, header: bytes, pcomp: bytes, coded, orig, filenames, flags: int, kernel: int, batch_blocks: int,
                   slot_bytes: int, out_cap: Optional[int] = None, args: Optional[List[int]] = None):

@@ -2,8 +2,8 @@
 
 The input is cut into blocks of `block_size` bytes; each becomes one block with one segment (size comment, SHA-1), coded by
 Context.compress_blocks (a model; a model that needs a pre-processor other than E8E9 is refused there) or, with `method`,
-by Context.compress_method (LibZPAQ.compressBlock's pre-processing levels 0, 1 and 2, with or without E8E9; BWT is not
-part of this path).
+by Context.compress_method (LibZPAQ.compressBlock's pre-processing levels 0, 1 and 2, with or without E8E9, and with
+`bwt=True` level 3, the Burrows-Wheeler transform; without the keyword a level 3 method is refused).
 """
 from __future__ import annotations
 
@@ -14,19 +14,19 @@ from .decompresser import Reader, Writer
 
 
 def compress(reader: Reader, writer: Writer, model="l1", block_size: int = 1 << 22, context: Optional[api.Context] = None,
-             batch_blocks: int = 64, method: Optional[str] = None) -> None:
+             batch_blocks: int = 64, method: Optional[str] = None, bwt: bool = False) -> None:
     if block_size < 1:
         raise ValueError("block_size must be positive")
     if method is not None:
         from . import method as mth
-        mth.check_blocks(mth.parse_args(method)[1], [block_size])
+        mth.check_blocks(mth.parse_args(method)[1], [block_size], bwt=bwt)
     ctx = context or api.Context(0)
     try:
         blocks = []
 
         def flush():
             if blocks:
-                writer.write(ctx.compress_blocks(model, blocks) if method is None else ctx.compress_method(method, blocks))
+                writer.write(ctx.compress_blocks(model, blocks) if method is None else ctx.compress_method(method, blocks, bwt=bwt))
                 blocks.clear()
 
         # A Reader may return fewer bytes than asked before its end (Reader.cs:14-25): only an empty read ends the input,

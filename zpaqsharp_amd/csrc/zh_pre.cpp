@@ -1,5 +1,5 @@
-// zh_pre.cpp — LibZPAQ.compressBlock for a method (LibZPAQ.cs:296-323): the pre-processing of levels 0, 1 and 2 with or
-// without E8E9 on the GPU (zh_pre_lz.hip), then either the existing encoders (n >= 1 headers, through compress_impl,
+// zh_pre.cpp — LibZPAQ.compressBlock for a method (LibZPAQ.cs:296-323): the pre-processing of levels 0, 1 and 2 and, where
+// the caller asks for it, 3 (BWT), with or without E8E9, on the GPU (zh_pre_lz.hip, zh_pre_bwt.hip), then either the existing encoders (n >= 1 headers, through compress_impl,
 // which reads the pre-processed bytes where the kernels left them) or the unmodelled store layout (n = 0 headers,
 // Encoder.cs:39-73: the decoded stream in 4-byte big-endian length-prefixed chunks of 65 536 bytes).
 #include <hip/hip_runtime.h>
@@ -17,6 +17,7 @@
 extern "C" hipError_t zh_launch_pre_prefix(const ZhPreLaunch *L, const uint8_t *prefix, uint32_t np, hipStream_t stream);
 extern "C" hipError_t zh_launch_pre_e8e9(const ZhPreLaunch *L, hipStream_t stream);
 extern "C" hipError_t zh_launch_pre_lz(const ZhPreLaunch *L, uint64_t max_n, hipStream_t stream);
+extern "C" hipError_t zh_launch_pre_bwt(const ZhBwtLaunch *L, hipStream_t stream, uint32_t *launches, uint32_t *rounds);
 extern "C" hipError_t zh_launch_sha1(const uint8_t *data, const uint64_t *seg, uint32_t n_seg, uint32_t *digest, hipStream_t stream);
 
 using namespace zh;
@@ -51,14 +52,16 @@ uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 // the method's numbers (tools/methods.preprocess / lz77_level1 / lz77_level2)
 struct Method {
   uint32_t level = 0, doe8 = 0, k = 0, m = 0, rb = 0, max_match = 0, max_off = 0;
-  uint64_t max_block = ~0ull;             // levels 1 / 2: 2^(args[0] + 20), the PCOMP's M
+  uint64_t max_block = ~0ull;             // levels 1 / 2: 2^(args[0] + 20), the PCOMP's M; level 3: 4096 less (LibZPAQ.cs:289)
 };
 
-int parse_method(const int32_t *args, Method &M, zpaqhip_err *err) {
+constexpr uint32_t kFlagBwt = 4;          // zpaqhip_compress_opts.flags: accept level 3
+
+int parse_method(const int32_t *args, bool bwt, Method &M, zpaqhip_err *err) {
   if (!args) { set_err(err, ZPAQHIP_E_ARG, -1, -1); return ZPAQHIP_E_ARG; }
   M.level = (uint32_t)args[1] & 3;
   M.doe8 = args[1] >= 4 && args[1] <= 7;
-  if (M.level == 3) {
+  if (M.level == 3 && !bwt) {
     set_err(err, ZPAQHIP_E_ARG, -1, -1, "BWT (level 3) pre-processing is not available on the GPU");
     return ZPAQHIP_E_ARG;
   }
@@ -78,7 +81,7 @@ int parse_method(const int32_t *args, Method &M, zpaqhip_err *err) {
     M.max_match = M.m + 63 + 256;
     M.max_off = (1u << 24) - 1;
   }
-  if (M.level) M.max_block = std::min<uint64_t>(1ull << std::min(args[0] + 20, 62), (1ull << 31) - 1);
+  if (M.level) M.max_block = std::min<uint64_t>((1ull << std::min(args[0] + 20, 62)) - (M.level == 3 ? 4096 : 0), (1ull << 31) - 1);
   return ZPAQHIP_OK;
 }
 
@@ -87,6 +90,7 @@ int parse_method(const int32_t *args, Method &M, zpaqhip_err *err) {
 uint64_t pre_bound(const Method &M, uint64_t n) {
   if (M.level == 1) return (11 * n + 7) / 8 + 16;
   if (M.level == 2) return 2 * n + 64;
+  if (M.level == 3) return n + 5;         // LZBuffer.cs:233-239
   return n;
 }
 
@@ -96,6 +100,13 @@ uint32_t tab_bits(uint64_t n) {           // at least two table entries per posi
   return b;
 }
 
+// zh_pre_bwt.hip's buffers for n slots: two key and two position arrays and the ranks (20 bytes per slot), the digit
+// counts of the radix tiles (1 / 4 byte per slot) and the partial results of the scans
+constexpr uint64_t kBwtSlots = (1ull << 31) - 1;
+uint64_t bwt_tiles(uint64_t n) { return (n + 4095) / 4096; }
+uint64_t bwt_sums(uint64_t n) { return 2 * ((std::max<uint64_t>(n, 256 * bwt_tiles(n)) + 4095) / 4096) + 2; }
+uint64_t bwt_bytes(uint64_t n) { return 20 * n + 1024 * bwt_tiles(n) + 4 * bwt_sums(n) + 5 * 256; }
+
 class DevPre : public PreStage {
  public:
   DevPre(const Method &M, const uint8_t *in, const uint64_t *in_off) : M_(M), in_(in), in_off_(in_off) {}
@@ -104,6 +115,7 @@ class DevPre : public PreStage {
   uint64_t scratch(size_t i) const override {
     const uint64_t n = n_of(i);
     uint64_t c = n + 64;
+    if (M_.level == 3) return c + (M_.doe8 ? n : 0) + bwt_bytes(n) + 8;
     if (M_.level) c += (M_.doe8 ? n : 0) + 8 * n + (4ull << tab_bits(n));
     return c;
   }
@@ -113,7 +125,8 @@ class DevPre : public PreStage {
     const size_t nb = b1 - b0;
     const uint64_t np = prefix.size(), base = in_off_[b0], plain = in_off_[b1] - base;
     std::vector<ZhPreBlock> desc(nb);
-    uint64_t scr = 0, tab = 0, max_n = 0;
+    uint64_t scr = 0, tab = 0, max_n = 0, max_scr = 0;
+    std::vector<size_t> cut(1, 0);        // level 3: first block of each launch (at most 2^31 - 1 slots per launch)
     sha_off.resize(nb);
     for (size_t j = 0; j < nb; ++j) {
       ZhPreBlock &d = desc[j];
@@ -122,6 +135,11 @@ class DevPre : public PreStage {
       d.n = n_of(b0 + j);
       d.out_off = off[j] + np;
       d.out_cap = pre_bound(M_, d.n);
+      if (M_.level == 3 && scr + d.n > kBwtSlots) {      // the next launch of zh_launch_pre_bwt starts here
+        cut.push_back(j);
+        max_scr = std::max(max_scr, scr);
+        scr = 0;
+      }
       d.scr_off = scr;
       scr += d.n;
       d.tab_bits = tab_bits(d.n);
@@ -148,7 +166,21 @@ class DevPre : public PreStage {
       HIPCHK(pref_.alloc(np));
       HIPCHK(hipMemcpy(pref_.p, prefix.data(), np, hipMemcpyHostToDevice));
     }
-    if (M_.level) {
+    std::vector<uint32_t> starts;
+    if (M_.level == 3) {
+      max_scr = std::max(max_scr, scr);
+      cut.push_back(nb);
+      for (size_t u = 0; u + 1 < cut.size(); ++u) {      // starts of launch u at starts[cut[u] + u ..]
+        for (size_t j = cut[u]; j < cut[u + 1]; ++j) starts.push_back((uint32_t)desc[j].scr_off);
+        starts.push_back((uint32_t)(desc[cut[u + 1] - 1].scr_off + desc[cut[u + 1] - 1].n));
+      }
+      HIPCHK(tab_.alloc(starts.size() * 4));
+      HIPCHK(hipMemcpy(tab_.p, starts.data(), starts.size() * 4, hipMemcpyHostToDevice));
+      HIPCHK(chain_.alloc(16 * max_scr));             // key[2], val[2]
+      HIPCHK(prev_.alloc(4 * max_scr + 1024 * bwt_tiles(max_scr) + 4 * bwt_sums(max_scr) + 4));   // rank, counts, sums, multi
+      if (M_.doe8) HIPCHK(e8_.alloc(plain));
+      L.e8 = e8_.as<uint8_t>();
+    } else if (M_.level) {
       HIPCHK(tab_.alloc(tab * 4));
       HIPCHK(chain_.alloc(scr * 4));
       HIPCHK(prev_.alloc(scr * 4));
@@ -163,14 +195,36 @@ class DevPre : public PreStage {
       for (size_t j = 0; j < nb; ++j)
         if (desc[j].n)
           HIPCHK(hipMemcpyAsync(d_out + desc[j].out_off, plain_.as<uint8_t>() + desc[j].in_off, desc[j].n, hipMemcpyDeviceToDevice, v.stream));
-    if (M_.level) {
+    if (M_.level == 3) {
+      for (size_t u = 0; u + 1 < cut.size(); ++u) {
+        ZhBwtLaunch W;
+        memset(&W, 0, sizeof W);
+        W.src = M_.doe8 ? e8_.as<uint8_t>() : plain_.as<uint8_t>();
+        W.out = d_out;
+        W.blocks = desc_.as<ZhPreBlock>() + cut[u];
+        W.out_len = len_.as<uint64_t>() + cut[u];
+        W.starts = tab_.as<uint32_t>() + cut[u] + u;
+        W.n_blocks = (uint32_t)(cut[u + 1] - cut[u]);
+        W.n = starts[cut[u + 1] + u];
+        for (size_t j = cut[u]; j < cut[u + 1]; ++j) W.max_n = std::max<uint32_t>(W.max_n, (uint32_t)desc[j].n);
+        for (int q = 0; q < 2; ++q) {
+          W.key[q] = chain_.as<uint32_t>() + (2 * q) * max_scr;
+          W.val[q] = chain_.as<uint32_t>() + (2 * q + 1) * max_scr;
+        }
+        W.rank = prev_.as<uint32_t>();
+        W.counts = W.rank + max_scr;
+        W.sums = W.counts + 256 * bwt_tiles(max_scr);
+        W.multi = W.sums + bwt_sums(max_scr);
+        HIPCHK(zh_launch_pre_bwt(&W, v.stream, &launches, &bwt_rounds));
+      }
+    } else if (M_.level) {
       HIPCHK(hipMemsetAsync(tab_.p, 0xFF, tab * 4, v.stream));
       HIPCHK(zh_launch_pre_lz(&L, max_n, v.stream));
     }
     HIPCHK(hipEventRecord(v.ev1, v.stream));
     HIPCHK(hipStreamSynchronize(v.stream));
     HIPCHK(hipEventElapsedTime(&ms, v.ev0, v.ev1));
-    launches += (np ? 1 : 0) + (M_.doe8 ? 1 : 0) + (M_.level ? 3 : 0);
+    launches += (np ? 1 : 0) + (M_.doe8 ? 1 : 0) + (M_.level == 3 ? 0 : M_.level ? 3 : 0);
     len.assign(nb, 0);
     if (M_.level || M_.doe8) HIPCHK(hipMemcpy(len.data(), len_.p, nb * 8, hipMemcpyDeviceToHost));
     else
@@ -184,6 +238,7 @@ class DevPre : public PreStage {
     return ZPAQHIP_OK;
   }
   uint32_t launches = 0;
+  uint32_t bwt_rounds = 0;                // level 3: doubling rounds after the first sort, over all launches
 
  private:
   Method M_;
@@ -214,27 +269,20 @@ int check_blocks(const Method &M, const uint8_t *in, const uint64_t *in_off, siz
       return ZPAQHIP_E_ARG;
     }
     if (in_off[i + 1] - in_off[i] > M.max_block) {
-      set_err(err, ZPAQHIP_E_ARG, (int)i, -1, "block longer than the post-processor's M (2^(args[0] + 20) bytes)");
+      set_err(err, ZPAQHIP_E_ARG, (int)i, -1,
+              M.level == 3 ? "block longer than the BWT method allows (2^(args[0] + 20) - 4096, at most 2^31 - 1 bytes)"
+                           : "block longer than the post-processor's M (2^(args[0] + 20) bytes)");
       return ZPAQHIP_E_ARG;
     }
   }
   return ZPAQHIP_OK;
 }
 
-}  // namespace
-
-extern "C" int zpaqhip_preprocess_blocks(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *in, const uint64_t *in_off,
-                                         size_t n_blocks, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off,
-                                         zpaqhip_err *err) {
-  if (!ctx || !out_len || (!out && out_cap) || (n_blocks && !in_off)) {
-    set_err(err, ZPAQHIP_E_ARG, -1, -1);
-    return ZPAQHIP_E_ARG;
-  }
-  *out_len = 0;
-  Method M;
-  int rc = parse_method(args, M, err);
+// the pre-processed bytes of a method's blocks, back to back (zpaqhip_preprocess_blocks, zpaqhip_bwt_blocks)
+int preprocess_impl(zpaqhip_ctx *ctx, const Method &M, const uint8_t *in, const uint64_t *in_off, size_t n_blocks, uint8_t *out,
+                    size_t out_cap, size_t *out_len, uint64_t *out_off, zpaqhip_err *err) {
+  int rc = check_blocks(M, in, in_off, n_blocks, err);
   if (rc) return rc;
-  if ((rc = check_blocks(M, in, in_off, n_blocks, err))) return rc;
   CtxView v = ctx_view(ctx);
   HIPCHK(hipSetDevice(v.device));
   DevPre P(M, in, in_off);
@@ -274,6 +322,36 @@ extern "C" int zpaqhip_preprocess_blocks(zpaqhip_ctx *ctx, const int32_t *args, 
   return ZPAQHIP_OK;
 }
 
+}  // namespace
+
+extern "C" int zpaqhip_preprocess_blocks(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *in, const uint64_t *in_off,
+                                         size_t n_blocks, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off,
+                                         zpaqhip_err *err) {
+  if (!ctx || !out_len || (!out && out_cap) || (n_blocks && !in_off)) {
+    set_err(err, ZPAQHIP_E_ARG, -1, -1);
+    return ZPAQHIP_E_ARG;
+  }
+  *out_len = 0;
+  Method M;
+  const int rc = parse_method(args, false, M, err);
+  if (rc) return rc;
+  return preprocess_impl(ctx, M, in, in_off, n_blocks, out, out_cap, out_len, out_off, err);
+}
+
+extern "C" int zpaqhip_bwt_blocks(zpaqhip_ctx *ctx, int doe8, const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
+                                  uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off, zpaqhip_err *err) {
+  if (!ctx || !out_len || (!out && out_cap) || (n_blocks && !in_off)) {
+    set_err(err, ZPAQHIP_E_ARG, -1, -1);
+    return ZPAQHIP_E_ARG;
+  }
+  *out_len = 0;
+  Method M;
+  M.level = 3;
+  M.doe8 = doe8 != 0;
+  M.max_block = (1ull << 31) - 1;         // no post-processor here: the suffix array's 32-bit slots are the only limit
+  return preprocess_impl(ctx, M, in, in_off, n_blocks, out, out_cap, out_len, out_off, err);
+}
+
 extern "C" int zpaqhip_compress_method_blocks(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *hdr, size_t hdr_len,
                                               const uint8_t *pcomp, size_t pcomp_len, const uint8_t *in, const uint64_t *in_off,
                                               size_t n_blocks, const char *const *filenames, uint8_t *out, size_t out_cap,
@@ -284,8 +362,12 @@ extern "C" int zpaqhip_compress_method_blocks(zpaqhip_ctx *ctx, const int32_t *a
     return ZPAQHIP_E_ARG;
   }
   *out_len = 0;
+  zpaqhip_compress_opts o;
+  memset(&o, 0, sizeof o);
+  if (opts) memcpy(&o, opts, std::min<size_t>(sizeof o, opts->struct_size ? opts->struct_size : sizeof o));
+  else o.flags = 3;
   Method M;
-  int rc = parse_method(args, M, err);
+  int rc = parse_method(args, (o.flags & kFlagBwt) != 0, M, err);
   if (rc) return rc;
   if ((rc = check_blocks(M, in, in_off, n_blocks, err))) return rc;
   ZhModel model;
@@ -296,10 +378,6 @@ extern "C" int zpaqhip_compress_method_blocks(zpaqhip_ctx *ctx, const int32_t *a
                                     out_len, block_off, opts, &P, err);
 
   // n = 0: the store layout of Encoder.compress with no model; the block is level 2 (Compressor.cs:92-96)
-  zpaqhip_compress_opts o;
-  memset(&o, 0, sizeof o);
-  if (opts) memcpy(&o, opts, std::min<size_t>(sizeof o, opts->struct_size ? opts->struct_size : sizeof o));
-  else o.flags = 3;
   const bool want_sha = (o.flags & 1) != 0, want_tag = (o.flags & 2) != 0;
   std::vector<uint8_t> sel;                       // the post-processor's header (Compressor.postProcess)
   if (pcomp_len) {

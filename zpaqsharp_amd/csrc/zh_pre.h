@@ -1,5 +1,6 @@
 // zh_pre.h — structures shared by the host side of the method path (zh_pre.cpp) and the pre-processing kernels
-// (zh_pre_lz.hip): LibZPAQ.compressBlock's E8E9 and LZBuffer levels 1 / 2 (LibZPAQ.cs:296-311, LZBuffer.cs:96-115).
+// (zh_pre_lz.hip, zh_pre_bwt.hip): LibZPAQ.compressBlock's E8E9 and LZBuffer levels 1 / 2 / 3 (LibZPAQ.cs:296-311,
+// LZBuffer.cs:96-115, :205-240).
 //
 // The parse is the one tools/methods._matches writes: every position p <= n - k is a dictionary entry, prev[i] is the
 // largest j < i whose k bytes equal those at i, position i starts a match iff prev[i] exists within max_off, the match is
@@ -14,7 +15,7 @@ struct ZhPreBlock {
   uint64_t n;            // plaintext bytes
   uint64_t out_off;      // pre-processed bytes in ::out
   uint64_t out_cap;      // their bound (zh::pre_bound); the kernels count past it but never write past it
-  uint64_t scr_off;      // first element of this block in ::chain / ::prev
+  uint64_t scr_off;      // first element of this block in ::chain / ::prev; level 3: its first slot in its ZhBwtLaunch
   uint64_t tab_off;      // first element of this block's hash table in ::table
   uint32_t tab_bits;     // the table has 1 << tab_bits entries
   uint32_t pad;
@@ -30,11 +31,29 @@ struct ZhPreLaunch {
   int32_t *chain;        // per position: the previous position of the same bucket, or -1
   uint32_t *prev;        // per position: distance to prev[i] << 8 | min(LCP - k, ZH_PRE_EXT), or 0 (no match starts here)
   uint32_t n_blocks;
-  uint32_t level;        // 0, 1 or 2 (args[1] & 3)
+  uint32_t level;        // args[1] & 3; 3 (BWT): zh_pre_e8e9 writes ::e8 as for 1 / 2, the rest is ZhBwtLaunch's
   uint32_t doe8;         // 4 <= args[1] <= 7
   uint32_t k;            // key length: max(4, args[2]) for level 1, max(args[2], 3) for level 2
   uint32_t m;            // level 2: args[2]
   uint32_t rb;           // level 1: args[0] - 4 when args[0] > 4, else 0
   uint32_t max_match;    // 2^16 (level 1), m + 63 + 256 (level 2)
   uint32_t max_off;      // 2^23 - 1 (level 1), 2^24 - 1 (level 2)
+};
+
+// Level 3 (zh_pre_bwt.hip): the blocks of one launch share a slot space of n = sum of their sizes <= 2^31 - 1 slots.
+struct ZhBwtLaunch {
+  const uint8_t *src;        // block b's bytes at src + blocks[b].in_off (the E8E9 copy for level 7)
+  uint8_t *out;              // block b's n + 5 bytes at out + blocks[b].out_off
+  const ZhPreBlock *blocks;
+  uint64_t *out_len;         // per block
+  const uint32_t *starts;    // n_blocks + 1: starts[b] = blocks[b].scr_off, starts[n_blocks] = n
+  uint32_t *key[2];          // n each: the radix sort's keys, ping and pong
+  uint32_t *val[2];          // n each: positions; after a sort, the suffix array
+  uint32_t *rank;            // n: first slot of the group of a position
+  uint32_t *counts;          // 256 * ceil(n / 4096): digit counts per tile
+  uint32_t *sums;            // 2 * ceil(max(n, 256 * tiles) / 4096) + 2: partial results of a scan
+  uint32_t *multi;           // positions in groups of two or more after a round
+  uint32_t n_blocks, n;
+  uint32_t max_n;            // the longest block
+  uint32_t pad;
 };

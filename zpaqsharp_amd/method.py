@@ -488,22 +488,25 @@ def model_of(method: str) -> Tuple[zpaql.Model, List[int]]:
 # ---------------------------------------------------------------------------------------------------------------------
 # what the GPU pre-processors (zpaqhip_preprocess_blocks, zpaqhip_compress_method_blocks) accept
 # ---------------------------------------------------------------------------------------------------------------------
-def check_blocks(args: List[int], sizes) -> None:
-    """ValueError for what the C ABI refuses with ZPAQHIP_E_ARG: level 3 (BWT), level 2 with args[2] outside 1..64, and at
-    level 1 or 2 a block longer than 2^(args[0] + 20) bytes (its offsets would wrap the PCOMP's M) or 2^31 - 1 bytes."""
+def check_blocks(args: List[int], sizes, bwt: bool = False) -> None:
+    """ValueError for what the C ABI refuses with ZPAQHIP_E_ARG: level 3 (BWT) unless `bwt` opts in, level 2 with args[2]
+    outside 1..64, and a block longer than 2^(args[0] + 20) bytes at level 1 or 2 (its offsets would wrap the PCOMP's M),
+    than 2^(args[0] + 20) - 4096 bytes at level 3 (compressBlock's own assertion, LibZPAQ.cs:289; it keeps the n + 5
+    bytes inside bwtrle's M), or than 2^31 - 1 bytes."""
     level = args[1] & 3
-    if level == 3:
+    if level == 3 and not bwt:
         raise ValueError("BWT (level 3) pre-processing is not available on the GPU")
     if level == 2 and not 1 <= args[2] <= 64:
         raise ValueError(f"level 2 needs a minimum match length of 1 to 64, not {args[2]}")
     if level:
-        limit = min(1 << min(args[0] + 20, 62), (1 << 31) - 1)
+        limit = min((1 << min(args[0] + 20, 62)) - (4096 if level == 3 else 0), (1 << 31) - 1)
         for i, n in enumerate(sizes):
             if n > limit:
-                raise ValueError(f"block {i} has {n} bytes; at level {level} a block holds at most {limit} (2^(args[0] + 20))")
+                raise ValueError(f"block {i} has {n} bytes; at level {level} a block holds at most {limit} "
+                                 f"(2^(args[0] + 20){' - 4096' if level == 3 else ''})")
 
 
 def pre_bound(args: List[int], n: int) -> int:
     """Pre-processed bytes of an n-byte block at most (zh_pre.cpp pre_bound)."""
     level = args[1] & 3
-    return (11 * n + 7) // 8 + 16 if level == 1 else 2 * n + 64 if level == 2 else n
+    return (11 * n + 7) // 8 + 16 if level == 1 else 2 * n + 64 if level == 2 else n + 5 if level == 3 else n

@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 
+#include "zh_compress.h"
 #include "zh_ctx_view.h"
 #include "zh_host.h"
 #include "zh_zpaql_native.h"
@@ -81,17 +82,6 @@ struct zpaqhip_ctx {
 };
 
 namespace {
-
-#define HIPCHK(expr)                                                          \
-  do {                                                                        \
-    hipError_t e_ = (expr);                                                   \
-    if (e_ != hipSuccess) {                                                   \
-      char m_[112];                                                           \
-      snprintf(m_, sizeof m_, "HIP: %s (%s)", hipGetErrorString(e_), #expr);  \
-      set_err(err, ZPAQHIP_E_HIP, -1, -1, m_);                                \
-      return ZPAQHIP_E_HIP;                                                   \
-    }                                                                         \
-  } while (0)
 
 constexpr size_t kQueueBytes = 512, kDebugBytes = 128;    // work-queue heads (32 B per family) and the *_prof kernels' sums
 constexpr uint64_t kPpOnlyMagic = 0x5A50505F4F4E4C59ull;   // internal: zpaqhip_block_pcomp -> decode_blocks_device ("ZPP_ONLY")
@@ -357,10 +347,8 @@ static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, 
     groups[r.group].push_back((uint32_t)k);
   }
 
-  size_t free_b = 0, total_b = 0;
-  HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  free_b += c->arena.cap;                               // our own cached arena is reusable
-  uint64_t mem_budget = (free_b > (1ull << 30) ? free_b - (1ull << 30) : free_b / 2) / std::max(1u, c->mem_share);
+  uint64_t mem_budget = 0;
+  HIPCHK(device_budget(c->mem_share, c->arena.cap, &mem_budget));     // our own cached arena is reusable
   {
     // Idle contexts zpaqhip_decompress_multi has pooled on this device keep their arenas (tens of GB for the larger models).
     // If this launch could not give every block (up to 256) its slot, they are released first and the budget taken again
@@ -372,9 +360,7 @@ static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, 
       wish += stride * std::min<uint64_t>(groups[g].size(), opts.max_concurrent ? opts.max_concurrent : 256u);
     }
     if (wish > mem_budget && pool_trim_device(c->device, 0)) {
-      HIPCHK(hipMemGetInfo(&free_b, &total_b));
-      free_b += c->arena.cap;
-      mem_budget = (free_b > (1ull << 30) ? free_b - (1ull << 30) : free_b / 2) / std::max(1u, c->mem_share);
+      HIPCHK(device_budget(c->mem_share, c->arena.cap, &mem_budget));
     }
   }
 

@@ -1,32 +1,114 @@
-// zh_compress.h — the batch loop of zpaqhip_compress_blocks (zh_compress.cpp), shared with the method path (zh_pre.cpp),
-// which fills the coded sequences on the device instead of copying them from the host.
+// zh_compress.h — the host side of the compress path, shared by zpaqhip_compress_blocks (zh_compress.cpp) and the method
+// entry points (zh_pre.cpp): call-scoped device resources, the device-memory budget (zh_api.cpp's too), the batch rule,
+// block framing, the SHA-1 step, the call epilogue, the device pre-processing stage and the batch loop itself.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <string>
 #include <vector>
 
 #include "zh_ctx_view.h"
 
 namespace zh {
 
-// Device pre-processing of a batch of blocks in place of the host copy of their coded bytes.
-class PreStage {
- public:
-  virtual ~PreStage() = default;
-  virtual uint64_t bound(size_t i) const = 0;        // pre-processed bytes of block i at most
-  virtual uint64_t scratch(size_t i) const = 0;      // device bytes the stage needs for block i
-  // Write the coded sequence of block b0 + j (prefix[0..np), then its pre-processed bytes) at d_in + off[j], for j < b1 - b0;
-  // len[j] = pre-processed bytes.  sha_base + sha_off[j] is the block's plaintext in device memory (valid until the next
-  // run).  ms = device time of the pre-processing.
-  virtual int run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_in, const std::vector<uint64_t> &off,
-                  const std::vector<uint8_t> &prefix, std::vector<uint64_t> &len, const uint8_t **sha_base,
-                  std::vector<uint64_t> &sha_off, float &ms, zpaqhip_err *err) = 0;
+struct DevMem {                           // device buffer owned by one call
+  void *p = nullptr;
+  ~DevMem() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t n) {
+    if (p) { (void)hipFree(p); p = nullptr; }
+    return hipMalloc(&p, std::max<size_t>(n, 256));
+  }
+  template <class T> T *as() const { return static_cast<T *>(p); }
 };
 
+struct Event {                            // one event owned by one call
+  hipEvent_t e = nullptr;
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+};
+
+inline uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
+
+// Device bytes a call may plan with: what is free (plus `reusable`, the caller's own cached bytes) less 1 GiB of headroom,
+// or half of it when little is free, divided among the contexts that share the device.
+hipError_t device_budget(uint32_t mem_share, uint64_t reusable, uint64_t *budget);
+
+// opts as the call uses them (struct_size-aware copy); NULL means SHA-1 and tag (flags = 3)
+zpaqhip_compress_opts resolve_compress_opts(const zpaqhip_compress_opts *opts);
+
+// What the coded sequence starts with (Compressor.postProcess, Compressor.cs:156-190): 0, or 1, len lo, len hi, pcomp
+std::vector<uint8_t> selector_prefix(const uint8_t *pcomp, size_t pcomp_len);
+
+// End of the batch that starts at block b0: opts.batch_blocks blocks when set, else blocks while their cost fits half the
+// budget (at least one block, at most 4096).
+template <class Cost>
+size_t batch_end(size_t b0, size_t n_blocks, uint64_t batch_blocks, uint64_t budget, Cost cost_of) {
+  if (batch_blocks) return std::min<size_t>(n_blocks, b0 + batch_blocks);
+  size_t b1 = b0 + 1;
+  uint64_t cost = cost_of(b0);
+  while (b1 < n_blocks && b1 - b0 < 4096 && cost + cost_of(b1) <= budget / 2) cost += cost_of(b1++);
+  return b1;
+}
+
+// The bytes around one block's coded data (LibZPAQ.cs:296-323; BlockWriter::write_block): tag, block and segment header
+// with the size comment in `head`, end of segment (with the SHA-1 when `digest` gives its five words) and of block in `tail`.
+struct BlockFrame {
+  std::string head, tail;
+  BlockFrame(bool tag, uint8_t level, const uint8_t *hdr, size_t hdr_len, const char *filename, uint64_t plain_len,
+             const uint32_t *digest);
+};
+// Encoder.compress without a model (Encoder.cs:39-73): the decoded stream, `sel` then `pre`, in chunks of at most 65 536
+// bytes behind their 4-byte big-endian lengths.
+uint64_t store_body_len(uint64_t decoded);
+void write_store_body(uint8_t *w, const std::vector<uint8_t> &sel, const uint8_t *pre, uint64_t pre_len);
+
+// SHA-1 (zh_sha1_dev.hip) of the segments d_base + seg[2k] of seg[2k + 1] bytes: five words per segment in `digest`.
+int sha1_segments(const CtxView &v, const uint8_t *d_base, const std::vector<uint64_t> &seg, std::vector<uint32_t> &digest,
+                  zpaqhip_err *err);
+
+// The end of every call: off[n_blocks], zpaqhip_last_stats and *out_len from the bytes needed; ZPAQHIP_E_OUTPUT_FULL when
+// they exceed out_cap.
+int finish_call(const CtxView &v, zpaqhip_stats st, uint64_t pos, size_t n_blocks, uint64_t *off, size_t out_cap, size_t *out_len,
+                zpaqhip_err *err);
+
+// the method's numbers (tools/methods.preprocess / lz77_level1 / lz77_level2)
+struct Method {
+  uint32_t level = 0, doe8 = 0, k = 0, m = 0, rb = 0, max_match = 0, max_off = 0;
+  uint64_t max_block = ~0ull;             // levels 1 / 2: 2^(args[0] + 20), the PCOMP's M; level 3: 4096 less (LibZPAQ.cs:289)
+};
+
+struct PreBatch {                         // what DevPre::run leaves of a batch [b0, b1)
+  std::vector<uint64_t> len;              // pre-processed bytes of block b0 + j
+  const uint8_t *plain = nullptr;         // device copy of in[in_off[b0], in_off[b1]), valid until the next run
+  float ms = 0;                           // device time of the pre-processing
+};
+
+// Device pre-processing of a batch of blocks (zh_pre.cpp), in place of the host copy of their coded bytes.
+class DevPre {
+ public:
+  DevPre(const Method &M, const uint8_t *in, const uint64_t *in_off) : M_(M), in_(in), in_off_(in_off) {}
+  uint64_t n_of(size_t i) const { return in_off_[i + 1] - in_off_[i]; }
+  uint64_t bound(size_t i) const;         // pre-processed bytes of block i at most
+  uint64_t scratch(size_t i) const;       // device bytes the stage needs for block i
+  // Write the coded sequence of block b0 + j (prefix, then its pre-processed bytes) at d_out + off[j], for j < b1 - b0.
+  int run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, const std::vector<uint64_t> &off,
+          const std::vector<uint8_t> &prefix, PreBatch &r, zpaqhip_err *err);
+  uint32_t launches = 0;
+
+ private:
+  Method M_;
+  const uint8_t *in_;
+  const uint64_t *in_off_;
+  DevMem plain_, e8_, tab_, chain_, prev_, len_, desc_, pref_;
+};
+
+// The batch loop.  Without `pre`, block i's coded bytes are in[in_off[i], in_off[i+1]) and `orig`, when given, is what the
+// size comment and SHA-1 describe.  With `pre` (the method path) `in` is the plaintext and `orig` NULL; a header with n = 0
+// then gets the store layout instead of an encoder.
 int compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
                   const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
                   const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
                   uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
-                  const zpaqhip_compress_opts *opts, PreStage *pre, zpaqhip_err *err);
+                  const zpaqhip_compress_opts *opts, DevPre *pre, zpaqhip_err *err);
 
 }  // namespace zh

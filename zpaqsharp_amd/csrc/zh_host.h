@@ -2,6 +2,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include <string>
 #include <vector>
@@ -13,6 +14,18 @@
 #define ZH_FAM_CHAIN_MID8 7u     // zh_nibble.hip: mid's shape with EIGHT mixer inputs (icm, five isse, match, icm; mix) — the level-4 text model
 #define ZH_FAM_CHAIN_MIN1 8u     // zh_nibble.hip: ONE ICM on min's loop — level 4's model for barely compressible data
 #define ZH_NFAM_HOST 9u
+
+// Fail the entry point (one with `zpaqhip_err *err` in scope) on a HIP error, naming the call in err->msg.
+#define HIPCHK(expr)                                                          \
+  do {                                                                        \
+    hipError_t e_ = (expr);                                                   \
+    if (e_ != hipSuccess) {                                                   \
+      char m_[112];                                                           \
+      snprintf(m_, sizeof m_, "HIP: %s (%s)", hipGetErrorString(e_), #expr);  \
+      zh::set_err(err, ZPAQHIP_E_HIP, -1, -1, m_);                            \
+      return ZPAQHIP_E_HIP;                                                   \
+    }                                                                         \
+  } while (0)
 
 namespace zh {
 

@@ -31,6 +31,7 @@
 #include "zh_zpaql_pcomp.h"
 #include "zh_ibwt.h"
 #include "zh_e8e9.h"
+#include "zh_lzcopy.h"
 
 using namespace zhcore;
 using namespace zhdev;
@@ -864,6 +865,8 @@ __device__ __attribute__((noinline)) int nb_pcomp_drain(const ZhLaunch *Lp_, LDS
     // length) is periodic with the distance: a chunk reads at a multiple of the distance that the bytes written so far cover.
     // M is written as the program writes it (later matches and the program's own runs — the general path's bytes, the end of a
     // segment — find it as they expect); loads of M go to L2 (glc): the bytes may have been written by other lanes a moment ago.
+    // The distance is taken modulo |M| first, as the program's addresses are; a distance of 0 (offset bytes FF FF FF FF, or
+    // |M| - 1 modulo |M|) writes out the cells M already holds.
     const uint32_t lane = threadIdx.x & 63u, minlen = uni(S.fxs[kFxPlz]) - 1u, mm = uni(pz.mmask);
     uint8_t *Mw = reinterpret_cast<uint8_t *>(uni64((uint64_t)(uintptr_t)pz.m));
     uint32_t r1 = uni(S.pr[1]), r2 = uni(S.pr[2]);
@@ -891,19 +894,19 @@ __device__ __attribute__((noinline)) int nb_pcomp_drain(const ZhLaunch *Lp_, LDS
         const uint32_t n = r1, dist = r2 + 1u;
         out_flush(o, lane);                              // the literals parked so far
         __builtin_amdgcn_s_waitcnt(0);                   // (their stores to M, too)
-        uint32_t done = 0, deff = dist;
+        // (zh_lzcopy.h: the distance modulo |M| decides — 0 is a copy of every cell onto itself, nothing to store)
+        const uint32_t d = zh_lz_reduce(dist, mm);
+        uint32_t done = 0, deff = d;
         while (done < n) {
-          uint32_t m = n - done;
-          m = m < 64u ? m : 64u;
-          m = m < deff ? m : deff;
+          const uint32_t m = zh_lz_width(deff, mm, n, done);
           if (lane < m) {
             const uint8_t v = __hip_atomic_load(&Mw[(pb + done + lane - deff) & mm], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            Mw[(pb + done + lane) & mm] = v;
+            if (d) Mw[(pb + done + lane) & mm] = v;
             if (o.len + done + lane < o.cap) o.base[o.len + done + lane] = v;
           }
           done += m;
           __builtin_amdgcn_s_waitcnt(0);
-          if (deff < 64u && 2u * deff <= done + dist) deff *= 2u;
+          if (d) deff = zh_lz_grow(d, deff, done, mm);
         }
         pb += n;
         o.len += n; o.stored = o.len; o.word = 0;

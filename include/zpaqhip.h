@@ -283,7 +283,10 @@ typedef struct zpaqhip_compress_opts {
   uint32_t flags;           /* bit0: store SHA-1 (253 + digest, else 254); bit1: write the 13-byte tag; bit2 (zpaqhip_compress_method_blocks
                                only): accept level 3 (BWT) methods; NULL opts = 3 */
   uint32_t kernel;          /* 0 auto: single-CM models of the `a<<= K  *d=a  halt` shape (K >= 9) on the window-parallel
-                               encoder, the rest on the generic one; 1 every block on the generic encoder (cross-check) */
+                               encoder, the rest on the generic one; 1 every block on the generic encoder (cross-check);
+                               2 as 0, but models that fit the lane-per-component kernel (ICM / ISSE / MATCH / MIX chains of at
+                               most 64 components and 4 mixers: min, mid, max, the models of the method strings) on the
+                               lane-per-component encoder (zh_enc_chain.hip); an opt-in until it becomes the default */
   uint32_t reserved0;
   uint64_t batch_blocks;    /* blocks per device batch; 0 = sized from free device memory */
   uint64_t slot_bytes;      /* test knob: device bytes reserved per block for coded data before the overflow path; 0 = auto
@@ -302,7 +305,9 @@ typedef struct zpaqhip_compress_opts {
  * n == 0 gives ZPAQHIP_E_ARG.  zpaqhip_last_stats: kernel_ms = both encoder passes (and any re-encoding of overflowed
  * blocks), init_ms = the model pass of the window-parallel CM encoder alone (part of kernel_ms; the rest is its coder pass
  * and the generic encoder), launches = encoder launches (one more per batch with an overflowed block), in_bytes =
- * plaintext, out_bytes = the stream, kernel_kind = 2 when a block ran on the window-parallel CM encoder, else 1. */
+ * plaintext, out_bytes = the stream, kernel_kind = 3 when a block ran on the lane-per-component encoder (opts.kernel
+ * == 2; its time is part of kernel_ms, an overflowed block of it is coded again on the same encoder), 2 when one ran on
+ * the window-parallel CM encoder, else 1. */
 int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
                             const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
                             const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
@@ -342,7 +347,8 @@ int zpaqhip_bwt_blocks(zpaqhip_ctx *ctx, int doe8, const uint8_t *in, const uint
  * Encoder.compress without a model (selector or PCOMP header, then the bytes, in 4-byte big-endian length-prefixed chunks
  * of 65 536 bytes, then four zero bytes) in a level 2 block (Compressor.cs:92-96); opts.batch_blocks applies.
  * zpaqhip_last_stats: init_ms = the pre-processing alone, kernel_ms = pre-processing and encoder passes, kernel_kind as
- * for zpaqhip_compress_blocks for modelled blocks and 0 when every block is unmodelled. */
+ * for zpaqhip_compress_blocks for modelled blocks (3 with opts.kernel == 2 for the chain models of levels 3 and 4) and 0
+ * when every block is unmodelled. */
 int zpaqhip_compress_method_blocks(zpaqhip_ctx *ctx, const int32_t args[9], const uint8_t *hdr, size_t hdr_len,
                                    const uint8_t *pcomp, size_t pcomp_len, const uint8_t *in, const uint64_t *in_off,
                                    size_t n_blocks, const char *const *filenames, uint8_t *out, size_t out_cap, size_t *out_len,

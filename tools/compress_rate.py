@@ -1,6 +1,7 @@
 """Compression rate of Context.compress_blocks (or, with --method, Context.compress_method) against the CPU stream writer.
 
     python3 tools/compress_rate.py [--blocks 256] [--block-size 4194304] [--kinds T,R] [--model l1] [--method M] [--bwt]
+                                   [--kernel 0] [--rounds 1] [--decode-kernel K] [--no-cpu]
 
 Per kind: plaintext MB/s from wall time, the time of each pass (zpaqhip_last_stats: init_ms = model pass, kernel_ms -
 init_ms = coder pass), and the CPU writer
@@ -10,6 +11,13 @@ init_ms = coder pass), and the CPU writer
 ratios are compared, not the bytes); pre_ms = the device pre-processing (init_ms), encoder_ms = the rest of kernel_ms.
 The GPU stream is checked by a round trip through Context.decompress(verify_sha1=True).  --bwt passes bwt=True, the
 opt-in a level 3 method needs (its transform is unique, but the CPU writer is still compared by ratio only).
+
+--model takes any models name (l1, min, mid, max, ...), --method any expanded method string, modelled ones included.
+--kernel K[,K...]: the encoder choice (zpaqhip_compress_opts.kernel; 2 = lane-per-component encoder for chain models).
+Several values are run ALTERNATED inside one process on the same blocks, --rounds times each, one JSON line per run, and
+their outputs are compared with each other.  --decode-kernel K adds the kernel time of Context.decompress of the stream
+with that decoder kernel (4 = zh_chain.hip, level walk at run time).  --no-cpu skips the CPU writer and with it every
+comparison with it (cpu16_MBps, identical, cpu16_ratio); the round trip and same_as_first remain.
 """
 import argparse
 import json
@@ -24,27 +32,48 @@ import zpaqsharp_amd as z  # noqa: E402
 from zpaqsharp_amd import method, synth  # noqa: E402
 
 
-def run_method(ctx, a):
+def decode_ms(ctx, a, stream):
+    """kernel_ms of Context.decompress(stream) on the decoder kernel --decode-kernel names; nothing without one"""
+    if a.decode_kernel is None:
+        return {}
+    ctx.decompress(stream, kernel=a.decode_kernel)
+    st = ctx.stats()
+    return {"decode_kernel": a.decode_kernel, "decode_kernel_ms": st.kernel_ms, "decode_kernel_kind": st.kernel_kind}
+
+
+def run_method(ctx, a, kernels):
     model, args = method.model_of(a.method)
     for kind in a.kinds.split(","):
         blocks = [synth.plain(kind, i, a.block_size) for i in range(a.blocks)]
         mb = a.blocks * a.block_size / 1e6
-        ctx.compress_method(a.method, blocks[:1], bwt=a.bwt)              # warm-up
-        t = time.perf_counter()
-        got = ctx.compress_method(a.method, blocks, bwt=a.bwt)
-        gpu_s = time.perf_counter() - t
-        st = ctx.stats()
-        t = time.perf_counter()
-        want, _ = synth.method_stream(model, args, kind, nblocks=a.blocks, block_size=a.block_size, threads=16)
-        cpu_s = time.perf_counter() - t
-        back = ctx.decompress(got, verify_sha1=True)
-        ok = back.size == a.blocks * a.block_size and all(
-            (back[i * a.block_size:(i + 1) * a.block_size] == blocks[i]).all() for i in range(a.blocks))
-        print(json.dumps({"method": a.method, "kind": kind, "blocks": a.blocks, "block_size": a.block_size,
-                          "gpu_MBps": mb / gpu_s, "gpu_wall_s": gpu_s, "kernel_ms": st.kernel_ms, "pre_ms": st.init_ms,
-                          "encoder_ms": st.kernel_ms - st.init_ms, "launches": st.launches, "kernel_kind": st.kernel_kind,
-                          "cpu16_MBps": mb / cpu_s, "ratio": len(got) / (mb * 1e6), "cpu16_ratio": want.size / (mb * 1e6),
-                          "round_trip": bool(ok)}))
+        cpu = {}
+        if not a.no_cpu:
+            t = time.perf_counter()
+            want, _ = synth.method_stream(model, args, kind, nblocks=a.blocks, block_size=a.block_size, threads=16)
+            cpu = {"cpu16_MBps": mb / (time.perf_counter() - t), "cpu16_ratio": want.size / (mb * 1e6)}
+        first = None
+        for k in kernels:
+            ctx.compress_method(a.method, blocks[:1], bwt=a.bwt, kernel=k)    # warm-up
+        for rnd in range(a.rounds):
+            for k in kernels:
+                t = time.perf_counter()
+                got = ctx.compress_method(a.method, blocks, bwt=a.bwt, kernel=k)
+                gpu_s = time.perf_counter() - t
+                st = ctx.stats()
+                row = {"method": a.method, "kind": kind, "blocks": a.blocks, "block_size": a.block_size, "kernel": k, "round": rnd,
+                       "gpu_MBps": mb / gpu_s, "gpu_wall_s": gpu_s, "kernel_ms": st.kernel_ms, "pre_ms": st.init_ms,
+                       "encoder_ms": st.kernel_ms - st.init_ms, "launches": st.launches, "kernel_kind": st.kernel_kind,
+                       "ratio": len(got) / (mb * 1e6)}
+                if first is None:
+                    first = got
+                    back = ctx.decompress(got, verify_sha1=True)
+                    row["round_trip"] = bool(back.size == a.blocks * a.block_size and all(
+                        (back[i * a.block_size:(i + 1) * a.block_size] == blocks[i]).all() for i in range(a.blocks)))
+                    row.update(decode_ms(ctx, a, got))
+                else:
+                    row["same_as_first"] = got == first
+                row.update(cpu)
+                print(json.dumps(row), flush=True)
 
 
 def main():
@@ -55,26 +84,45 @@ def main():
     ap.add_argument("--model", default="l1")
     ap.add_argument("--method", default=None)
     ap.add_argument("--bwt", action="store_true", help="accept a level 3 (BWT) method")
+    ap.add_argument("--kernel", default="0", help="encoder choice(s), comma separated; several are alternated")
+    ap.add_argument("--rounds", type=int, default=1, help="runs of each --kernel value")
+    ap.add_argument("--decode-kernel", type=int, default=None, help="also time the decoder with this opts.kernel")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU writer")
     a = ap.parse_args()
+    kernels = [int(k) for k in a.kernel.split(",")]
     with z.Context(0) as ctx:
         if a.method:
-            return run_method(ctx, a)
+            return run_method(ctx, a, kernels)
         for kind in a.kinds.split(","):
             blocks = [synth.plain(kind, i, a.block_size) for i in range(a.blocks)]
             mb = a.blocks * a.block_size / 1e6
-            ctx.compress_blocks(a.model, blocks[:1])                     # warm-up
-            t = time.perf_counter()
-            got = ctx.compress_blocks(a.model, blocks)
-            gpu_s = time.perf_counter() - t
-            st = ctx.stats()
-            t = time.perf_counter()
-            want, _ = synth.stream(a.model, kind, nblocks=a.blocks, block_size=a.block_size, threads=16)
-            cpu_s = time.perf_counter() - t
-            print(json.dumps({"model": a.model, "kind": kind, "blocks": a.blocks, "block_size": a.block_size,
-                              "gpu_MBps": mb / gpu_s, "gpu_wall_s": gpu_s, "kernel_ms": st.kernel_ms, "model_pass_ms": st.init_ms,
-                              "coder_pass_ms": st.kernel_ms - st.init_ms, "launches": st.launches,
-                              "kernel_kind": st.kernel_kind, "cpu16_MBps": mb / cpu_s, "ratio": len(got) / (mb * 1e6),
-                              "identical": got == want.tobytes()}))
+            cpu, want = {}, None
+            if not a.no_cpu:
+                t = time.perf_counter()
+                want = synth.stream(a.model, kind, nblocks=a.blocks, block_size=a.block_size, threads=16)[0].tobytes()
+                cpu = {"cpu16_MBps": mb / (time.perf_counter() - t)}
+            for k in kernels:
+                ctx.compress_blocks(a.model, blocks[:1], kernel=k)       # warm-up
+            first = None
+            for rnd in range(a.rounds):
+                for k in kernels:
+                    t = time.perf_counter()
+                    got = ctx.compress_blocks(a.model, blocks, kernel=k)
+                    gpu_s = time.perf_counter() - t
+                    st = ctx.stats()
+                    row = {"model": a.model, "kind": kind, "blocks": a.blocks, "block_size": a.block_size, "kernel": k, "round": rnd,
+                           "gpu_MBps": mb / gpu_s, "gpu_wall_s": gpu_s, "kernel_ms": st.kernel_ms, "model_pass_ms": st.init_ms,
+                           "coder_pass_ms": st.kernel_ms - st.init_ms, "launches": st.launches,
+                           "kernel_kind": st.kernel_kind, "ratio": len(got) / (mb * 1e6)}
+                    if want is not None:
+                        row["identical"] = got == want
+                    if first is None:
+                        first = got
+                        row.update(decode_ms(ctx, a, got))
+                    else:
+                        row["same_as_first"] = got == first
+                    row.update(cpu)
+                    print(json.dumps(row), flush=True)
 
 
 if __name__ == "__main__":

@@ -204,7 +204,11 @@ class Context:
         """Compressor.startBlock .. endBlock for each block (LibZPAQ.cs:296-323 framing, one segment per block), coded on
         the GPU: the same bytes the CPU stream writer (synth.compress_block) produces.  `model` is a models name or a
         zpaql.Model.  A `+e8e9` model codes the forward E8E9 transform of each block; a `+lz77` model needs `pre`, the
-        pre-processed bytes of each block (size comment and SHA-1 still describe `blocks`)."""
+        pre-processed bytes of each block (size comment and SHA-1 still describe `blocks`).  `kernel`: 0 single-CM models
+        on the window-parallel encoder, the rest on the one-lane generic encoder; 1 everything on the generic encoder;
+        2 as 0, but models that fit the lane-per-component kernel (ICM / ISSE / MATCH / MIX chains of at most 64
+        components and 4 mixers: min, mid, max, the method models) on the lane-per-component encoder
+        (stats().kernel_kind == 3)."""
         from . import e8e9, models
         m = models.get(model) if isinstance(model, str) else model
         plain = [_as_u8(b) for b in blocks]
@@ -268,7 +272,8 @@ class Context:
         """LibZPAQ.compressBlock(method) for each block (LibZPAQ.cs:296-323, one segment per block) on the GPU: the bytes
         tools.methods.compress_block writes.  Levels 0, 1 and 2 with or without E8E9, and with `bwt=True` level 3; the
         model of an n >= 1 method codes the pre-processed bytes on the encoders of compress_blocks (kernel, batch_blocks,
-        slot_bytes as there), an n = 0 method stores them.  ValueError, before the device is touched, for level 3 without
+        slot_bytes as there: kernel=2 puts the chain models of levels 3 and 4 on the lane-per-component encoder), an
+        n = 0 method stores them.  ValueError, before the device is touched, for level 3 without
         `bwt=True`, a level 2 `m` outside 1..64 and a block longer than 2^(args[0] + 20) bytes at level 1 or 2 (4096
         less at level 3)."""
         from . import method as mth

@@ -3,7 +3,8 @@
 The input is cut into blocks of `block_size` bytes; each becomes one block with one segment (size comment, SHA-1), coded by
 Context.compress_blocks (a model; a model that needs a pre-processor other than E8E9 is refused there) or, with `method`,
 by Context.compress_method (LibZPAQ.compressBlock's pre-processing levels 0, 1 and 2, with or without E8E9, and with
-`bwt=True` level 3, the Burrows-Wheeler transform; without the keyword a level 3 method is refused).
+`bwt=True` level 3, the Burrows-Wheeler transform; without the keyword a level 3 method is refused).  `kernel` is the
+encoder choice of both (2: ICM / ISSE / MIX chain models on the lane-per-component encoder).
 """
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ from .decompresser import Reader, Writer
 
 
 def compress(reader: Reader, writer: Writer, model="l1", block_size: int = 1 << 22, context: Optional[api.Context] = None,
-             batch_blocks: int = 64, method: Optional[str] = None, bwt: bool = False) -> None:
+             batch_blocks: int = 64, method: Optional[str] = None, bwt: bool = False, kernel: int = 0) -> None:
     if block_size < 1:
         raise ValueError("block_size must be positive")
     if method is not None:
@@ -26,7 +27,8 @@ def compress(reader: Reader, writer: Writer, model="l1", block_size: int = 1 << 
 
         def flush():
             if blocks:
-                writer.write(ctx.compress_blocks(model, blocks) if method is None else ctx.compress_method(method, blocks, bwt=bwt))
+                writer.write(ctx.compress_blocks(model, blocks, kernel=kernel) if method is None
+                             else ctx.compress_method(method, blocks, bwt=bwt, kernel=kernel))
                 blocks.clear()
 
         # A Reader may return fewer bytes than asked before its end (Reader.cs:14-25): only an empty read ends the input,

@@ -5,8 +5,9 @@
 // The host validates the header with the decoder's framing code and then, batch by batch (Call's steps below): plans the
 // batch from the device budget, stages the coded sequences (a host copy, or the pre-processing stage on the device),
 // takes the SHA-1s, picks an encoder per block (route_encode) and launches the encoders, re-encodes a block whose slot was
-// too small on the generic encoder with a worst-case slot, and writes tag, block, segment and end framing around each
-// slot's bytes.  Every coded byte comes out of a HIP kernel (zh_enc_cm.hip, zh_enc_generic.hip); there is no CPU encoder here.
+// too small with a worst-case slot (on the chain encoder if it ran there, else on the generic one), and writes tag, block,
+// segment and end framing around each slot's bytes.  Every coded byte comes out of a HIP kernel (zh_enc_cm.hip, zh_enc_chain.hip, zh_enc_generic.hip); there is
+// no CPU encoder here.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -20,6 +21,7 @@
 #include "zh_enc.h"
 
 extern "C" hipError_t zh_launch_enc_generic(const ZhEncLaunch *L, uint32_t grid, hipStream_t stream);
+extern "C" hipError_t zh_launch_enc_chain(const ZhEncLaunch *L, uint32_t grid, hipStream_t stream);
 extern "C" hipError_t zh_launch_enc_cm_model(const ZhEncLaunch *L, uint32_t n_blocks, hipStream_t stream);
 extern "C" hipError_t zh_launch_enc_cm_code(const ZhEncLaunch *L, uint32_t n_blocks, hipStream_t stream);
 extern "C" hipError_t zh_launch_sha1(const uint8_t *data, const uint64_t *seg, uint32_t n_seg, uint32_t *digest, hipStream_t stream);
@@ -116,11 +118,15 @@ int zh::finish_call(const CtxView &v, zpaqhip_stats st, uint64_t pos, size_t n_b
 namespace {
 
 // ---- which kernel encodes a block (the encode-side twin of zh_api.cpp's route_block): the window-parallel CM encoder for
-// ZH_FAM_CM1 models with opts.kernel 0, the generic encoder for everything else (and for a block too long for zh_enc_cm's
-// 28-bit positions)
-enum class EncKernel { Generic, Cm };
+// ZH_FAM_CM1 models with opts.kernel 0 or 2, the lane-per-component encoder for the chain families with opts.kernel 2, the
+// generic encoder for everything else (and for a block too long for zh_enc_cm's 28-bit positions)
+enum class EncKernel { Generic, Cm, Chain };
+bool chain_family(uint32_t f) {
+  return (f >= ZH_FAM_CHAIN && f <= ZH_FAM_CHAIN + 3) || f == ZH_FAM_CHAIN_MID8 || f == ZH_FAM_CHAIN_MIN1;
+}
 EncKernel route_encode(const ZhModel &m, const zpaqhip_compress_opts &o, uint64_t coded) {
-  if ((m.kind & 255u) == ZH_FAM_CM1 && o.kernel == 0 && coded < ZH_ENC_CM_MAX_N) return EncKernel::Cm;
+  if ((m.kind & 255u) == ZH_FAM_CM1 && (o.kernel == 0 || o.kernel == 2) && coded < ZH_ENC_CM_MAX_N) return EncKernel::Cm;
+  if (o.kernel == 2 && chain_family(m.kind & 255u)) return EncKernel::Chain;
   return EncKernel::Generic;
 }
 
@@ -134,12 +140,12 @@ uint8_t *put(uint8_t *w, const std::string &s) {
 
 // One launch of the encoders over blocks of a batch: what the host lays out, the device buffers, and the results
 struct EncRun {
-  std::vector<ZhEncBlock> desc;           // the CM blocks first (blockIdx = index), then the generic ones (work queue)
-  std::vector<size_t> block;              // desc[k] codes block block[k] of the call
-  size_t n_cm = 0;
+  std::vector<ZhEncBlock> desc;           // the CM blocks first (blockIdx = index), then the chain encoder's, then the generic
+  std::vector<size_t> block;              // one's (a work queue each); desc[k] codes block block[k] of the call
+  size_t n_cm = 0, n_chain = 0;
   uint64_t slot_total = 0, scr_total = 0;
   std::vector<ZhEncResult> res;
-  DevMem slots, d_desc, d_res, queue, arena, la, lb, bases, P;
+  DevMem slots, d_desc, d_res, queue, arena, chain_arena, la, lb, bases, P;
 };
 
 struct Batch {                            // blocks [b0, b1) of the call
@@ -175,7 +181,8 @@ struct Call {
   uint64_t budget = 0, arena_stride = 0;
   zpaqhip_stats st{};
   uint64_t pos = 0;                       // bytes of the stream so far
-  bool any_cm = false;
+  bool any_cm = false, any_chain = false;
+  int cus = 0;                            // compute units: the chain encoder's LDS lets one of its waves live on each
 
   bool want_sha() const { return (o.flags & 1) != 0; }
   uint64_t in_len(size_t i) const { return in_off[i + 1] - in_off[i]; }
@@ -217,6 +224,7 @@ int Call::open(zpaqhip_ctx *ctx) {
         if ((((1ull << (b + K)) & 0xFFFFFFFFull) & M.comp[0].cm_mask) >> 9) wmask |= 1u << b;
     }
   }
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, v.device));
   HIPCHK(device_budget(v.mem_share, 0, &budget));
   arena_stride = align_up(M.arena_bytes, 256);
   return ZPAQHIP_OK;
@@ -285,7 +293,7 @@ int Call::digests(Batch &B) const {
 
 // allocate what r's blocks need, upload their descriptors, launch the encoders, fetch and check the results
 int Call::encode(const Batch &B, EncRun &r) {
-  const size_t n = r.desc.size(), n_gen = n - r.n_cm;
+  const size_t n = r.desc.size(), n_gen = n - r.n_cm - r.n_chain;
   HIPCHK(r.slots.alloc(r.slot_total));
   HIPCHK(r.d_desc.alloc(n * sizeof(ZhEncBlock)));
   HIPCHK(r.d_res.alloc(n * sizeof(ZhEncResult)));
@@ -300,7 +308,7 @@ int Call::encode(const Batch &B, EncRun &r) {
   L.budget = 1ull << 32;
   L.limit = (uint32_t)M.comp[0].arg[1] * 4;
   L.wmask = wmask;
-  uint32_t grid = 0;
+  uint32_t grid = 0, chain_grid = 0;
   if (r.n_cm) {
     HIPCHK(r.la.alloc(r.scr_total * 4));
     HIPCHK(r.lb.alloc(r.scr_total * 4));
@@ -308,15 +316,23 @@ int Call::encode(const Batch &B, EncRun &r) {
     HIPCHK(r.bases.alloc(r.n_cm * (ZH_ENC_CM_KEYS + 1) * 4));
     L.list_a = r.la.as<uint32_t>(); L.list_b = r.lb.as<uint32_t>(); L.P = r.P.as<uint16_t>(); L.bases = r.bases.as<uint32_t>();
   }
+  // an arena slot per resident wave; the two queue heads share one buffer
+  if (n_gen || r.n_chain) {
+    HIPCHK(r.queue.alloc(256));
+    HIPCHK(hipMemset(r.queue.p, 0, 256));
+    L.arena_stride = arena_stride;
+  }
   if (n_gen) {
     const uint64_t by_mem = std::max<uint64_t>(1, (budget / 4) / arena_stride);
     grid = (uint32_t)std::min<uint64_t>({(uint64_t)n_gen, 1024, by_mem});
-    HIPCHK(r.queue.alloc(256));
-    HIPCHK(hipMemset(r.queue.p, 0, 256));
     HIPCHK(r.arena.alloc(grid * arena_stride));
-    L.queue = r.queue.as<uint32_t>();
-    L.arena = r.arena.as<uint8_t>();
-    L.arena_stride = arena_stride;
+  }
+  if (r.n_chain) {
+    // (half the budget for these arenas: a batch's own buffers are planned within the other half, and max's 22 tables
+    // would otherwise leave most compute units without a wave)
+    const uint64_t chain_mem = std::max<uint64_t>(1, (budget / 2) / arena_stride);
+    chain_grid = (uint32_t)std::min<uint64_t>({(uint64_t)r.n_chain, (uint64_t)std::max(1, cus), chain_mem});
+    HIPCHK(r.chain_arena.alloc(chain_grid * arena_stride));
   }
 
   HIPCHK(hipEventRecord(v.ev0, v.stream));
@@ -327,8 +343,16 @@ int Call::encode(const Batch &B, EncRun &r) {
     HIPCHK(zh_launch_enc_cm_code(&L, (uint32_t)r.n_cm, v.stream));
     st.launches += 2;
   }
+  if (r.n_chain) {
+    L.blocks = r.d_desc.as<ZhEncBlock>() + r.n_cm; L.res = r.d_res.as<ZhEncResult>() + r.n_cm; L.n_blocks = (uint32_t)r.n_chain;
+    L.queue = r.queue.as<uint32_t>() + 16; L.arena = r.chain_arena.as<uint8_t>();
+    HIPCHK(zh_launch_enc_chain(&L, chain_grid, v.stream));
+    st.launches += 1;
+  }
   if (n_gen) {
-    L.blocks = r.d_desc.as<ZhEncBlock>() + r.n_cm; L.res = r.d_res.as<ZhEncResult>() + r.n_cm; L.n_blocks = (uint32_t)n_gen;
+    const size_t g0 = r.n_cm + r.n_chain;
+    L.blocks = r.d_desc.as<ZhEncBlock>() + g0; L.res = r.d_res.as<ZhEncResult>() + g0; L.n_blocks = (uint32_t)n_gen;
+    L.queue = r.queue.as<uint32_t>(); L.arena = r.arena.as<uint8_t>();
     HIPCHK(zh_launch_enc_generic(&L, grid, v.stream));
     st.launches += 1;
   }
@@ -354,10 +378,16 @@ int Call::encode(const Batch &B, EncRun &r) {
 // every block of the batch on its encoder, with the slot the options give it
 int Call::encode_batch(Batch &B) {
   EncRun &r = B.first;
-  for (size_t i = B.b0; i < B.b1; ++i) if (route_encode(M, o, B.blen[i - B.b0]) == EncKernel::Cm) r.block.push_back(i);
+  auto take = [&](EncKernel k) {
+    for (size_t i = B.b0; i < B.b1; ++i) if (route_encode(M, o, B.blen[i - B.b0]) == k) r.block.push_back(i);
+  };
+  take(EncKernel::Cm);
   r.n_cm = r.block.size();
-  for (size_t i = B.b0; i < B.b1; ++i) if (route_encode(M, o, B.blen[i - B.b0]) != EncKernel::Cm) r.block.push_back(i);
+  take(EncKernel::Chain);
+  r.n_chain = r.block.size() - r.n_cm;
+  take(EncKernel::Generic);
   any_cm |= r.n_cm > 0;
+  any_chain |= r.n_chain > 0;
   r.desc.resize(B.nb());
   B.slot_of.resize(B.nb());
   for (size_t k = 0; k < B.nb(); ++k) {
@@ -375,12 +405,15 @@ int Call::encode_batch(Batch &B) {
   return encode(B, r);
 }
 
-// overflow: the block goes again on the generic encoder with a slot that cannot overflow
+// overflow: the block goes again with a slot that cannot overflow, on the chain encoder if it ran there, else on the
+// generic one
 int Call::retry(Batch &B) {
   EncRun &r = B.redo;
   B.redo_of.assign(B.nb(), -1);
+  const size_t c0 = B.first.n_cm, c1 = c0 + B.first.n_chain;
+  for (int pass = 0; pass < 2; ++pass)
   for (size_t k = 0; k < B.nb(); ++k)
-    if (B.first.res[k].overflow) {
+    if (B.first.res[k].overflow && (pass == 0) == (k >= c0 && k < c1)) {
       ZhEncBlock d = B.first.desc[k];
       d.slot_cap = worst_slot(d.n);
       d.slot_off = r.slot_total;
@@ -388,6 +421,7 @@ int Call::retry(Batch &B) {
       B.redo_of[k] = (int64_t)r.desc.size();
       r.desc.push_back(d);
       r.block.push_back(B.first.block[k]);
+      r.n_chain += pass == 0;
     }
   if (r.desc.empty()) return ZPAQHIP_OK;
   const int rc = encode(B, r);
@@ -481,6 +515,6 @@ int zh::compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, cons
   // A known wart, kept for zpaqhip_last_stats' sake: the store layout counts the pre-processing launches, the encoders' path
   // counts its own only.
   if (c.store) c.st.launches = pre->launches;
-  c.st.kernel_kind = c.store ? 0 : c.any_cm ? 2 : 1;
+  c.st.kernel_kind = c.store ? 0 : c.any_chain ? 3 : c.any_cm ? 2 : 1;
   return finish_call(c.v, c.st, c.pos, n_blocks, block_off, out_cap, out_len, err);
 }

@@ -354,6 +354,19 @@ int zpaqhip_compress_method_blocks(zpaqhip_ctx *ctx, const int32_t args[9], cons
                                    size_t n_blocks, const char *const *filenames, uint8_t *out, size_t out_cap, size_t *out_len,
                                    uint64_t *block_off, const zpaqhip_compress_opts *opts, zpaqhip_err *err);
 
+/* ---- the data analysis of LibZPAQ.compressBlock's numeric levels 5..9 (LibZPAQ.cs:242-255) -------------------------------
+ * The histogram of repetition gaps of each block p = in[in_off[i], in_off[i+1]): with pt[256] and r[4096] all zero,
+ *     for j in 0..n-1:  k = j - pt[p[j]];  if 0 < k < 4096: ++r[k];  pt[p[j]] = j
+ * and hist[i * 4096 + k] = r[k] (hist[i * 4096] = 0).  As in the reference pt starts at 0, so a byte value first seen at
+ * position j counts as gap j when 0 < j < 4096, and position 0 counts nothing.  compressBlock picks the periodic context
+ * models of a level 5..9 method from r (zpaqsharp_amd.method.expand_level does the same from this histogram).  Computed on
+ * the GPU (zh_analyze.hip), in batches sized like those of zpaqhip_preprocess_blocks.  A block holds at most 2^31 - 1
+ * bytes (ZPAQHIP_E_ARG beyond); an empty block gives zeros.  zpaqhip_last_stats: kernel_ms = init_ms = the kernel,
+ * launches = its launches, h2d_ms / d2h_ms = the host's time in the copy of the plaintext in and of the histograms out,
+ * in_bytes = plaintext, out_bytes = n_blocks * 16 384. */
+int zpaqhip_gap_hist_blocks(zpaqhip_ctx *ctx, const uint8_t *in, const uint64_t *in_off, size_t n_blocks, uint32_t *hist,
+                            zpaqhip_err *err);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """Compression rate of Context.compress_blocks (or, with --method, Context.compress_method) against the CPU stream writer.
 
     python3 tools/compress_rate.py [--blocks 256] [--block-size 4194304] [--kinds T,R] [--model l1] [--method M] [--bwt]
-                                   [--kernel 0] [--rounds 1] [--decode-kernel K] [--no-cpu]
+                                   [--level L [--analysis-only]] [--kernel 0] [--rounds 1] [--decode-kernel K] [--no-cpu]
 
 Per kind: plaintext MB/s from wall time, the time of each pass (zpaqhip_last_stats: init_ms = model pass, kernel_ms -
 init_ms = coder pass), and the CPU writer
@@ -11,6 +11,12 @@ init_ms = coder pass), and the CPU writer
 ratios are compared, not the bytes); pre_ms = the device pre-processing (init_ms), encoder_ms = the rest of kernel_ms.
 The GPU stream is checked by a round trip through Context.decompress(verify_sha1=True).  --bwt passes bwt=True, the
 opt-in a level 3 method needs (its transform is unique, but the CPU writer is still compared by ratio only).
+
+--level L: a numeric method "LB,R,t" (Context.compress_level).  First the analysis of levels 5..9 on its own, whatever L is:
+Context.gap_hist_blocks (kernel_ms, the host's copy times, wall time with the copies) against synth.gap_hist, the plain host
+loop, on 1 and on 16 threads in this process, the histograms compared.  Then, unless --analysis-only, compress_level itself:
+wall time, its split into analysis and encoding (Context.level_ms), the methods chosen, and a round trip through
+Context.decompress(verify_sha1=True).  --kernel defaults to 2 here.
 
 --model takes any models name (l1, min, mid, max, ...), --method any expanded method string, modelled ones included.
 --kernel K[,K...]: the encoder choice (zpaqhip_compress_opts.kernel; 2 = lane-per-component encoder for chain models).
@@ -76,6 +82,48 @@ def run_method(ctx, a, kernels):
                 print(json.dumps(row), flush=True)
 
 
+def run_level(ctx, a, kernels):
+    for kind in a.kinds.split(","):
+        blocks = [synth.plain(kind, i, a.block_size) for i in range(a.blocks)]
+        mb = a.blocks * a.block_size / 1e6
+        ctx.gap_hist_blocks(blocks[:1])                                     # warm-up
+        row = {"level": a.level, "kind": kind, "blocks": a.blocks, "block_size": a.block_size}
+        for rnd in range(a.rounds):
+            t = time.perf_counter()
+            hist = ctx.gap_hist_blocks(blocks)
+            wall = time.perf_counter() - t
+            st = ctx.stats()
+            row.update({"round": rnd, "analysis_kernel_ms": st.kernel_ms, "analysis_h2d_ms": st.h2d_ms, "analysis_d2h_ms": st.d2h_ms,
+                        "analysis_launches": st.launches, "analysis_wall_ms": wall * 1e3, "analysis_wall_MBps": mb / wall,
+                        "analysis_kernel_MBps": mb / (st.kernel_ms / 1e3)})
+            if not a.no_cpu:
+                for th in (1, 16):
+                    t = time.perf_counter()
+                    want = synth.gap_hist(blocks, threads=th)
+                    row[f"cpu{th}_ms"] = (time.perf_counter() - t) * 1e3
+                row["identical"] = bool((hist == want).all())
+            print(json.dumps(row), flush=True)
+        if a.analysis_only:
+            continue
+        for k in kernels:
+            ctx.compress_level(a.level, blocks[:1], kernel=k)                 # warm-up
+        for rnd in range(a.rounds):
+            for k in kernels:
+                t = time.perf_counter()
+                got = ctx.compress_level(a.level, blocks, kernel=k)
+                gpu_s = time.perf_counter() - t
+                methods = {}
+                for m in ctx.level_methods:
+                    methods[m] = methods.get(m, 0) + 1
+                back = ctx.decompress(got, verify_sha1=True)
+                print(json.dumps({"level": a.level, "kind": kind, "blocks": a.blocks, "block_size": a.block_size, "kernel": k,
+                                  "round": rnd, "gpu_MBps": mb / gpu_s, "gpu_wall_s": gpu_s, "analysis_ms": ctx.level_ms["analysis"],
+                                  "encode_ms": ctx.level_ms["encode"], "ratio": len(got) / (mb * 1e6), "methods": methods,
+                                  "round_trip": bool(back.size == a.blocks * a.block_size and all(
+                                      (back[i * a.block_size:(i + 1) * a.block_size] == blocks[i]).all() for i in range(a.blocks)))}),
+                      flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--blocks", type=int, default=256)
@@ -84,13 +132,17 @@ def main():
     ap.add_argument("--model", default="l1")
     ap.add_argument("--method", default=None)
     ap.add_argument("--bwt", action="store_true", help="accept a level 3 (BWT) method")
-    ap.add_argument("--kernel", default="0", help="encoder choice(s), comma separated; several are alternated")
+    ap.add_argument("--level", default=None, help='numeric method "LB,R,t" (Context.compress_level)')
+    ap.add_argument("--analysis-only", action="store_true", help="with --level: only the gap histogram, GPU against the host loop")
+    ap.add_argument("--kernel", default=None, help="encoder choice(s), comma separated; several are alternated (default 0; 2 with --level)")
     ap.add_argument("--rounds", type=int, default=1, help="runs of each --kernel value")
     ap.add_argument("--decode-kernel", type=int, default=None, help="also time the decoder with this opts.kernel")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU writer")
     a = ap.parse_args()
-    kernels = [int(k) for k in a.kernel.split(",")]
+    kernels = [int(k) for k in (a.kernel or ("2" if a.level else "0")).split(",")]
     with z.Context(0) as ctx:
+        if a.level:
+            return run_level(ctx, a, kernels)
         if a.method:
             return run_method(ctx, a, kernels)
         for kind in a.kinds.split(","):

@@ -65,7 +65,8 @@ SYMBOLS = ("zpaqhip_version", "zpaqhip_strerror", "zpaqhip_device_count", "zpaqh
            "zpaqhip_ctx_destroy", "zpaqhip_last_stats", "zpaqhip_scan", "zpaqhip_decompress",
            "zpaqhip_decompress_segments", "zpaqhip_decompress_cb", "zpaqhip_decode_blocks_device", "zpaqhip_read_device_tables",
            "zpaqhip_block_pcomp", "zpaqhip_decompress_multi", "zpaqhip_decompress_multi_stats", "zpaqhip_block_costs", "zpaqhip_multi_trim",
-           "zpaqhip_compress_blocks", "zpaqhip_preprocess_blocks", "zpaqhip_compress_method_blocks", "zpaqhip_bwt_blocks")
+           "zpaqhip_compress_blocks", "zpaqhip_preprocess_blocks", "zpaqhip_compress_method_blocks", "zpaqhip_bwt_blocks",
+           "zpaqhip_gap_hist_blocks")
 
 _lib = None
 
@@ -116,5 +117,6 @@ def load():
     L.zpaqhip_bwt_blocks.argtypes = [vp, C.c_int, vp, vp, sz, vp, sz, C.POINTER(sz), vp, errp]
     L.zpaqhip_compress_method_blocks.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, sz, C.POINTER(sz), vp,
                                                  C.POINTER(CompressOpts), errp]
+    L.zpaqhip_gap_hist_blocks.argtypes = [vp, vp, vp, sz, vp, errp]
     _lib = L
     return L

@@ -276,6 +276,11 @@ class Context:
         n = 0 method stores them.  ValueError, before the device is touched, for level 3 without
         `bwt=True`, a level 2 `m` outside 1..64 and a block longer than 2^(args[0] + 20) bytes at level 1 or 2 (4096
         less at level 3)."""
+        return self._compress_method(method, blocks, filenames, sha1, tag, kernel, batch_blocks, slot_bytes, bwt)[0]
+
+    def _compress_method(self, method: str, blocks, filenames, sha1: bool, tag: bool, kernel: int, batch_blocks: int,
+                         slot_bytes: int, bwt: bool):
+        """compress_method: (stream bytes, block offsets)."""
         from . import method as mth
         args = mth.parse_args(method)[1]
         plain = [_as_u8(b) for b in blocks]
@@ -284,7 +289,60 @@ class Context:
         cap = sum(mth.pre_bound(args, p.size) for p in plain) + len(plain) * (len(model.header) + 2 * len(model.pcomp) + 4096) + 4096
         return self._compress(model.header, model.pcomp or b"", plain, None, filenames,
                               (1 if sha1 else 0) | (2 if tag else 0) | (4 if bwt else 0), kernel, batch_blocks, slot_bytes, out_cap=cap,
-                              args=args)[0]
+                              args=args)[:2]
+
+    def gap_hist_blocks(self, blocks) -> np.ndarray:
+        """The repetition-gap histogram LibZPAQ.compressBlock takes of a block at levels 5..9 (LibZPAQ.cs:242-255), of each
+        block on the GPU (zpaqhip_gap_hist_blocks): shape (len(blocks), 4096), uint32, [b, k] = positions of block b whose
+        byte value last occurred k positions earlier, or, as the reference's table starts at zero, was first seen at
+        position k.  Equal to synth.gap_hist; method.expand_level reads the periodic models of a level off a row."""
+        plain = [_as_u8(b) for b in blocks]
+        for i, p in enumerate(plain):
+            if p.size > (1 << 31) - 1:
+                raise ValueError(f"block {i} has {p.size} bytes; the analysis takes at most 2^31 - 1")
+        hist = np.zeros((len(plain), 4096), np.uint32)
+        if not plain:
+            return hist
+        buf, offs = _cat(plain)
+        err = Err()
+        rc = self._L.zpaqhip_gap_hist_blocks(self._h, buf.ctypes.data, offs.ctypes.data, len(plain), hist.ctypes.data, C.byref(err))
+        if rc:
+            _raise(err, rc)
+        return hist
+
+    def compress_level(self, level: str, blocks, *, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 2,
+                       batch_blocks: int = 0, slot_bytes: int = 0) -> bytes:
+        """LibZPAQ.compressBlock with a numeric method "LB,R,t" (LibZPAQ.cs:124-323) for each block: `level` is expanded per
+        block by method.expand_level (the block's length gives the x<N> argument; at levels 5..9 its gap histogram, taken by
+        gap_hist_blocks, gives the periodic models), the blocks are grouped by the string they got, each group goes through
+        compress_method(string, ..., bwt=True, kernel=kernel), and the blocks come back in input order.  `kernel` defaults to
+        the lane-per-component encoder for chain models (2): the one-lane encoder needs seconds per 64 KiB of a level 5
+        model.  `level_methods` keeps the expanded string of each block of the last call, `level_ms` its wall time in ms
+        spent on the analysis and on the encoding."""
+        import time
+
+        from . import method as mth
+        if not level or not level[0].isdigit():
+            raise ValueError("a numeric method starts with its level, a digit")
+        plain = [_as_u8(b) for b in blocks]
+        if filenames is not None and len(filenames) != len(plain):
+            raise ValueError("filenames needs one entry per block")
+        t0 = time.perf_counter()
+        hist = self.gap_hist_blocks(plain) if int(level[0]) >= 5 else None
+        t1 = time.perf_counter()
+        expanded = [mth.expand_level(level, p.size, None if hist is None else hist[i]) for i, p in enumerate(plain)]
+        groups = {}
+        for i, m in enumerate(expanded):
+            groups.setdefault(m, []).append(i)
+        parts = [b""] * len(plain)
+        for m, ids in groups.items():
+            out, off = self._compress_method(m, [plain[i] for i in ids], None if filenames is None else [filenames[i] for i in ids],
+                                             sha1, tag, kernel, batch_blocks, slot_bytes, True)
+            for j, i in enumerate(ids):
+                parts[i] = out[int(off[j]):int(off[j + 1])]
+        self.level_methods = expanded
+        self.level_ms = {"analysis": (t1 - t0) * 1e3, "encode": (time.perf_counter() - t1) * 1e3}
+        return b"".join(parts)
 
     def _compress(self, header: bytes, pcomp: bytes, coded, orig, filenames, flags: int, kernel: int, batch_blocks: int,
                   slot_bytes: int, out_cap: Optional[int] = None, args: Optional[List[int]] = None):

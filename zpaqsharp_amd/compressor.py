@@ -5,6 +5,11 @@ Context.compress_blocks (a model; a model that needs a pre-processor other than 
 by Context.compress_method (LibZPAQ.compressBlock's pre-processing levels 0, 1 and 2, with or without E8E9, and with
 `bwt=True` level 3, the Burrows-Wheeler transform; without the keyword a level 3 method is refused).  `kernel` is the
 encoder choice of both (2: ICM / ISSE / MIX chain models on the lane-per-component encoder).
+
+With `level`, a numeric method "LB,R,t" (level, block size digits, redundancy, type), this is LibZPAQ.compress as the
+reference's callers use it (LibZPAQ.cs:84-108): the block size is (2^20 << B) - 4096 unless `block_size` is given, and
+Context.compress_level picks each block's method (LibZPAQ.cs:124-283), on the lane-per-component encoder unless `kernel`
+says otherwise.
 """
 from __future__ import annotations
 
@@ -14,8 +19,19 @@ from . import api
 from .decompresser import Reader, Writer
 
 
-def compress(reader: Reader, writer: Writer, model="l1", block_size: int = 1 << 22, context: Optional[api.Context] = None,
-             batch_blocks: int = 64, method: Optional[str] = None, bwt: bool = False, kernel: int = 0) -> None:
+def compress(reader: Reader, writer: Writer, model="l1", block_size: Optional[int] = None, context: Optional[api.Context] = None,
+             batch_blocks: int = 64, method: Optional[str] = None, bwt: bool = False, kernel: Optional[int] = None,
+             level: Optional[str] = None) -> None:
+    if level is not None:
+        from . import method as mth
+        if method is not None:
+            raise ValueError("give a numeric level or an expanded method, not both")
+        if not level or not level[0].isdigit():
+            raise ValueError("a numeric method starts with its level, a digit")
+        if block_size is None:
+            block_size = mth.level_block_size(level)
+    elif block_size is None:
+        block_size = 1 << 22
     if block_size < 1:
         raise ValueError("block_size must be positive")
     if method is not None:
@@ -27,8 +43,11 @@ def compress(reader: Reader, writer: Writer, model="l1", block_size: int = 1 << 
 
         def flush():
             if blocks:
-                writer.write(ctx.compress_blocks(model, blocks, kernel=kernel) if method is None
-                             else ctx.compress_method(method, blocks, bwt=bwt, kernel=kernel))
+                if level is not None:
+                    writer.write(ctx.compress_level(level, blocks, kernel=2 if kernel is None else kernel))
+                else:
+                    writer.write(ctx.compress_blocks(model, blocks, kernel=kernel or 0) if method is None
+                                 else ctx.compress_method(method, blocks, bwt=bwt, kernel=kernel or 0))
                 blocks.clear()
 
         # A Reader may return fewer bytes than asked before its end (Reader.cs:14-25): only an empty read ends the input,

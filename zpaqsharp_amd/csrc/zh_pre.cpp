@@ -7,9 +7,11 @@
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <string>
 #include <vector>
 
+#include "zh_analyze.h"
 #include "zh_compress.h"
 #include "zh_ctx_view.h"
 #include "zh_pre.h"
@@ -18,6 +20,7 @@ extern "C" hipError_t zh_launch_pre_prefix(const ZhPreLaunch *L, const uint8_t *
 extern "C" hipError_t zh_launch_pre_e8e9(const ZhPreLaunch *L, hipStream_t stream);
 extern "C" hipError_t zh_launch_pre_lz(const ZhPreLaunch *L, uint64_t max_n, hipStream_t stream);
 extern "C" hipError_t zh_launch_pre_bwt(const ZhBwtLaunch *L, hipStream_t stream, uint32_t *launches, uint32_t *rounds);
+extern "C" hipError_t zh_launch_gap_hist(const ZhGapLaunch *L, uint32_t n_blocks, uint64_t max_n, hipStream_t stream);
 
 using namespace zh;
 
@@ -258,7 +261,76 @@ int preprocess_impl(zpaqhip_ctx *ctx, const Method &M, const uint8_t *in, const 
   return finish_call(v, st, pos, n_blocks, out_off, out_cap, out_len, err);
 }
 
+// the repetition-gap histograms of compressBlock's levels 5..9 (LibZPAQ.cs:242-255), zh_analyze.hip
+int gap_hist_impl(zpaqhip_ctx *ctx, const uint8_t *in, const uint64_t *in_off, size_t n_blocks, uint32_t *hist, zpaqhip_err *err) {
+  for (size_t i = 0; i < n_blocks; ++i) {
+    if (in_off[i + 1] < in_off[i] || (!in && in_off[i + 1] > in_off[i])) {
+      set_err(err, ZPAQHIP_E_ARG, (int)i, -1, "block offsets must not decrease");
+      return ZPAQHIP_E_ARG;
+    }
+    if (in_off[i + 1] - in_off[i] > (1ull << 31) - 1) {      // 32-bit positions and counters
+      set_err(err, ZPAQHIP_E_ARG, (int)i, -1, "block longer than 2^31 - 1 bytes");
+      return ZPAQHIP_E_ARG;
+    }
+  }
+  CtxView v = ctx_view(ctx);
+  HIPCHK(hipSetDevice(v.device));
+  uint64_t budget = 0;
+  HIPCHK(device_budget(v.mem_share, 0, &budget));
+  zpaqhip_stats st{};
+  st.blocks = n_blocks;
+  using clk = std::chrono::steady_clock;
+  auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
+  DevMem d_in, d_off, d_hist;
+  for (size_t b0 = 0; b0 < n_blocks;) {
+    const size_t b1 = batch_end(b0, n_blocks, 0, budget, [&](size_t i) { return in_off[i + 1] - in_off[i] + 4 * ZH_GAP_NR + 8; });
+    const size_t nb = b1 - b0;
+    const uint64_t base = in_off[b0], plain = in_off[b1] - base;
+    uint64_t max_n = 0;
+    for (size_t i = b0; i < b1; ++i) max_n = std::max(max_n, in_off[i + 1] - in_off[i]);
+    HIPCHK(d_in.alloc(plain + 16));       // the kernel loads aligned 16-byte groups: the last may reach past the data
+    HIPCHK(d_off.alloc((nb + 1) * 8));
+    HIPCHK(d_hist.alloc(nb * 4 * ZH_GAP_NR));
+    auto t = clk::now();
+    if (plain) HIPCHK(hipMemcpy(d_in.p, in + base, plain, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_off.p, in_off + b0, (nb + 1) * 8, hipMemcpyHostToDevice));
+    st.h2d_ms += ms_since(t);
+    ZhGapLaunch L;
+    L.in = d_in.as<uint8_t>();
+    L.in_off = d_off.as<uint64_t>();
+    L.base = base;
+    L.hist = d_hist.as<uint32_t>();
+    HIPCHK(hipMemsetAsync(d_hist.p, 0, nb * 4 * ZH_GAP_NR, v.stream));
+    HIPCHK(hipEventRecord(v.ev0, v.stream));
+    HIPCHK(zh_launch_gap_hist(&L, (uint32_t)nb, max_n, v.stream));
+    HIPCHK(hipEventRecord(v.ev1, v.stream));
+    HIPCHK(hipStreamSynchronize(v.stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, v.ev0, v.ev1));
+    st.kernel_ms += ms;
+    st.launches += max_n ? 1 : 0;
+    t = clk::now();
+    HIPCHK(hipMemcpy(hist + b0 * ZH_GAP_NR, d_hist.p, nb * 4 * ZH_GAP_NR, hipMemcpyDeviceToHost));
+    st.d2h_ms += ms_since(t);
+    st.in_bytes += plain;
+    b0 = b1;
+  }
+  st.init_ms = st.kernel_ms;
+  st.out_bytes = n_blocks * 4ull * ZH_GAP_NR;
+  *v.stats = st;
+  return ZPAQHIP_OK;
+}
+
 }  // namespace
+
+extern "C" int zpaqhip_gap_hist_blocks(zpaqhip_ctx *ctx, const uint8_t *in, const uint64_t *in_off, size_t n_blocks, uint32_t *hist,
+                                       zpaqhip_err *err) {
+  if (!ctx || (n_blocks && (!in_off || !hist))) {
+    set_err(err, ZPAQHIP_E_ARG, -1, -1);
+    return ZPAQHIP_E_ARG;
+  }
+  return gap_hist_impl(ctx, in, in_off, n_blocks, hist, err);
+}
 
 extern "C" int zpaqhip_preprocess_blocks(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *in, const uint64_t *in_off,
                                          size_t n_blocks, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off,

@@ -591,6 +591,34 @@ void *zpaqgen_method_stream_new(const uint8_t *hdr, size_t hdrlen, const uint8_t
   return s;
 }
 
+// The repetition-gap histogram of compressBlock's levels 5..9 (LibZPAQ.cs:242-255) of each block data[off[b], off[b+1]):
+// hist[b * 4096 + k] = r[k].  pt starts at 0 as in the reference, so a value first seen at position i < 4096 counts as gap
+// i.  The blocks are shared among `threads` host threads.
+void zpaqgen_gap_hist(const uint8_t *data, const uint64_t *off, size_t nblocks, uint32_t *hist, int threads) {
+  std::atomic<size_t> next{0};
+  if (threads < 1) threads = 1;
+  auto work = [&] {
+    for (;;) {
+      const size_t b = next.fetch_add(1);
+      if (b >= nblocks) break;
+      const uint8_t *p = data + off[b];
+      const uint64_t n = off[b + 1] - off[b];
+      uint32_t *r = hist + b * 4096;
+      uint64_t pt[256] = {0};
+      memset(r, 0, 4096 * sizeof(uint32_t));
+      for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t k = i - pt[p[i]];
+        if (k > 0 && k < 4096) ++r[k];
+        pt[p[i]] = i;
+      }
+    }
+  };
+  std::vector<std::thread> th;
+  for (int t = 1; t < threads; ++t) th.emplace_back(work);
+  work();
+  for (auto &t : th) t.join();
+}
+
 const char *zpaqgen_stream_error(void *h) { return ((Stream *)h)->error.c_str(); }
 size_t zpaqgen_stream_size(void *h) { return ((Stream *)h)->bytes.size(); }
 void zpaqgen_stream_copy(void *h, uint8_t *out, uint64_t *offsets) {

@@ -5,6 +5,9 @@ the component letters, and the PCOMP program of the chosen pre-processing level:
     level = N2 & 3:  0 none, 1 `lazy2` (bit-packed LZ77, LibZPAQ.cs:427-572), 2 `lzpre` (byte-aligned LZ77, :575-639),
                      3 `bwtrle` (inverse BWT, :642-795);   N2 in 4..7 adds E8E9 (the stand-alone E8E9 program :802-826)
 
+expand_level is the step in front of it, LibZPAQ.compressBlock's choice of that string for a numeric method "LB,R,t"
+(LibZPAQ.cs:124-283).
+
 The PCOMP source texts below are the reference's programs (they are data the decoder must run, like the built-in model
 bytecodes in models.py); the generator around them is this module's own code.  Context.compress_method and
 compressor.compress(method=...) build their blocks from it; tools/methods.py re-exports it next to the CPU
@@ -25,6 +28,111 @@ def _lg(x: int) -> int:
 
 def _nbits(x: int) -> int:
     return bin(x).count("1")
+
+
+def expand_level(method: str, n: int, hist=None) -> str:
+    """The method string LibZPAQ.compressBlock makes of a numeric method "LB,R,t" for a block of n bytes (LibZPAQ.cs:124-283):
+    L the level 0..9, B the block size digits (not used here), R the redundancy 0..255, t = 0..3 = binary, text, exe, both.
+    Levels 5..9 need `hist`, the block's 4096 repetition-gap counts (Context.gap_hist_blocks, synth.gap_hist), for the
+    periodic models of LibZPAQ.cs:257-280.  The text is the reference's, odd places included: level 4 with 24 <= type < 48
+    runs `sasz` and "1c0,0,511" together without a comma."""
+    if not method or not method[0].isdigit():
+        raise ValueError("a numeric method starts with its level, a digit")
+    arg0 = max(_lg(n + 4095) - 20, 0)
+    commas, arg = 0, [0, 0, 0, 0]
+    for ch in method[1:]:
+        if commas >= 4:
+            break
+        if ch in ",.":
+            commas += 1
+        elif ch.isdigit() and commas < 4:
+            arg[commas] = arg[commas] * 10 + int(ch)
+    typ = 512 if commas == 0 else arg[1] * 4 + arg[2]
+    level = int(method[0])
+    doe8 = (typ & 2) * 2
+    m = f"x{arg0}"
+    htsz = f",{19 + arg0 + (arg0 <= 6)}"                # lz77 hash table size
+    sasz = f",{21 + arg0}"                              # lz77 suffix array size
+    if level == 0:
+        return f"0{arg0},0"
+    if level == 1:
+        if typ < 40:
+            return m + ",0"
+        m += f",{1 + doe8},"
+        if typ < 80:
+            return m + "4,0,1,15"
+        if typ < 128:
+            return m + "4,0,2,16"
+        if typ < 256:
+            return m + "4,0,2" + htsz
+        if typ < 960:
+            return m + "5,0,3" + htsz
+        return m + "6,0,3" + htsz
+    if level == 2:
+        if typ < 32:
+            return m + ",0"
+        m += f",{1 + doe8},"
+        if typ < 64:
+            return m + "4,0,3" + htsz
+        return m + "4,0,7" + sasz + ",1"
+    if level == 3:
+        if typ < 20:
+            return m + ",0"
+        if typ < 48:
+            return m + f",{1 + doe8},4,0,3" + htsz
+        if typ >= 640 or typ & 1:
+            return m + f",{3 + doe8}ci1"
+        return m + f",{2 + doe8},12,0,7" + sasz + ",1c0,0,511i2"
+    if level == 4:
+        if typ < 12:
+            return m + ",0"
+        if typ < 24:
+            return m + f",{1 + doe8},4,0,3" + htsz
+        if typ < 48:
+            return m + f",{2 + doe8},5,0,7" + sasz + "1c0,0,511"
+        if typ < 900:
+            return m + f",{doe8}ci1,1,1,1,2a" + ("w" if typ & 1 else "") + "m"
+        return m + f",{3 + doe8}ci1"
+    # 5..9: slow CM with lots of models, periodic ones from the gap histogram
+    if hist is None:
+        raise ValueError("levels 5 to 9 need the block's gap histogram (hist)")
+    r = [int(x) for x in hist]
+    if len(r) != 4096:
+        raise ValueError("hist has 4096 counts")
+    m += f",{doe8}"
+    m += "w2c0,1010,255i1" if typ & 1 else "w1i1"
+    m += "c256ci1,1,1,1,1,1,2a"
+    n1 = n - r[1] - r[2] - r[3]
+    for _ in range(2):
+        period, score, t = 0, 0.0, 0
+        j = 5
+        while j < 4096 and t < n1:
+            s = r[j] / (256.0 + n1 - t)
+            if s > score:
+                score, period = s, j
+            t += r[j]
+            j += 1
+        if period > 4 and score > 0.1:
+            m += f"c0,0,{999 + period},255i1"
+            if period <= 255:
+                m += f"c0,{period}i1"
+            n1 -= r[period]
+            r[period] = 0
+        else:
+            break
+    return m + "c0,2,0,255i1c0,3,0,0,255i1c0,4,0,0,0,255i1mm16ts19t0"
+
+
+def level_block_size(method: str) -> int:
+    """The block size LibZPAQ.compress cuts its input into for a numeric method (LibZPAQ.cs:86-94): (2^20 << B) - 4096 with B
+    the one or two digits after the level, at most 11, and 4 without them."""
+    bs = 4
+    if len(method) > 1 and method[1].isdigit():
+        bs = int(method[1])
+        if len(method) > 2 and method[2].isdigit():
+            bs = bs * 10 + int(method[2])
+        bs = min(bs, 11)
+    return (0x100000 << bs) - 4096
 
 
 def parse_args(method: str) -> Tuple[str, List[int], str]:

@@ -43,6 +43,8 @@ def load():
         L.zpaqgen_preprocess.restype = C.c_long
         L.zpaqgen_method_stream_new.argtypes = [vp, sz, vp, sz, C.POINTER(C.c_int), C.c_int, C.c_uint64, C.c_uint32, sz, C.c_int]
         L.zpaqgen_method_stream_new.restype = vp
+        L.zpaqgen_gap_hist.argtypes = [vp, vp, sz, vp, C.c_int]
+        L.zpaqgen_gap_hist.restype = None
         L.zpaqgen_stream_error.argtypes = [vp]
         L.zpaqgen_stream_error.restype = C.c_char_p
         L.zpaqgen_stream_size.argtypes = [vp]
@@ -206,3 +208,16 @@ def method_stream(model, args, kind: str = "T", nblocks: int = 1, block_size: in
         return out, offs
     finally:
         L.zpaqgen_stream_free(h)
+
+
+def gap_hist(blocks, threads: int = 1) -> np.ndarray:
+    """The repetition-gap histogram of LibZPAQ.compressBlock's levels 5..9 (LibZPAQ.cs:242-255) of each block, on `threads`
+    host threads: shape (len(blocks), 4096), uint32.  The CPU twin of Context.gap_hist_blocks."""
+    parts = [_u8(b).reshape(-1) for b in blocks]
+    offs = np.zeros(len(parts) + 1, np.uint64)
+    offs[1:] = np.cumsum([p.size for p in parts], dtype=np.uint64) if parts else []
+    buf = np.ascontiguousarray(np.concatenate(parts)) if parts and offs[-1] else np.zeros(1, np.uint8)
+    hist = np.zeros((len(parts), 4096), np.uint32)
+    if parts:
+        load().zpaqgen_gap_hist(buf.ctypes.data, offs.ctypes.data, len(parts), hist.ctypes.data, threads)
+    return hist

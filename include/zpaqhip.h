@@ -281,7 +281,9 @@ int zpaqhip_block_pcomp(zpaqhip_ctx *ctx, const uint8_t *in, size_t in_len, uint
 typedef struct zpaqhip_compress_opts {
   uint32_t struct_size;     /* = sizeof(zpaqhip_compress_opts) */
   uint32_t flags;           /* bit0: store SHA-1 (253 + digest, else 254); bit1: write the 13-byte tag; bit2 (zpaqhip_compress_method_blocks
-                               only): accept level 3 (BWT) methods; NULL opts = 3 */
+                               only): accept level 3 (BWT) methods; bit3 (zpaqhip_compress_method_blocks only): a level 1 / 2 method
+                               with args[5] - args[0] >= 21 is parsed by the reference's suffix-array search (see
+                               zpaqhip_lzsa_blocks); no effect on any other method; NULL opts = 3 */
   uint32_t kernel;          /* 0 auto: single-CM models of the `a<<= K  *d=a  halt` shape (K >= 9) on the window-parallel
                                encoder, the rest on the generic one; 1 every block on the generic encoder (cross-check);
                                2 as 0, but models that fit the lane-per-component kernel (ICM / ISSE / MATCH / MIX chains of at
@@ -324,6 +326,12 @@ int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len
  * (LZBuffer.cs:228-240: n + 5 bytes for n, the end of the block sorting below every byte) from a suffix array built by
  * prefix doubling (zh_pre_bwt.hip); it is an opt-in: zpaqhip_compress_method_blocks takes it with bit2 of opts.flags,
  * zpaqhip_bwt_blocks always.  Everything runs on the GPU (zh_pre_lz.hip, zh_pre_bwt.hip).
+ * A second opt-in (bit3 of opts.flags, zpaqhip_lzsa_blocks always) replaces the greedy parse of a level 1 / 2 method with
+ * args[5] - args[0] >= 21 by the one LZBuffer itself makes for such a method (LZBuffer.cs:246-283, :329-383): a search of up
+ * to 2^args[4] - 1 neighbours on each side in suffix order, scored 8 * length - lg(offset) - 11, with args[6] bytes of
+ * look-ahead, matches up to 49 152 bytes and a literal flush every 4096; the bytes are LZBuffer's (zh_pre_lzsa.hip).  That
+ * route refuses, with ZPAQHIP_E_ARG, level 1 with args[2] < 4, args[2] or args[6] above 255, args[4] above 30 and a block
+ * longer than 2^24 bytes (offsets of 2^24 and more are not written).
  * Refused with ZPAQHIP_E_ARG: level 3 (BWT) without the opt-in (zpaqhip_preprocess_blocks: always); level 2 with args[2]
  * outside 1..64; at level 1 or 2 a block longer than 2^(args[0] + 20) bytes (its offsets would wrap the PCOMP's M), at
  * level 3 than 2^(args[0] + 20) - 4096 bytes (LibZPAQ.cs:289), or than 2^31 - 1 bytes. */
@@ -339,6 +347,12 @@ int zpaqhip_preprocess_blocks(zpaqhip_ctx *ctx, const int32_t args[9], const uin
  * 2^31 - 1 bytes per block. */
 int zpaqhip_bwt_blocks(zpaqhip_ctx *ctx, int doe8, const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
                        uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off, zpaqhip_err *err);
+
+/* LZBuffer's codes of each block for a level 1 / 2 method with args[5] - args[0] >= 21 (ZPAQHIP_E_ARG for any other), from
+ * its suffix-array search, after forward E8E9 when 4 <= args[1] <= 7; out_off, capacity and statistics as for
+ * zpaqhip_preprocess_blocks (init_ms covers the suffix sort, launches counts its kernels as zpaqhip_bwt_blocks does). */
+int zpaqhip_lzsa_blocks(zpaqhip_ctx *ctx, const int32_t args[9], const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
+                        uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off, zpaqhip_err *err);
 
 /* compressBlock of a method for each block, one segment per block, framing as zpaqhip_compress_blocks.  hdr / pcomp are
  * the block header and PCOMP of makeConfig's text for the method; the size comment and SHA-1 (zh_sha1_dev) describe the

@@ -1,6 +1,6 @@
 """Compression rate of Context.compress_blocks (or, with --method, Context.compress_method) against the CPU stream writer.
 
-    python3 tools/compress_rate.py [--blocks 256] [--block-size 4194304] [--kinds T,R] [--model l1] [--method M] [--bwt]
+    python3 tools/compress_rate.py [--blocks 256] [--block-size 4194304] [--kinds T,R] [--model l1] [--method M] [--bwt] [--sa]
                                    [--level L [--analysis-only]] [--kernel 0] [--rounds 1] [--decode-kernel K] [--no-cpu]
 
 Per kind: plaintext MB/s from wall time, the time of each pass (zpaqhip_last_stats: init_ms = model pass, kernel_ms -
@@ -10,7 +10,10 @@ init_ms = coder pass), and the CPU writer
 --method M: Context.compress_method(M) against synth.method_stream (16 host threads, its own greedy hash parse, so the
 ratios are compared, not the bytes); pre_ms = the device pre-processing (init_ms), encoder_ms = the rest of kernel_ms.
 The GPU stream is checked by a round trip through Context.decompress(verify_sha1=True).  --bwt passes bwt=True, the
-opt-in a level 3 method needs (its transform is unique, but the CPU writer is still compared by ratio only).
+opt-in a level 3 method needs (its transform is unique, but the CPU writer is still compared by ratio only).  --sa runs
+every call twice, without and with sa=True (the reference's suffix-array parse, for a level 1 / 2 method with
+args[5] - args[0] >= 21), one line each with "sa" false / true; the CPU writer then makes the same parse (cpu16_*: its
+suffix sort included), and its stream is compared with the sa=True one byte for byte ("identical").
 
 --level L: a numeric method "LB,R,t" (Context.compress_level).  First the analysis of levels 5..9 on its own, whatever L is:
 Context.gap_hist_blocks (kernel_ms, the host's copy times, wall time with the copies) against synth.gap_hist, the plain host
@@ -55,22 +58,24 @@ def run_method(ctx, a, kernels):
         cpu = {}
         if not a.no_cpu:
             t = time.perf_counter()
-            want, _ = synth.method_stream(model, args, kind, nblocks=a.blocks, block_size=a.block_size, threads=16)
+            want, _ = synth.method_stream(model, args, kind, nblocks=a.blocks, block_size=a.block_size, threads=16, sa=a.sa)
             cpu = {"cpu16_MBps": mb / (time.perf_counter() - t), "cpu16_ratio": want.size / (mb * 1e6)}
         first = None
         for k in kernels:
-            ctx.compress_method(a.method, blocks[:1], bwt=a.bwt, kernel=k)    # warm-up
+            for sa in (False, True) if a.sa else (False,):
+                ctx.compress_method(a.method, blocks[:1], bwt=a.bwt, kernel=k, sa=sa)    # warm-up
         for rnd in range(a.rounds):
-            for k in kernels:
+            for k, sa in [(k, sa) for k in kernels for sa in ((False, True) if a.sa else (False,))]:
                 t = time.perf_counter()
-                got = ctx.compress_method(a.method, blocks, bwt=a.bwt, kernel=k)
+                got = ctx.compress_method(a.method, blocks, bwt=a.bwt, kernel=k, sa=sa)
                 gpu_s = time.perf_counter() - t
                 st = ctx.stats()
                 row = {"method": a.method, "kind": kind, "blocks": a.blocks, "block_size": a.block_size, "kernel": k, "round": rnd,
+                       "sa": sa,
                        "gpu_MBps": mb / gpu_s, "gpu_wall_s": gpu_s, "kernel_ms": st.kernel_ms, "pre_ms": st.init_ms,
                        "encoder_ms": st.kernel_ms - st.init_ms, "launches": st.launches, "kernel_kind": st.kernel_kind,
                        "ratio": len(got) / (mb * 1e6)}
-                if first is None:
+                if first is None or a.sa:
                     first = got
                     back = ctx.decompress(got, verify_sha1=True)
                     row["round_trip"] = bool(back.size == a.blocks * a.block_size and all(
@@ -78,6 +83,8 @@ def run_method(ctx, a, kernels):
                     row.update(decode_ms(ctx, a, got))
                 else:
                     row["same_as_first"] = got == first
+                if sa and cpu:
+                    row["identical"] = got == want.tobytes()
                 row.update(cpu)
                 print(json.dumps(row), flush=True)
 
@@ -132,6 +139,7 @@ def main():
     ap.add_argument("--model", default="l1")
     ap.add_argument("--method", default=None)
     ap.add_argument("--bwt", action="store_true", help="accept a level 3 (BWT) method")
+    ap.add_argument("--sa", action="store_true", help="also run with sa=True (the reference's suffix-array parse)")
     ap.add_argument("--level", default=None, help='numeric method "LB,R,t" (Context.compress_level)')
     ap.add_argument("--analysis-only", action="store_true", help="with --level: only the gap histogram, GPU against the host loop")
     ap.add_argument("--kernel", default=None, help="encoder choice(s), comma separated; several are alternated (default 0; 2 with --level)")

@@ -7,7 +7,8 @@ zpaqsharp_amd/method.py (Context.compress_method builds its blocks from them) an
 
 `preprocess(data, args)` is the equivalent of `LZBuffer` (LZBuffer.cs:96-115 formats, :225-486): it produces the byte
 stream those PCOMP programs invert.  Match finding here is a plain greedy hash search — only the CODE FORMAT has to
-agree with the reference, not its parse.
+agree with the reference, not its parse.  With `sa=True`, a level 1 / 2 method with args[5] - args[0] >= 21 gets the
+reference's own parse instead: `lz77_sa`, a literal port of LZBuffer's suffix-array search (LZBuffer.cs:246-283, :332-383).
 """
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ from typing import List
 import numpy as np
 
 from zpaqsharp_amd.method import (_E8E9_TAIL, _lg, _nbits, _pcomp_bwtrle, _pcomp_lazy2, _pcomp_lzpre,  # noqa: F401
-                                  make_config, model_of, parse_args)
+                                  make_config, model_of, parse_args, uses_sa)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -80,6 +81,63 @@ def _matches(d: bytes, min_match: int, max_match: int, max_off: int):
         yield ("lit", lit0, n)
 
 
+def _put_literal1(w: _BitWriter, data: bytes, a: int, b: int):
+    """write_literal, level 1 (LZBuffer.cs:392-406): data[a:b], b > a."""
+    lit = b - a
+    ll = _lg(lit)
+    w.putb(0, 2)
+    ll -= 1
+    while ll > 0:
+        ll -= 1
+        w.putb(1, 1)
+        w.putb((lit >> ll) & 1, 1)
+    w.putb(0, 1)
+    for c in data[a:b]:
+        w.putb(c, 8)
+
+
+def _put_match1(w: _BitWriter, ln: int, off: int, rb: int):
+    """write_match, level 1 (LZBuffer.cs:426-448)."""
+    ll = _lg(ln) - 1
+    off += (1 << rb) - 1
+    lo = _lg(off) - 1 - rb
+    assert 0 <= lo <= 23 and ll >= 2
+    w.putb((lo + 8) >> 3, 2)
+    w.putb(lo & 7, 3)
+    while ll > 2:
+        ll -= 1
+        w.putb(1, 1)
+        w.putb((ln >> ll) & 1, 1)
+    w.putb(0, 1)
+    w.putb(ln & 3, 2)
+    w.putb(off, rb)
+    w.putb(off >> rb, lo)
+
+
+def _put_literal2(out: bytearray, data: bytes, a: int, b: int):
+    """write_literal, level 2 (LZBuffer.cs:407-418)."""
+    while a < b:
+        k = min(64, b - a)
+        out.append(k - 1)
+        out += data[a:a + k]
+        a += k
+
+
+def _put_match2(out: bytearray, ln: int, off: int, m: int):
+    """write_match, level 2 (LZBuffer.cs:451-485)."""
+    off -= 1
+    while ln > 0:
+        len1 = m + 63 if ln > m * 2 + 63 else ln - m if ln > m + 63 else ln
+        assert m <= len1 < m + 64
+        if off < (1 << 16):
+            out += bytes([64 + len1 - m, off >> 8, off & 255])
+        elif off < (1 << 24):
+            out += bytes([128 + len1 - m, off >> 16, (off >> 8) & 255, off & 255])
+        else:
+            out += bytes([192 + len1 - m, off >> 24, (off >> 16) & 255, (off >> 8) & 255, off & 255])
+        ln -= len1
+
+
 def lz77_level1(data: bytes, args: List[int]) -> bytes:
     """Bit-packed codes of LZBuffer level 1 (LZBuffer.cs:96-107, write_literal :387-405, write_match :422-446)."""
     rb = args[0] - 4 if args[0] > 4 else 0
@@ -87,34 +145,9 @@ def lz77_level1(data: bytes, args: List[int]) -> bytes:
     w = _BitWriter()
     for item in _matches(data, min_match, 1 << 16, (1 << 23) - 1):
         if item[0] == "lit":
-            _, a, b = item
-            lit = b - a
-            ll = _lg(lit)
-            w.putb(0, 2)
-            ll -= 1
-            while ll > 0:
-                ll -= 1
-                w.putb(1, 1)
-                w.putb((lit >> ll) & 1, 1)
-            w.putb(0, 1)
-            for c in data[a:b]:
-                w.putb(c, 8)
+            _put_literal1(w, data, item[1], item[2])
         else:
-            _, ln, off = item
-            ll = _lg(ln) - 1
-            off += (1 << rb) - 1
-            lo = _lg(off) - 1 - rb
-            assert 0 <= lo <= 23 and ll >= 2
-            w.putb((lo + 8) >> 3, 2)
-            w.putb(lo & 7, 3)
-            while ll > 2:
-                ll -= 1
-                w.putb(1, 1)
-                w.putb((ln >> ll) & 1, 1)
-            w.putb(0, 1)
-            w.putb(ln & 3, 2)
-            w.putb(off, rb)
-            w.putb(off >> rb, lo)
+            _put_match1(w, item[1], item[2], rb)
     w.flush()
     return bytes(w.out)
 
@@ -126,33 +159,26 @@ def lz77_level2(data: bytes, args: List[int]) -> bytes:
     out = bytearray()
     for item in _matches(data, max(m, 3), m + 63 + 4 * 64, (1 << 24) - 1):
         if item[0] == "lit":
-            _, a, b = item
-            while a < b:
-                k = min(64, b - a)
-                out.append(k - 1)
-                out += data[a:a + k]
-                a += k
+            _put_literal2(out, data, item[1], item[2])
         else:
-            _, ln, off = item
-            off -= 1
-            while ln > 0:
-                len1 = m + 63 if ln > m * 2 + 63 else ln - m if ln > m + 63 else ln
-                assert m <= len1 < m + 64
-                if off < (1 << 16):
-                    out += bytes([64 + len1 - m, off >> 8, off & 255])
-                else:
-                    out += bytes([128 + len1 - m, off >> 16, (off >> 8) & 255, off & 255])
-                ln -= len1
+            _put_match2(out, item[1], item[2], m)
     return bytes(out)
 
 
-def bwt_level3(data: bytes) -> bytes:
-    """LZBuffer.cs:228-240: BWT with the end-of-string byte coded as 255 and its position in the last 4 bytes."""
+# ---------------------------------------------------------------------------------------------------------------------
+# the reference's suffix-array match search (LZBuffer's `isa` path: args[5] - args[0] >= 21, levels 1 and 2)
+# ---------------------------------------------------------------------------------------------------------------------
+MAX_MATCH = 49152                                          # maxMatch = BUFSIZE * 3 (LZBuffer.cs:45, :172)
+MAX_LITERAL = 4096                                         # maxLiteral = BUFSIZE / 4 (LZBuffer.cs:174)
+
+
+def suffix_array(data: bytes) -> np.ndarray:
+    """The suffix array divsufsort gives (the end of the block sorts below every byte), by prefix doubling: there is no
+    suffix-sorting library here and fixtures are small."""
     n = len(data)
     if n == 0:
-        return bytes([255, 0, 0, 0, 0])
+        return np.zeros(0, np.int64)
     a = np.frombuffer(data, np.uint8)
-    # suffix array by prefix doubling (no suffix-sorting library here; fixtures are small)
     rank = a.astype(np.int64)
     sa = np.argsort(rank, kind="stable")
     k = 1
@@ -167,6 +193,132 @@ def bwt_level3(data: bytes) -> bytes:
         if nr.max() == n - 1:
             break
         k *= 2
+    return sa
+
+
+def _match_len(d: bytes, p: int, i: int, l: int, n: int) -> int:
+    """for (; i+l<n && l<maxMatch && in[p+l]==in[i+l]; ++l) (LZBuffer.cs:272), comparing slices."""
+    lim = min(n - i, MAX_MATCH)
+    step = 8
+    while l < lim:
+        e = min(l + step, lim)
+        if d[p + l:p + e] == d[i + l:i + e]:
+            l, step = e, step * 2
+        elif step > 8:
+            step = 8
+        else:
+            while d[p + l] == d[i + l]:
+                l += 1
+            return l
+    return l
+
+
+def sa_window_ok(i: int, h: int, n: int, a0: int) -> bool:
+    """The closed form of `sa[isa[(h + i) & mask]] == h + i` (LZBuffer.cs:256-264): the inverse array covers the window of
+    2^(17 + args[0]) positions that holds i, so look-ahead h is searched iff h + i is inside the block and that window."""
+    return h + i < n and (h + i) >> (17 + a0) == i >> (17 + a0)
+
+
+def lz77_sa_parse(d: bytes, args: List[int], windowed: bool = False):
+    """LZBuffer.fill on its `isa` path (LZBuffer.cs:244-283, :329-383) as the calls it makes: ('lit', a, b) for
+    write_literal of d[a:b] (b > a) and ('match', length, offset) for write_match.  `windowed` keeps the inverse array the
+    way the reference does, one window of 2^(17 + args[0]) slots rebuilt on demand (:256-264), instead of sa_window_ok."""
+    level, min_match, bucket, lookahead, a0 = args[1] & 3, args[2], (1 << args[4]) - 1, args[6], args[0]
+    if (min_match < 4 and level == 1) or (min_match < 1 and level == 2):
+        raise ValueError("match length $3 too small")                # LZBuffer.cs:198-199
+    n = len(d)
+    sa = [int(x) for x in suffix_array(d)]
+    mask = (1 << (17 + a0)) - 1
+    if windowed:
+        isa = [0] * (mask + 1)                                       # libzpaq::Array starts zeroed
+    else:
+        full = [0] * n
+        for j, s in enumerate(sa):
+            full[s] = j
+    i = lit = 0
+    while i < n:
+        blen, bp, blit, bscore = min_match - 1, 0, 0, 0
+        if windowed and sa[isa[i & mask]] != i:
+            for j in range(n):
+                if (sa[j] & ~mask) == (i & ~mask):
+                    isa[sa[j] & mask] = j
+        for h in range(lookahead + 1):
+            if windowed:
+                q = isa[(h + i) & mask]
+                if sa[q] != h + i:
+                    continue
+            else:
+                if not sa_window_ok(i, h, n, a0):
+                    continue
+                q = full[h + i]
+            for j in (-1, 1):
+                for k in range(1, bucket + 1):
+                    if not 0 <= q + j * k < n:
+                        continue
+                    p = sa[q + j * k] - h
+                    if not 0 <= p < i:
+                        continue
+                    l = _match_len(d, p, i, h, n)
+                    l1 = h
+                    while l1 > 0 and d[p + l1 - 1] == d[i + l1 - 1]:
+                        l1 -= 1
+                    score = (l - l1) * 8 - _lg(i - p) - 4 * (lit == 0 and l1 > 0) - 11
+                    for _ in range(h):
+                        score = score * 5 // 8 if score >= 0 else -(-score * 5 // 8)     # C division truncates
+                    if score > bscore:
+                        blen, bp, blit, bscore = l, p, l1, score
+                    if l < blen or l < min_match or l > 255:
+                        break
+            if bscore <= 0 or blen < min_match:
+                break
+        off = i - bp
+        if off > 0 and bscore > 0 and blen - blit >= min_match + (level == 2) * ((off >= 1 << 16) + (off >= 1 << 24)):
+            lit += blit
+            if lit:
+                yield ("lit", i + blit - lit, i + blit)
+            lit = 0
+            yield ("match", blen - blit, off)
+        else:
+            blen = 1
+            lit += 1
+        i += blen
+        if lit >= MAX_LITERAL:
+            yield ("lit", i - lit, i)
+            lit = 0
+    if lit:
+        yield ("lit", n - lit, n)
+
+
+def lz77_sa(data: bytes, args: List[int], windowed: bool = False) -> bytes:
+    """What LZBuffer writes for a level 1 / 2 method with args[5] - args[0] >= 21 (`data` after E8E9 where the method
+    asks for it): the suffix-array parse in the codes of the level."""
+    level = args[1] & 3
+    assert uses_sa(args)
+    if level == 1:
+        rb = args[0] - 4 if args[0] > 4 else 0
+        w = _BitWriter()
+        for item in lz77_sa_parse(data, args, windowed):
+            if item[0] == "lit":
+                _put_literal1(w, data, item[1], item[2])
+            else:
+                _put_match1(w, item[1], item[2], rb)
+        w.flush()
+        return bytes(w.out)
+    out = bytearray()
+    for item in lz77_sa_parse(data, args, windowed):
+        if item[0] == "lit":
+            _put_literal2(out, data, item[1], item[2])
+        else:
+            _put_match2(out, item[1], item[2], args[2])
+    return bytes(out)
+
+
+def bwt_level3(data: bytes) -> bytes:
+    """LZBuffer.cs:228-240: BWT with the end-of-string byte coded as 255 and its position in the last 4 bytes."""
+    n = len(data)
+    if n == 0:
+        return bytes([255, 0, 0, 0, 0])
+    sa = suffix_array(data)
     out = bytearray([data[n - 1]])
     idx = 0
     for i in range(1, n + 1):
@@ -180,10 +332,13 @@ def bwt_level3(data: bytes) -> bytes:
     return bytes(out)
 
 
-def preprocess(data: bytes, args: List[int]) -> bytes:
-    """What compressBlock feeds the coder (LibZPAQ.cs:296-311): LZBuffer output for levels 1-3, E8E9 for 4-7."""
+def preprocess(data: bytes, args: List[int], sa: bool = False) -> bytes:
+    """What compressBlock feeds the coder (LibZPAQ.cs:296-311): LZBuffer output for levels 1-3, E8E9 for 4-7.  `sa`: the
+    reference's suffix-array parse where the method selects it (uses_sa); no effect on any other method."""
     level, doe8 = args[1] & 3, 4 <= args[1] <= 7
     d = e8e9_forward(data) if doe8 else data
+    if sa and uses_sa(args):
+        return lz77_sa(d, args)
     if level == 1:
         return lz77_level1(d, args)
     if level == 2:
@@ -193,17 +348,17 @@ def preprocess(data: bytes, args: List[int]) -> bytes:
     return d
 
 
-def compress_block(method: str, data: bytes, filename: bytes = b"", pre: bytes = None) -> bytes:
+def compress_block(method: str, data: bytes, filename: bytes = b"", pre: bytes = None, sa: bool = False) -> bytes:
     """One block the way LibZPAQ.compressBlock frames it (tag, header, segment with the size as comment, SHA-1), coded by
     this repo's CPU stream writer; n = 0 models (methods like "x0,1,4,0,3,24") use the unmodelled store layout.
     `pre`: bytes to feed the post-processor instead of preprocess(data) (tests of the PCOMP programs on input no
-    encoder writes; the size comment and SHA-1 still describe `data`)."""
+    encoder writes; the size comment and SHA-1 still describe `data`).  `sa`: as for preprocess."""
     import hashlib
 
     from zpaqsharp_amd import synth
     model, args = model_of(method)
     if pre is None:
-        pre = preprocess(data, args)
+        pre = preprocess(data, args, sa)
     if model.n:
         return synth.compress_block(model, np.frombuffer(data, np.uint8) if data else np.zeros(0, np.uint8), filename=filename,
                                     pre=np.frombuffer(pre, np.uint8) if pre else np.zeros(0, np.uint8))

@@ -75,6 +75,8 @@ int finish_call(const CtxView &v, zpaqhip_stats st, uint64_t pos, size_t n_block
 struct Method {
   uint32_t level = 0, doe8 = 0, k = 0, m = 0, rb = 0, max_match = 0, max_off = 0;
   uint64_t max_block = ~0ull;             // levels 1 / 2: 2^(args[0] + 20), the PCOMP's M; level 3: 4096 less (LibZPAQ.cs:289)
+  // levels 1 / 2 with the reference's suffix-array search (tools/methods.lz77_sa, zh_pre_lzsa.hip): k, max_match, max_off unused
+  uint32_t sa = 0, bucket = 0, lookahead = 0, win_bits = 0;
 };
 
 struct PreBatch {                         // what DevPre::run leaves of a batch [b0, b1)
@@ -99,7 +101,7 @@ class DevPre {
   Method M_;
   const uint8_t *in_;
   const uint64_t *in_off_;
-  DevMem plain_, e8_, tab_, chain_, prev_, len_, desc_, pref_;
+  DevMem plain_, e8_, tab_, chain_, prev_, dec_, len_, desc_, pref_;
 };
 
 // The batch loop.  Without `pre`, block i's coded bytes are in[in_off[i], in_off[i+1]) and `orig`, when given, is what the

@@ -1,5 +1,6 @@
 // zh_pre.cpp — LibZPAQ.compressBlock for a method (LibZPAQ.cs:296-323): the pre-processing of levels 0, 1 and 2 and, where
-// the caller asks for it, 3 (BWT), with or without E8E9, on the GPU (zh_pre_lz.hip, zh_pre_bwt.hip).  DevPre is that stage;
+// the caller asks for it, 3 (BWT) and the reference's suffix-array parse of levels 1 / 2 (zh_pre_lzsa.hip), with or without
+// E8E9, on the GPU (zh_pre_lz.hip, zh_pre_bwt.hip).  DevPre is that stage;
 // compress_impl (zh_compress.cpp) runs it in place of its host copy and then codes the bytes where the kernels left them
 // (n >= 1 headers) or stores them (n = 0 headers).  zpaqhip_preprocess_blocks / zpaqhip_bwt_blocks return them as they are.
 #include <hip/hip_runtime.h>
@@ -20,6 +21,8 @@ extern "C" hipError_t zh_launch_pre_prefix(const ZhPreLaunch *L, const uint8_t *
 extern "C" hipError_t zh_launch_pre_e8e9(const ZhPreLaunch *L, hipStream_t stream);
 extern "C" hipError_t zh_launch_pre_lz(const ZhPreLaunch *L, uint64_t max_n, hipStream_t stream);
 extern "C" hipError_t zh_launch_pre_bwt(const ZhBwtLaunch *L, hipStream_t stream, uint32_t *launches, uint32_t *rounds);
+extern "C" hipError_t zh_launch_pre_sufsort(const ZhBwtLaunch *L, hipStream_t stream, uint32_t *launches, uint32_t *c);
+extern "C" hipError_t zh_launch_pre_lzsa(const ZhLzsaLaunch *L, hipStream_t stream, uint32_t *launches);
 extern "C" hipError_t zh_launch_gap_hist(const ZhGapLaunch *L, uint32_t n_blocks, uint64_t max_n, hipStream_t stream);
 
 using namespace zh;
@@ -27,8 +30,9 @@ using namespace zh;
 namespace {
 
 constexpr uint32_t kFlagBwt = 4;          // zpaqhip_compress_opts.flags: accept level 3
+constexpr uint32_t kFlagSa = 8;           // ... the reference's suffix-array search where the method selects it
 
-int parse_method(const int32_t *args, bool bwt, Method &M, zpaqhip_err *err) {
+int parse_method(const int32_t *args, bool bwt, bool sa, Method &M, zpaqhip_err *err) {
   if (!args) { set_err(err, ZPAQHIP_E_ARG, -1, -1); return ZPAQHIP_E_ARG; }
   M.level = (uint32_t)args[1] & 3;
   M.doe8 = args[1] >= 4 && args[1] <= 7;
@@ -53,6 +57,22 @@ int parse_method(const int32_t *args, bool bwt, Method &M, zpaqhip_err *err) {
     M.max_off = (1u << 24) - 1;
   }
   if (M.level) M.max_block = std::min<uint64_t>((1ull << std::min(args[0] + 20, 62)) - (M.level == 3 ? 4096 : 0), (1ull << 31) - 1);
+  if (sa && (M.level == 1 || M.level == 2) && args[5] - args[0] >= 21) {    // LZBuffer.cs:153-158, :205
+    if (M.level == 1 && args[2] < 4) {                                        // LZBuffer.cs:198-199
+      set_err(err, ZPAQHIP_E_ARG, -1, -1, "level 1 needs a minimum match length of 4 or more (args[2])");
+      return ZPAQHIP_E_ARG;
+    }
+    if (args[3] < 0 || args[4] < 0 || args[4] > 30 || args[6] < 0 || args[6] > 255 || args[2] > 255) {
+      set_err(err, ZPAQHIP_E_ARG, -1, -1, "the suffix-array search takes args[2] and args[6] up to 255 and args[4] up to 30");
+      return ZPAQHIP_E_ARG;
+    }
+    M.sa = 1;
+    M.m = (uint32_t)args[2];
+    M.bucket = (1u << args[4]) - 1;
+    M.lookahead = (uint32_t)args[6];
+    M.win_bits = (uint32_t)std::min(17 + args[0], 31);
+    M.max_block = std::min<uint64_t>(M.max_block, 1ull << 24);                // offsets of 2^24 and more are not written
+  }
   return ZPAQHIP_OK;
 }
 
@@ -86,6 +106,7 @@ uint64_t zh::DevPre::scratch(size_t i) const {
   const uint64_t n = n_of(i);
   uint64_t c = n + 64;
   if (M_.level == 3) return c + (M_.doe8 ? n : 0) + bwt_bytes(n) + 8;
+  if (M_.sa) return c + (M_.doe8 ? n : 0) + bwt_bytes(n) + 8 * n + 8;         // the sort's arrays and one decision array
   if (M_.level) c += (M_.doe8 ? n : 0) + 8 * n + (4ull << tab_bits(n));
   return c;
 }
@@ -96,7 +117,8 @@ int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, cons
   const uint64_t np = prefix.size(), base = in_off_[b0], plain = in_off_[b1] - base;
   std::vector<ZhPreBlock> desc(nb);
   uint64_t scr = 0, tab = 0, max_n = 0, max_scr = 0;
-  std::vector<size_t> cut(1, 0);        // level 3: first block of each launch (at most 2^31 - 1 slots per launch)
+  const bool slots = M_.level == 3 || M_.sa;        // the suffix sort's slot space (BWT, suffix-array search)
+  std::vector<size_t> cut(1, 0);        // slots: first block of each launch (at most 2^31 - 1 slots per launch)
   for (size_t j = 0; j < nb; ++j) {
     ZhPreBlock &d = desc[j];
     memset(&d, 0, sizeof d);
@@ -104,7 +126,7 @@ int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, cons
     d.n = n_of(b0 + j);
     d.out_off = off[j] + np;
     d.out_cap = pre_bound(M_, d.n);
-    if (M_.level == 3 && scr + d.n > kBwtSlots) {      // the next launch of zh_launch_pre_bwt starts here
+    if (slots && scr + d.n > kBwtSlots) {      // the next launch of zh_launch_pre_bwt starts here
       cut.push_back(j);
       max_scr = std::max(max_scr, scr);
       scr = 0;
@@ -135,7 +157,7 @@ int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, cons
     HIPCHK(hipMemcpy(pref_.p, prefix.data(), np, hipMemcpyHostToDevice));
   }
   std::vector<uint32_t> starts;
-  if (M_.level == 3) {
+  if (slots) {
     max_scr = std::max(max_scr, scr);
     cut.push_back(nb);
     for (size_t u = 0; u + 1 < cut.size(); ++u) {      // starts of launch u at starts[cut[u] + u ..]
@@ -146,6 +168,7 @@ int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, cons
     HIPCHK(hipMemcpy(tab_.p, starts.data(), starts.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(chain_.alloc(16 * max_scr));             // key[2], val[2]
     HIPCHK(prev_.alloc(4 * max_scr + 1024 * bwt_tiles(max_scr) + 4 * bwt_sums(max_scr) + 4));   // rank, counts, sums, multi
+    if (M_.sa) HIPCHK(dec_.alloc(8 * max_scr));
     if (M_.doe8) HIPCHK(e8_.alloc(plain));
     L.e8 = e8_.as<uint8_t>();
   } else if (M_.level) {
@@ -163,7 +186,7 @@ int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, cons
     for (size_t j = 0; j < nb; ++j)
       if (desc[j].n)
         HIPCHK(hipMemcpyAsync(d_out + desc[j].out_off, plain_.as<uint8_t>() + desc[j].in_off, desc[j].n, hipMemcpyDeviceToDevice, v.stream));
-  if (M_.level == 3) {
+  if (slots) {
     for (size_t u = 0; u + 1 < cut.size(); ++u) {
       ZhBwtLaunch W;
       memset(&W, 0, sizeof W);
@@ -184,7 +207,23 @@ int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, cons
       W.sums = W.counts + 256 * bwt_tiles(max_scr);
       W.multi = W.sums + bwt_sums(max_scr);
       uint32_t rounds = 0;                // the launcher reports its doubling rounds; nothing here uses them
-      HIPCHK(zh_launch_pre_bwt(&W, v.stream, &launches, &rounds));
+      if (!M_.sa) {
+        HIPCHK(zh_launch_pre_bwt(&W, v.stream, &launches, &rounds));
+        continue;
+      }
+      uint32_t c = 0;
+      HIPCHK(zh_launch_pre_sufsort(&W, v.stream, &launches, &c));
+      ZhLzsaLaunch S;
+      memset(&S, 0, sizeof S);
+      S.src = W.src; S.out = d_out; S.blocks = W.blocks; S.out_len = W.out_len; S.starts = W.starts;
+      S.sa = W.val[c];
+      S.rank = W.rank;
+      S.lcp = W.key[c];                   // the sort is done with its keys and with the other pair of arrays
+      S.dec[0] = dec_.as<uint64_t>();
+      S.dec[1] = reinterpret_cast<uint64_t *>(W.key[c ^ 1]);      // key and val of a pair are adjacent: n 64-bit words
+      S.n_blocks = W.n_blocks; S.n = W.n;
+      S.level = M_.level; S.min_match = M_.m; S.bucket = M_.bucket; S.lookahead = M_.lookahead; S.win_bits = M_.win_bits; S.rb = M_.rb;
+      HIPCHK(zh_launch_pre_lzsa(&S, v.stream, &launches));
     }
   } else if (M_.level) {
     HIPCHK(hipMemsetAsync(tab_.p, 0xFF, tab * 4, v.stream));
@@ -193,7 +232,7 @@ int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, cons
   HIPCHK(hipEventRecord(v.ev1, v.stream));
   HIPCHK(hipStreamSynchronize(v.stream));
   HIPCHK(hipEventElapsedTime(&r.ms, v.ev0, v.ev1));
-  launches += (np ? 1 : 0) + (M_.doe8 ? 1 : 0) + (M_.level == 3 ? 0 : M_.level ? 3 : 0);
+  launches += (np ? 1 : 0) + (M_.doe8 ? 1 : 0) + (slots ? 0 : M_.level ? 3 : 0);
   r.len.assign(nb, 0);
   if (M_.level || M_.doe8) HIPCHK(hipMemcpy(r.len.data(), len_.p, nb * 8, hipMemcpyDeviceToHost));
   else
@@ -218,6 +257,7 @@ int check_blocks(const Method &M, const uint8_t *in, const uint64_t *in_off, siz
     if (in_off[i + 1] - in_off[i] > M.max_block) {
       set_err(err, ZPAQHIP_E_ARG, (int)i, -1,
               M.level == 3 ? "block longer than the BWT method allows (2^(args[0] + 20) - 4096, at most 2^31 - 1 bytes)"
+              : M.sa       ? "block longer than the suffix-array search takes (2^(args[0] + 20), at most 2^24 bytes)"
                            : "block longer than the post-processor's M (2^(args[0] + 20) bytes)");
       return ZPAQHIP_E_ARG;
     }
@@ -341,8 +381,25 @@ extern "C" int zpaqhip_preprocess_blocks(zpaqhip_ctx *ctx, const int32_t *args, 
   }
   *out_len = 0;
   Method M;
-  const int rc = parse_method(args, false, M, err);
+  const int rc = parse_method(args, false, false, M, err);
   if (rc) return rc;
+  return preprocess_impl(ctx, M, in, in_off, n_blocks, out, out_cap, out_len, out_off, err);
+}
+
+extern "C" int zpaqhip_lzsa_blocks(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
+                                   uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off, zpaqhip_err *err) {
+  if (!ctx || !out_len || (!out && out_cap) || (n_blocks && !in_off)) {
+    set_err(err, ZPAQHIP_E_ARG, -1, -1);
+    return ZPAQHIP_E_ARG;
+  }
+  *out_len = 0;
+  Method M;
+  const int rc = parse_method(args, false, true, M, err);
+  if (rc) return rc;
+  if (!M.sa) {
+    set_err(err, ZPAQHIP_E_ARG, -1, -1, "not a level 1 / 2 method with args[5] - args[0] >= 21");
+    return ZPAQHIP_E_ARG;
+  }
   return preprocess_impl(ctx, M, in, in_off, n_blocks, out, out_cap, out_len, out_off, err);
 }
 
@@ -371,7 +428,8 @@ extern "C" int zpaqhip_compress_method_blocks(zpaqhip_ctx *ctx, const int32_t *a
   }
   *out_len = 0;
   Method M;
-  int rc = parse_method(args, (resolve_compress_opts(opts).flags & kFlagBwt) != 0, M, err);
+  const uint32_t flags = resolve_compress_opts(opts).flags;
+  int rc = parse_method(args, (flags & kFlagBwt) != 0, (flags & kFlagSa) != 0, M, err);
   if (rc) return rc;
   if ((rc = check_blocks(M, in, in_off, n_blocks, err))) return rc;
   DevPre P(M, in, in_off);

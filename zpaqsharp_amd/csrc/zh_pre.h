@@ -57,3 +57,28 @@ struct ZhBwtLaunch {
   uint32_t max_n;            // the longest block
   uint32_t pad;
 };
+
+// LZBuffer's suffix-array search for levels 1 / 2 (zh_pre_lzsa.hip, LZBuffer.cs:246-283): the slot space, suffix array and
+// ranks of a finished ZhBwtLaunch, searched for all blocks of the launch at once.
+#define ZH_LZSA_MAX_MATCH 49152u   // maxMatch = BUFSIZE * 3 (LZBuffer.cs:45, :172)
+#define ZH_LZSA_MAX_LITERAL 4096u  // maxLiteral = BUFSIZE / 4 (LZBuffer.cs:174)
+
+// a decision: offset (24 bits, 0 = a literal) | blen << 24 (16 bits) | blit << 40 (8 bits)
+struct ZhLzsaLaunch {
+  const uint8_t *src;        // block b's bytes at src + blocks[b].in_off (the E8E9 copy when the method asks for it)
+  uint8_t *out;              // block b's codes at out + blocks[b].out_off
+  const ZhPreBlock *blocks;
+  uint64_t *out_len;         // per block (counted past out_cap)
+  const uint32_t *starts;    // n_blocks + 1, as in ZhBwtLaunch
+  const uint32_t *sa;        // n: the position (as a slot number) of the suffix in each slot
+  const uint32_t *rank;      // n: the slot of each position
+  uint32_t *lcp;             // n: min(common prefix of the suffixes in slots j - 1 and j, ZH_LZSA_MAX_MATCH); 0 at a block's first slot
+  uint64_t *dec[2];          // n each: the decision of a position visited with lit == 0 ([0]) or lit > 0 ([1])
+  uint32_t n_blocks, n;
+  uint32_t level;            // 1 or 2
+  uint32_t min_match;        // args[2]
+  uint32_t bucket;           // 2^args[4] - 1 neighbours per side
+  uint32_t lookahead;        // args[6], at most 255
+  uint32_t win_bits;         // 17 + args[0]: the window of the reference's inverse array
+  uint32_t rb;               // level 1: args[0] - 4 when args[0] > 4, else 0
+};

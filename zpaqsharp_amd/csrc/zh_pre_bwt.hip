@@ -315,31 +315,51 @@ uint32_t bits_of(uint32_t x) {
 
 }  // namespace
 
+namespace {
+
+// The suffix sort of all blocks of the launch: afterwards val[c] is the suffix array and rank[] its inverse, both in slots.
+bool sort_suffixes(Run &R, uint32_t &c, uint32_t *rounds) {
+  const ZhBwtLaunch *L = &R.L;
+  hipStream_t stream = R.stream;
+  hipLaunchKernelGGL(zh_bwt_init, dim3(R.grid()), dim3(256), 0, stream, *L);
+  if (!R.ok() || !R.sort(c, 32)) return false;
+  if (L->n_blocks > 1) {
+    hipLaunchKernelGGL(zh_bwt_blockkey, dim3(R.grid()), dim3(256), 0, stream, *L, c);
+    if (!R.ok() || !R.sort(c, bits_of(L->n_blocks - 1))) return false;
+  }
+  uint32_t multi = 0;
+  if (!R.regroup(c, 4, 1, multi)) return false;
+  const uint32_t bits = bits_of(L->n - 1);
+  for (uint64_t h = 4; multi && h < L->max_n; h *= 2) {      // at most 29 rounds: max_n < 2^31
+    hipLaunchKernelGGL(zh_bwt_build, dim3(R.grid()), dim3(256), 0, stream, *L, c, (uint32_t)h);
+    if (!R.ok() || !R.sort(c, bits) || !R.regroup(c, (uint32_t)h, 0, multi)) return false;
+    if (rounds) ++*rounds;
+  }
+  return true;
+}
+
+}  // namespace
+
 // The BWT of L->n_blocks blocks (L->n <= 2^31 - 1 bytes together).  *launches grows by the kernels launched, *rounds by the
 // doubling rounds after the first sort.
 extern "C" hipError_t zh_launch_pre_bwt(const ZhBwtLaunch *L, hipStream_t stream, uint32_t *launches, uint32_t *rounds) {
   if (!L->n_blocks) return hipSuccess;
   Run R{*L, stream};
   uint32_t c = 0;
-  if (L->n) {
-    hipLaunchKernelGGL(zh_bwt_init, dim3(R.grid()), dim3(256), 0, stream, *L);
-    if (!R.ok() || !R.sort(c, 32)) return R.e;
-    if (L->n_blocks > 1) {
-      hipLaunchKernelGGL(zh_bwt_blockkey, dim3(R.grid()), dim3(256), 0, stream, *L, c);
-      if (!R.ok() || !R.sort(c, bits_of(L->n_blocks - 1))) return R.e;
-    }
-    uint32_t multi = 0;
-    if (!R.regroup(c, 4, 1, multi)) return R.e;
-    const uint32_t bits = bits_of(L->n - 1);
-    for (uint64_t h = 4; multi && h < L->max_n; h *= 2) {      // at most 29 rounds: max_n < 2^31
-      hipLaunchKernelGGL(zh_bwt_build, dim3(R.grid()), dim3(256), 0, stream, *L, c, (uint32_t)h);
-      if (!R.ok() || !R.sort(c, bits) || !R.regroup(c, (uint32_t)h, 0, multi)) return R.e;
-      if (rounds) ++*rounds;
-    }
-  }
+  if (L->n && !sort_suffixes(R, c, rounds)) return R.e;
   const uint64_t threads = (uint64_t)L->n + L->n_blocks;
   hipLaunchKernelGGL(zh_bwt_emit, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream, *L, c);
   R.ok();
+  if (launches) *launches += R.launches;
+  return R.e;
+}
+
+// The suffix sort alone (zh_pre_lzsa.hip searches it): L->val[*c] is the suffix array, L->rank the slot of every position.
+extern "C" hipError_t zh_launch_pre_sufsort(const ZhBwtLaunch *L, hipStream_t stream, uint32_t *launches, uint32_t *c) {
+  *c = 0;
+  if (!L->n_blocks || !L->n) return hipSuccess;
+  Run R{*L, stream};
+  sort_suffixes(R, *c, nullptr);
   if (launches) *launches += R.launches;
   return R.e;
 }

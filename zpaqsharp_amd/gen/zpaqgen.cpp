@@ -327,56 +327,151 @@ static void greedy_parse(const uint8_t *d, size_t n, uint32_t min_match, uint32_
   if (n > lit0) lit(lit0, n);
 }
 
-// level 1 (lazy2's input): 00,n,L[n] literals; mm,mmm,n,ll,r,q matches (LZBuffer.cs:96-107)
+// the codes of level 1 (lazy2's input): 00,n,L[n] literals; mm,mmm,n,ll,r,q matches (LZBuffer.cs:96-107)
+static void lz1_lit(BitW &w, const uint8_t *d, size_t a, size_t b) {
+  const uint32_t litn = (uint32_t)(b - a);
+  int ll = lg32(litn) - 1;
+  w.put(0, 2);
+  while (ll > 0) { --ll; w.put(1, 1); w.put((litn >> ll) & 1, 1); }
+  w.put(0, 1);
+  for (size_t k = a; k < b; ++k) w.put(d[k], 8);
+}
+static void lz1_match(BitW &w, uint32_t ln, uint32_t off, int rb) {
+  int ll = lg32(ln) - 1;
+  off += (1u << rb) - 1;
+  const int lo = lg32(off) - 1 - rb;
+  w.put((uint32_t)((lo + 8) >> 3), 2);
+  w.put((uint32_t)(lo & 7), 3);
+  while (ll > 2) { --ll; w.put(1, 1); w.put((ln >> ll) & 1, 1); }
+  w.put(0, 1);
+  w.put(ln & 3, 2);
+  w.put(off, rb);
+  w.put(off >> rb, lo);
+}
+// the codes of level 2 (lzpre's input): 00xxxxxx x+1 literals; yyxxxxxx y+1 offset bytes, length x+m (LZBuffer.cs:109-112)
+static void lz2_lit(std::vector<uint8_t> &out, const uint8_t *d, size_t a, size_t b) {
+  while (a < b) {
+    const size_t k = b - a < 64 ? b - a : 64;
+    out.push_back((uint8_t)(k - 1));
+    out.insert(out.end(), d + a, d + a + k);
+    a += k;
+  }
+}
+static void lz2_match(std::vector<uint8_t> &out, uint32_t ln, uint32_t off, uint32_t m) {
+  off -= 1;
+  while (ln > 0) {
+    const uint32_t len1 = ln > m * 2 + 63 ? m + 63 : ln > m + 63 ? ln - m : ln;
+    if (off < (1u << 16)) { out.push_back((uint8_t)(64 + len1 - m)); out.push_back((uint8_t)(off >> 8)); out.push_back((uint8_t)off); }
+    else if (off < (1u << 24)) { out.push_back((uint8_t)(128 + len1 - m)); out.push_back((uint8_t)(off >> 16)); out.push_back((uint8_t)(off >> 8)); out.push_back((uint8_t)off); }
+    else { out.push_back((uint8_t)(192 + len1 - m)); out.push_back((uint8_t)(off >> 24)); out.push_back((uint8_t)(off >> 16)); out.push_back((uint8_t)(off >> 8)); out.push_back((uint8_t)off); }
+    ln -= len1;
+  }
+}
+
 static void pre_lz1(const uint8_t *d, size_t n, const int *args, std::vector<uint8_t> &out) {
   const int rb = args[0] > 4 ? args[0] - 4 : 0;
   const uint32_t min_match = args[2] < 4 ? 4 : (uint32_t)args[2];
   BitW w(out);
   greedy_parse(d, n, min_match, 1u << 16, (1u << 23) - 1,
-    [&](size_t a, size_t b) {
-      const uint32_t litn = (uint32_t)(b - a);
-      int ll = lg32(litn) - 1;
-      w.put(0, 2);
-      while (ll > 0) { --ll; w.put(1, 1); w.put((litn >> ll) & 1, 1); }
-      w.put(0, 1);
-      for (size_t k = a; k < b; ++k) w.put(d[k], 8);
-    },
-    [&](uint32_t ln, uint32_t off) {
-      int ll = lg32(ln) - 1;
-      off += (1u << rb) - 1;
-      const int lo = lg32(off) - 1 - rb;
-      w.put((uint32_t)((lo + 8) >> 3), 2);
-      w.put((uint32_t)(lo & 7), 3);
-      while (ll > 2) { --ll; w.put(1, 1); w.put((ln >> ll) & 1, 1); }
-      w.put(0, 1);
-      w.put(ln & 3, 2);
-      w.put(off, rb);
-      w.put(off >> rb, lo);
-    });
+    [&](size_t a, size_t b) { lz1_lit(w, d, a, b); },
+    [&](uint32_t ln, uint32_t off) { lz1_match(w, ln, off, rb); });
   w.flush();
 }
 
-// level 2 (lzpre's input): 00xxxxxx x+1 literals; yyxxxxxx y+1 offset bytes, length x+m (LZBuffer.cs:109-112)
 static void pre_lz2(const uint8_t *d, size_t n, const int *args, std::vector<uint8_t> &out) {
   const uint32_t m = (uint32_t)args[2];
   greedy_parse(d, n, m < 3 ? 3 : m, m + 63 + 4 * 64, (1u << 24) - 1,
-    [&](size_t a, size_t b) {
-      while (a < b) {
-        const size_t k = b - a < 64 ? b - a : 64;
-        out.push_back((uint8_t)(k - 1));
-        out.insert(out.end(), d + a, d + a + k);
-        a += k;
+    [&](size_t a, size_t b) { lz2_lit(out, d, a, b); },
+    [&](uint32_t ln, uint32_t off) { lz2_match(out, ln, off, m); });
+}
+
+// ---------------------------------------------------------------------------
+// The reference's own parse for a level 1 / 2 method with args[5] - args[0] >= 21: LZBuffer's suffix-array search
+// (LZBuffer.cs:246-283), accept rule (:332-346), literal flush (:370-373) and end (:376-383), as tools/methods.lz77_sa
+// ports it; the inverse array is kept whole and the reference's window of 2^(17 + args[0]) slots applied as a rule.
+// ---------------------------------------------------------------------------
+static bool uses_sa(const int *args) { return ((args[1] & 3) == 1 || (args[1] & 3) == 2) && args[5] - args[0] >= 21; }
+
+// suffix array by prefix doubling (the end of the block sorts below every byte); isa = its inverse
+static void suffix_array(const uint8_t *d, size_t n, std::vector<uint32_t> &sa, std::vector<uint32_t> &isa) {
+  sa.resize(n); isa.resize(n);
+  if (!n) return;
+  std::vector<uint64_t> key(n);
+  std::vector<uint32_t> tmp(n);
+  for (size_t i = 0; i < n; ++i) { sa[i] = (uint32_t)i; isa[i] = d[i]; }
+  for (size_t h = 0;; h = h ? 2 * h : 1) {
+    // order by (rank, rank h further on; 0 = past the end)
+    for (size_t i = 0; i < n; ++i) key[i] = (uint64_t)isa[i] << 32 | (h && i + h < n ? isa[i + h] + 1u : 0u);
+    std::sort(sa.begin(), sa.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+    uint32_t r = 0;
+    for (size_t j = 0; j < n; ++j) {
+      if (j && key[sa[j]] != key[sa[j - 1]]) ++r;
+      tmp[sa[j]] = r;
+    }
+    isa.swap(tmp);
+    if (r == n - 1) break;
+  }
+  for (size_t j = 0; j < n; ++j) isa[sa[j]] = (uint32_t)j;
+}
+
+template <class Lit, class Match>
+static void sa_parse(const uint8_t *d, size_t n_, const int *args, Lit lit_out, Match match_out) {
+  const uint32_t n = (uint32_t)n_;
+  const int level = args[1] & 3, min_match = args[2], win = 17 + args[0] > 31 ? 31 : 17 + args[0];
+  const uint32_t bucket = (1u << args[4]) - 1, lookahead = (uint32_t)args[6];
+  const uint32_t max_match = 49152, max_literal = 4096;              // BUFSIZE * 3, BUFSIZE / 4 (LZBuffer.cs:45, :172-174)
+  std::vector<uint32_t> sa, isa;
+  suffix_array(d, n, sa, isa);
+  uint32_t i = 0, lit = 0;
+  while (i < n) {
+    int blen = min_match - 1, blit = 0, bscore = 0;
+    uint32_t bp = 0;
+    for (uint32_t h = 0; h <= lookahead; ++h) {
+      if (h + i >= n || ((h + i) >> win) != (i >> win)) continue;    // sa[isa[(h + i) & mask]] != h + i
+      const uint32_t q = isa[h + i];
+      for (int j = -1; j <= 1; j += 2) {
+        for (uint32_t k = 1; k <= bucket; ++k) {
+          const int64_t at = (int64_t)q + (int64_t)j * k;
+          if (at < 0 || at >= n) break;                              // every further k fails the same test
+          if (sa[at] < h || sa[at] - h >= i) continue;
+          const uint32_t p = sa[at] - h;
+          uint32_t l = h, l1 = h;
+          while (i + l < n && l < max_match && d[p + l] == d[i + l]) ++l;
+          while (l1 > 0 && d[p + l1 - 1] == d[i + l1 - 1]) --l1;
+          int score = (int)(l - l1) * 8 - lg32(i - p) - 4 * (lit == 0 && l1 > 0) - 11;
+          for (uint32_t a = 0; a < h; ++a) score = score * 5 / 8;
+          if (score > bscore) { blen = (int)l; bp = p; blit = (int)l1; bscore = score; }
+          if ((int)l < blen || (int)l < min_match || l > 255) break;
+        }
       }
-    },
-    [&](uint32_t ln, uint32_t off) {
-      off -= 1;
-      while (ln > 0) {
-        const uint32_t len1 = ln > m * 2 + 63 ? m + 63 : ln > m + 63 ? ln - m : ln;
-        if (off < (1u << 16)) { out.push_back((uint8_t)(64 + len1 - m)); out.push_back((uint8_t)(off >> 8)); out.push_back((uint8_t)off); }
-        else { out.push_back((uint8_t)(128 + len1 - m)); out.push_back((uint8_t)(off >> 16)); out.push_back((uint8_t)(off >> 8)); out.push_back((uint8_t)off); }
-        ln -= len1;
-      }
-    });
+      if (bscore <= 0 || blen < min_match) break;
+    }
+    const uint32_t off = i - bp;
+    if (off > 0 && bscore > 0 && blen - blit >= min_match + (level == 2) * ((off >= (1u << 16)) + (off >= (1u << 24)))) {
+      lit += blit;
+      if (lit) lit_out((size_t)(i + blit - lit), (size_t)(i + blit));
+      lit = 0;
+      match_out((uint32_t)(blen - blit), off);
+    } else {
+      blen = 1;
+      ++lit;
+    }
+    i += blen;
+    if (lit >= max_literal) { lit_out((size_t)(i - lit), (size_t)i); lit = 0; }
+  }
+  if (lit) lit_out((size_t)(n - lit), (size_t)n);
+}
+
+static void pre_lzsa(const uint8_t *d, size_t n, const int *args, std::vector<uint8_t> &out) {
+  if ((args[1] & 3) == 1) {
+    const int rb = args[0] > 4 ? args[0] - 4 : 0;
+    BitW w(out);
+    sa_parse(d, n, args, [&](size_t a, size_t b) { lz1_lit(w, d, a, b); }, [&](uint32_t ln, uint32_t off) { lz1_match(w, ln, off, rb); });
+    w.flush();
+  } else {
+    const uint32_t m = (uint32_t)args[2];
+    sa_parse(d, n, args, [&](size_t a, size_t b) { lz2_lit(out, d, a, b); }, [&](uint32_t ln, uint32_t off) { lz2_match(out, ln, off, m); });
+  }
 }
 
 // level 3 (bwtrle's input): BWT, end of string coded as 255, its position in the last 4 bytes (LZBuffer.cs:113-115, :228-240)
@@ -408,10 +503,11 @@ static void pre_bwt(const uint8_t *d, size_t n, std::vector<uint8_t> &out) {
   for (int k = 0; k < 4; ++k) out.push_back((uint8_t)(idx >> (8 * k)));
 }
 
-static void preprocess(const uint8_t *d, size_t n, const int *args, std::vector<uint8_t> &out) {
+static void preprocess(const uint8_t *d, size_t n, const int *args, std::vector<uint8_t> &out, bool sa = false) {
   out.clear();
   const int level = args[1] & 3;
-  if (level == 1) pre_lz1(d, n, args, out);
+  if (sa && uses_sa(args)) pre_lzsa(d, n, args, out);
+  else if (level == 1) pre_lz1(d, n, args, out);
   else if (level == 2) pre_lz2(d, n, args, out);
   else if (level == 3) pre_bwt(d, n, out);
   else out.assign(d, d + n);
@@ -509,20 +605,25 @@ void *zpaqgen_stream_new(const uint8_t *hdr, size_t hdrlen, const uint8_t *pcomp
 
 // What the pre-processor of a method makes of `data` (args[0..8] = the method's numbers, args[1] & 3 = level; the E8E9
 // variants expect the caller to have applied the forward transform).  Returns the size, or -20 with *need set.
-long zpaqgen_preprocess(const int *args, const uint8_t *data, size_t n, uint8_t *out, size_t cap, size_t *need) {
+// sa != 0: a level 1 / 2 method with args[5] - args[0] >= 21 gets the reference's suffix-array parse.
+long zpaqgen_preprocess_sa(const int *args, const uint8_t *data, size_t n, uint8_t *out, size_t cap, size_t *need, int sa) {
   std::vector<uint8_t> v;
-  preprocess(data, n, args, v);
+  preprocess(data, n, args, v, sa != 0);
   if (need) *need = v.size();
   if (v.size() > cap) return ZPAQHIP_E_OUTPUT_FULL;
   if (!v.empty()) memcpy(out, v.data(), v.size());
   return (long)v.size();
 }
 
+long zpaqgen_preprocess(const int *args, const uint8_t *data, size_t n, uint8_t *out, size_t cap, size_t *need) {
+  return zpaqgen_preprocess_sa(args, data, n, out, cap, need, 0);
+}
+
 // Synthetic stream of a METHOD (LibZPAQ.compressBlock's framing): every block's plaintext goes through the method's
 // pre-processor and is then coded with the model of `hdr` — or, for n = 0, stored in length-prefixed chunks
-// (Encoder.cs:39-73) behind the selector and the PCOMP program.
-void *zpaqgen_method_stream_new(const uint8_t *hdr, size_t hdrlen, const uint8_t *pcomp, size_t plen, const int *args, int kind,
-                                uint64_t first_block, uint32_t nblocks, size_t block_size, int threads) {
+// (Encoder.cs:39-73) behind the selector and the PCOMP program.  sa as for zpaqgen_preprocess_sa.
+void *zpaqgen_method_stream_new_sa(const uint8_t *hdr, size_t hdrlen, const uint8_t *pcomp, size_t plen, const int *args, int kind,
+                                   uint64_t first_block, uint32_t nblocks, size_t block_size, int threads, int sa) {
   Stream *s = new Stream();
   if (!zh::host_tables_ok()) { s->error = "table pins failed"; return s; }
   const bool stored = hdrlen > 6 && hdr[6] == 0;
@@ -545,7 +646,7 @@ void *zpaqgen_method_stream_new(const uint8_t *hdr, size_t hdrlen, const uint8_t
         zh::sha1(plain.data(), block_size, sha);
         const uint8_t *src = plain.data();
         if (doe8) { enc = plain; e8e9_forward(enc.data(), enc.size()); src = enc.data(); }
-        preprocess(src, block_size, args, pre);
+        preprocess(src, block_size, args, pre, sa != 0);
         char comment[32];
         snprintf(comment, sizeof comment, "%zu", block_size);
         Out o;
@@ -589,6 +690,11 @@ void *zpaqgen_method_stream_new(const uint8_t *hdr, size_t hdrlen, const uint8_t
   }
   s->offsets.push_back(s->bytes.size());
   return s;
+}
+
+void *zpaqgen_method_stream_new(const uint8_t *hdr, size_t hdrlen, const uint8_t *pcomp, size_t plen, const int *args, int kind,
+                                uint64_t first_block, uint32_t nblocks, size_t block_size, int threads) {
+  return zpaqgen_method_stream_new_sa(hdr, hdrlen, pcomp, plen, args, kind, first_block, nblocks, block_size, threads, 0);
 }
 
 // The repetition-gap histogram of compressBlock's levels 5..9 (LibZPAQ.cs:242-255) of each block data[off[b], off[b+1]):

@@ -43,6 +43,11 @@ def load():
         L.zpaqgen_preprocess.restype = C.c_long
         L.zpaqgen_method_stream_new.argtypes = [vp, sz, vp, sz, C.POINTER(C.c_int), C.c_int, C.c_uint64, C.c_uint32, sz, C.c_int]
         L.zpaqgen_method_stream_new.restype = vp
+        L.zpaqgen_preprocess_sa.argtypes = [C.POINTER(C.c_int), vp, sz, vp, sz, C.POINTER(sz), C.c_int]
+        L.zpaqgen_preprocess_sa.restype = C.c_long
+        L.zpaqgen_method_stream_new_sa.argtypes = [vp, sz, vp, sz, C.POINTER(C.c_int), C.c_int, C.c_uint64, C.c_uint32, sz, C.c_int,
+                                                   C.c_int]
+        L.zpaqgen_method_stream_new_sa.restype = vp
         L.zpaqgen_gap_hist.argtypes = [vp, vp, sz, vp, C.c_int]
         L.zpaqgen_gap_hist.restype = None
         L.zpaqgen_stream_error.argtypes = [vp]
@@ -166,28 +171,30 @@ def stream(model, kind: str = "T", nblocks: int = 1, block_size: int = 1 << 16, 
         L.zpaqgen_stream_free(h)
 
 
-def preprocess(args, data) -> bytes:
+def preprocess(args, data, sa: bool = False) -> bytes:
     """What the pre-processor of a method (LZBuffer.cs:96-115 formats: level = args[1] & 3) makes of `data`: the fast C++
-    twin of tools/methods.preprocess for benchmark-sized inputs (same formats, its own greedy parse)."""
+    twin of tools/methods.preprocess for benchmark-sized inputs (same formats, its own greedy parse).  With `sa`, a level
+    1 / 2 method with args[5] - args[0] >= 21 gets the reference's suffix-array parse: the bytes of tools/methods.lz77_sa.
+    As there, `data` is what the parse reads (after E8E9 where the method asks for it)."""
     L = load()
     d = _u8(data)
     a = (C.c_int * 9)(*[int(x) for x in list(args)[:9]] + [0] * (9 - min(9, len(args))))
     need = C.c_size_t(0)
     out = np.empty(max(16, d.size + d.size // 8 + 64), np.uint8)
-    rc = L.zpaqgen_preprocess(a, d.ctypes.data if d.size else None, d.size, out.ctypes.data, out.size, C.byref(need))
+    rc = L.zpaqgen_preprocess_sa(a, d.ctypes.data if d.size else None, d.size, out.ctypes.data, out.size, C.byref(need), int(sa))
     if rc == -20:
         out = np.empty(need.value, np.uint8)
-        rc = L.zpaqgen_preprocess(a, d.ctypes.data if d.size else None, d.size, out.ctypes.data, out.size, C.byref(need))
+        rc = L.zpaqgen_preprocess_sa(a, d.ctypes.data if d.size else None, d.size, out.ctypes.data, out.size, C.byref(need), int(sa))
     if rc < 0:
         raise RuntimeError(f"zpaqgen_preprocess failed: {rc}")
     return out[:rc].tobytes()
 
 
 def method_stream(model, args, kind: str = "T", nblocks: int = 1, block_size: int = 1 << 16, first_block: int = 0,
-                  threads: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+                  threads: Optional[int] = None, sa: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """`nblocks` distinct blocks written with a METHOD of the reference (LibZPAQ.compressBlock framing): plaintext
     generator `kind`, the method's pre-processor (args as tools/methods.make_config returns them), then the model of
-    `model` — stored chunks for n = 0.  Returns (stream, block offsets)."""
+    `model` — stored chunks for n = 0.  `sa` as for preprocess.  Returns (stream, block offsets)."""
     L = load()
     hdr, pc = _u8(model.header), _u8(model.pcomp or b"")
     a = (C.c_int * 9)(*[int(x) for x in list(args)[:9]] + [0] * (9 - min(9, len(args))))
@@ -196,8 +203,8 @@ def method_stream(model, args, kind: str = "T", nblocks: int = 1, block_size: in
         raise ValueError(f"a BWT block of {block_size} bytes does not fit the post-processor's M (2^{model.header[5]} bytes)")
     if threads is None:
         threads = min(32, os.cpu_count() or 1)
-    h = L.zpaqgen_method_stream_new(hdr.ctypes.data, hdr.size, pc.ctypes.data if pc.size else None, pc.size, a, KINDS[kind],
-                                    first_block, nblocks, block_size, threads)
+    h = L.zpaqgen_method_stream_new_sa(hdr.ctypes.data, hdr.size, pc.ctypes.data if pc.size else None, pc.size, a, KINDS[kind],
+                                       first_block, nblocks, block_size, threads, int(sa))
     try:
         err = L.zpaqgen_stream_error(h)
         if err:

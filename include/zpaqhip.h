@@ -283,7 +283,10 @@ typedef struct zpaqhip_compress_opts {
   uint32_t flags;           /* bit0: store SHA-1 (253 + digest, else 254); bit1: write the 13-byte tag; bit2 (zpaqhip_compress_method_blocks
                                only): accept level 3 (BWT) methods; bit3 (zpaqhip_compress_method_blocks only): a level 1 / 2 method
                                with args[5] - args[0] >= 21 is parsed by the reference's suffix-array search (see
-                               zpaqhip_lzsa_blocks); no effect on any other method; NULL opts = 3 */
+                               zpaqhip_lzsa_blocks); no effect on any other method; bit4 (zpaqhip_compress_method_blocks only): a
+                               level 1 / 2 method with args[5] - args[0] < 21 is parsed by the reference's hash-table search
+                               (see zpaqhip_lzht_blocks); no effect on any other method; bits 3 and 4 may be given together;
+                               NULL opts = 3 */
   uint32_t kernel;          /* 0 auto: single-CM models of the `a<<= K  *d=a  halt` shape (K >= 9) on the window-parallel
                                encoder, the rest on the generic one; 1 every block on the generic encoder (cross-check);
                                2 as 0, but models that fit the lane-per-component kernel (ICM / ISSE / MATCH / MIX chains of at
@@ -332,6 +335,13 @@ int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len
  * look-ahead, matches up to 49 152 bytes and a literal flush every 4096; the bytes are LZBuffer's (zh_pre_lzsa.hip).  That
  * route refuses, with ZPAQHIP_E_ARG, level 1 with args[2] < 4, args[2] or args[6] above 255, args[4] above 30 and a block
  * longer than 2^24 bytes (offsets of 2^24 and more are not written).
+ * A third opt-in (bit4 of opts.flags, zpaqhip_lzht_blocks always) does the same for a level 1 / 2 method with
+ * args[5] - args[0] < 21: LZBuffer's hash-table search (LZBuffer.cs:285-327, :349-368) of the 2^args[4] slots around the
+ * hash of the next args[2] bytes in a table of 2^args[5] entries with 12 - args[0] check bits, scored
+ * 8 * length - lg(offset) - 2 * (literals pending) - 11, matches up to 49 152 bytes, a literal flush every 4096; level 2
+ * with args[2] > 64 searches nothing (zh_pre_lzht.hip).  That route refuses, with ZPAQHIP_E_ARG: args[3] != 0 (the second
+ * hash order) and args[6] != 0 (look-ahead), level 1 with args[2] < 4, level 2 with args[2] < 2, args[2] > 255,
+ * args[0] > 11, args[4] > args[5] or args[4] > 6, args[5] > 30 and a block longer than 2^24 bytes.
  * Refused with ZPAQHIP_E_ARG: level 3 (BWT) without the opt-in (zpaqhip_preprocess_blocks: always); level 2 with args[2]
  * outside 1..64; at level 1 or 2 a block longer than 2^(args[0] + 20) bytes (its offsets would wrap the PCOMP's M), at
  * level 3 than 2^(args[0] + 20) - 4096 bytes (LibZPAQ.cs:289), or than 2^31 - 1 bytes. */
@@ -352,6 +362,12 @@ int zpaqhip_bwt_blocks(zpaqhip_ctx *ctx, int doe8, const uint8_t *in, const uint
  * its suffix-array search, after forward E8E9 when 4 <= args[1] <= 7; out_off, capacity and statistics as for
  * zpaqhip_preprocess_blocks (init_ms covers the suffix sort, launches counts its kernels as zpaqhip_bwt_blocks does). */
 int zpaqhip_lzsa_blocks(zpaqhip_ctx *ctx, const int32_t args[9], const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
+                        uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off, zpaqhip_err *err);
+
+/* LZBuffer's codes of each block for a level 1 / 2 method with args[5] - args[0] < 21 (ZPAQHIP_E_ARG for any other, and for
+ * what the route refuses, see above), from its hash-table search, after forward E8E9 when 4 <= args[1] <= 7; out_off,
+ * capacity and statistics as for zpaqhip_lzsa_blocks (init_ms covers the sort of the positions by hash slot). */
+int zpaqhip_lzht_blocks(zpaqhip_ctx *ctx, const int32_t args[9], const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
                         uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off, zpaqhip_err *err);
 
 /* compressBlock of a method for each block, one segment per block, framing as zpaqhip_compress_blocks.  hdr / pcomp are

@@ -1,6 +1,6 @@
 """Compression rate of Context.compress_blocks (or, with --method, Context.compress_method) against the CPU stream writer.
 
-    python3 tools/compress_rate.py [--blocks 256] [--block-size 4194304] [--kinds T,R] [--model l1] [--method M] [--bwt] [--sa]
+    python3 tools/compress_rate.py [--blocks 256] [--block-size 4194304] [--kinds T,R] [--model l1] [--method M] [--bwt] [--sa | --ht]
                                    [--level L [--analysis-only]] [--kernel 0] [--rounds 1] [--decode-kernel K] [--no-cpu]
 
 Per kind: plaintext MB/s from wall time, the time of each pass (zpaqhip_last_stats: init_ms = model pass, kernel_ms -
@@ -13,7 +13,9 @@ The GPU stream is checked by a round trip through Context.decompress(verify_sha1
 opt-in a level 3 method needs (its transform is unique, but the CPU writer is still compared by ratio only).  --sa runs
 every call twice, without and with sa=True (the reference's suffix-array parse, for a level 1 / 2 method with
 args[5] - args[0] >= 21), one line each with "sa" false / true; the CPU writer then makes the same parse (cpu16_*: its
-suffix sort included), and its stream is compared with the sa=True one byte for byte ("identical").
+suffix sort included), and its stream is compared with the sa=True one byte for byte ("identical").  --ht does the same
+with ht=True (the reference's hash-table parse, for a level 1 / 2 method with args[5] - args[0] < 21), lines with "ht" false /
+true.
 
 --level L: a numeric method "LB,R,t" (Context.compress_level).  First the analysis of levels 5..9 on its own, whatever L is:
 Context.gap_hist_blocks (kernel_ms, the host's copy times, wall time with the copies) against synth.gap_hist, the plain host
@@ -58,24 +60,24 @@ def run_method(ctx, a, kernels):
         cpu = {}
         if not a.no_cpu:
             t = time.perf_counter()
-            want, _ = synth.method_stream(model, args, kind, nblocks=a.blocks, block_size=a.block_size, threads=16, sa=a.sa)
+            want, _ = synth.method_stream(model, args, kind, nblocks=a.blocks, block_size=a.block_size, threads=16, sa=a.sa, ht=a.ht)
             cpu = {"cpu16_MBps": mb / (time.perf_counter() - t), "cpu16_ratio": want.size / (mb * 1e6)}
         first = None
         for k in kernels:
-            for sa in (False, True) if a.sa else (False,):
-                ctx.compress_method(a.method, blocks[:1], bwt=a.bwt, kernel=k, sa=sa)    # warm-up
+            for sa in (False, True) if a.sa or a.ht else (False,):
+                ctx.compress_method(a.method, blocks[:1], bwt=a.bwt, kernel=k, sa=sa and a.sa, ht=sa and a.ht)    # warm-up
         for rnd in range(a.rounds):
-            for k, sa in [(k, sa) for k in kernels for sa in ((False, True) if a.sa else (False,))]:
+            for k, sa in [(k, sa) for k in kernels for sa in ((False, True) if a.sa or a.ht else (False,))]:
                 t = time.perf_counter()
-                got = ctx.compress_method(a.method, blocks, bwt=a.bwt, kernel=k, sa=sa)
+                got = ctx.compress_method(a.method, blocks, bwt=a.bwt, kernel=k, sa=sa and a.sa, ht=sa and a.ht)
                 gpu_s = time.perf_counter() - t
                 st = ctx.stats()
                 row = {"method": a.method, "kind": kind, "blocks": a.blocks, "block_size": a.block_size, "kernel": k, "round": rnd,
-                       "sa": sa,
+                       "ht" if a.ht else "sa": sa,
                        "gpu_MBps": mb / gpu_s, "gpu_wall_s": gpu_s, "kernel_ms": st.kernel_ms, "pre_ms": st.init_ms,
                        "encoder_ms": st.kernel_ms - st.init_ms, "launches": st.launches, "kernel_kind": st.kernel_kind,
                        "ratio": len(got) / (mb * 1e6)}
-                if first is None or a.sa:
+                if first is None or a.sa or a.ht:
                     first = got
                     back = ctx.decompress(got, verify_sha1=True)
                     row["round_trip"] = bool(back.size == a.blocks * a.block_size and all(
@@ -140,6 +142,7 @@ def main():
     ap.add_argument("--method", default=None)
     ap.add_argument("--bwt", action="store_true", help="accept a level 3 (BWT) method")
     ap.add_argument("--sa", action="store_true", help="also run with sa=True (the reference's suffix-array parse)")
+    ap.add_argument("--ht", action="store_true", help="also run with ht=True (the reference's hash-table parse)")
     ap.add_argument("--level", default=None, help='numeric method "LB,R,t" (Context.compress_level)')
     ap.add_argument("--analysis-only", action="store_true", help="with --level: only the gap histogram, GPU against the host loop")
     ap.add_argument("--kernel", default=None, help="encoder choice(s), comma separated; several are alternated (default 0; 2 with --level)")

@@ -9,6 +9,8 @@ zpaqsharp_amd/method.py (Context.compress_method builds its blocks from them) an
 stream those PCOMP programs invert.  Match finding here is a plain greedy hash search — only the CODE FORMAT has to
 agree with the reference, not its parse.  With `sa=True`, a level 1 / 2 method with args[5] - args[0] >= 21 gets the
 reference's own parse instead: `lz77_sa`, a literal port of LZBuffer's suffix-array search (LZBuffer.cs:246-283, :332-383).
+With `ht=True`, a level 1 / 2 method with args[5] - args[0] < 21 gets `lz77_ht`, the port of its hash-table search
+(LZBuffer.cs:285-327, :349-368).
 """
 from __future__ import annotations
 
@@ -17,7 +19,7 @@ from typing import List
 import numpy as np
 
 from zpaqsharp_amd.method import (_E8E9_TAIL, _lg, _nbits, _pcomp_bwtrle, _pcomp_lazy2, _pcomp_lzpre,  # noqa: F401
-                                  make_config, model_of, parse_args, uses_sa)
+                                  make_config, model_of, parse_args, uses_ht, uses_sa)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -289,15 +291,12 @@ def lz77_sa_parse(d: bytes, args: List[int], windowed: bool = False):
         yield ("lit", n - lit, n)
 
 
-def lz77_sa(data: bytes, args: List[int], windowed: bool = False) -> bytes:
-    """What LZBuffer writes for a level 1 / 2 method with args[5] - args[0] >= 21 (`data` after E8E9 where the method
-    asks for it): the suffix-array parse in the codes of the level."""
-    level = args[1] & 3
-    assert uses_sa(args)
-    if level == 1:
+def _write_codes(data: bytes, args: List[int], items) -> bytes:
+    """The parse `items` of `data` in the codes of the method's level (1: bits, 2: bytes)."""
+    if args[1] & 3 == 1:
         rb = args[0] - 4 if args[0] > 4 else 0
         w = _BitWriter()
-        for item in lz77_sa_parse(data, args, windowed):
+        for item in items:
             if item[0] == "lit":
                 _put_literal1(w, data, item[1], item[2])
             else:
@@ -305,12 +304,123 @@ def lz77_sa(data: bytes, args: List[int], windowed: bool = False) -> bytes:
         w.flush()
         return bytes(w.out)
     out = bytearray()
-    for item in lz77_sa_parse(data, args, windowed):
+    for item in items:
         if item[0] == "lit":
             _put_literal2(out, data, item[1], item[2])
         else:
             _put_match2(out, item[1], item[2], args[2])
     return bytes(out)
+
+
+def lz77_sa(data: bytes, args: List[int], windowed: bool = False) -> bytes:
+    """What LZBuffer writes for a level 1 / 2 method with args[5] - args[0] >= 21 (`data` after E8E9 where the method
+    asks for it): the suffix-array parse in the codes of the level."""
+    assert uses_sa(args)
+    return _write_codes(data, args, lz77_sa_parse(data, args, windowed))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the reference's hash-table match search (LZBuffer without `isa`: args[5] - args[0] < 21, levels 1 and 2)
+# ---------------------------------------------------------------------------------------------------------------------
+def ht_shift1(args: List[int]) -> int:
+    """shift1(minMatch>0 ? (args[5]-1)/minMatch+1 : 1) (LZBuffer.cs:182) in C's division, which truncates: args[5] = 0
+    gives 1 where Python's // gives 0."""
+    return int((args[5] - 1) / args[2]) + 1 if args[2] > 0 else 1
+
+
+def ht_h1(d: bytes, args: List[int]) -> np.ndarray:
+    """h1 before the step at each position 0 .. F, F = max(0, n - minMatchBoth), straight from the bytes.  The update
+    h1 = ((h1 * 5) << shift1) + (in[j + minMatch] + 1) * 123456791 (LZBuffer.cs:364) multiplies a term by 5 * 2^shift1 per
+    later step and shift1 * minMatch >= args[5], so after minMatch steps a term has left the masked value: h1 before the
+    step at e is a sum over in[max(e, minMatch) .. e + minMatch - 1].  From F on no step is made (:353) and h1 stays h1[F]."""
+    n, mm = len(d), args[2]
+    F = max(0, n - (mm + 4))
+    term = ((np.frombuffer(d, np.uint8).astype(np.uint64) + np.uint64(1)) * np.uint64(123456791)) & np.uint64(0xFFFFFFFF)
+    W, w = (5 << ht_shift1(args)) & 0xFFFFFFFF, 1
+    h = np.zeros(F + 1, np.uint64)
+    for t in range(1, min(mm, F) + 1):                               # the term of the step t before: in[e - t + minMatch]
+        h[t:] = (h[t:] + np.uint64(w) * term[mm:mm + F + 1 - t]) & np.uint64(0xFFFFFFFF)
+        w = (w * W) & 0xFFFFFFFF
+    return h & np.uint64((1 << args[5]) - 1)
+
+
+def lz77_ht_parse(d: bytes, args: List[int], table: bool = False):
+    """LZBuffer.fill without `isa` and with minMatch2 = lookahead = 0 (LZBuffer.cs:244-252, :285-383) as the calls it
+    makes, in the items of lz77_sa_parse.  `table` keeps h1 and the array ht[] the way the reference does, one store per
+    position the walk passes (:352-367; a dict stands for the zeroed array).  Without it h1 comes from the bytes (ht_h1)
+    and ht[s] when i is searched is the largest j < i with j + minMatchBoth < n whose slot h1(j) ^ ih(j) is s, whatever the
+    parse skipped: what zh_pre_lzht.hip computes."""
+    level, mm, a0 = args[1] & 3, args[2], args[0]
+    if (mm < 4 and level == 1) or (mm < 1 and level == 2):
+        raise ValueError("match length $3 too small")                # LZBuffer.cs:198-199
+    if args[3] or args[6] or (level == 2 and mm < 2) or a0 > 11 or args[4] > args[5]:
+        raise ValueError("the hash-table search is ported for args[3] = args[6] = 0, level 2 from args[2] = 2, args[0] <= 11 "
+                         "and args[4] <= args[5]")
+    n = len(d)
+    checkbits = 12 - a0
+    mask, bucket, htsize, shift1, mmb = (1 << checkbits) - 1, (1 << args[4]) - 1, 1 << args[5], ht_shift1(args), mm + 4
+    search = level == 1 or mm <= 64                                  # LZBuffer.cs:288
+    if table:
+        ht, h1 = {}, 0
+    elif search:
+        F = max(0, n - mmb)
+        H = [int(x) for x in ht_h1(d, args)]
+        last, ins = {}, 0
+    i = lit = 0
+    while i < n:
+        blen, bp, bscore = mm - 1, 0, 0
+        if search:
+            if not table:
+                while ins < i:                                       # every earlier position has been stored
+                    if ins + mmb < n:
+                        last[H[ins] ^ (((ins * 1234547 & 0xFFFFFFFF) >> 19) & bucket)] = ins
+                    ins += 1
+                h1 = H[min(i, F)]
+            for k in range(bucket + 1):
+                if table:
+                    p = ht.get(h1 ^ k, 0)
+                else:
+                    j = last.get(h1 ^ k)
+                    p = 0 if j is None else (j << checkbits) | (d[j + 3] & mask)
+                if p and i + 3 < n and (p & mask) == (d[i + 3] & mask):
+                    p >>= checkbits
+                    if p < i and i + blen <= n and d[p + blen - 1] == d[i + blen - 1]:
+                        l = _match_len(d, p, i, 0, n)
+                        score = l * 8 - _lg(i - p) - 2 * (lit > 0) - 11
+                        if score > bscore:
+                            blen, bp, bscore = l, p, score
+                if blen >= 128:
+                    break
+        off = i - bp
+        if off > 0 and bscore > 0 and blen >= mm + (level == 2) * ((off >= 1 << 16) + (off >= 1 << 24)):
+            if lit:
+                yield ("lit", i - lit, i)
+            lit = 0
+            yield ("match", blen, off)
+        else:
+            blen = 1
+            lit += 1
+        if table:
+            for _ in range(blen):
+                if i + mmb < n:
+                    ih = ((i * 1234547 & 0xFFFFFFFF) >> 19) & bucket
+                    ht[h1 ^ ih] = ((i << checkbits) | (d[i + 3] & mask)) & 0xFFFFFFFF
+                    h1 = ((((h1 * 5) << shift1) & 0xFFFFFFFF) + (d[i + mm] + 1) * 123456791) & (htsize - 1)
+                i += 1
+        else:
+            i += blen
+        if lit >= MAX_LITERAL:
+            yield ("lit", i - lit, i)
+            lit = 0
+    if lit:
+        yield ("lit", n - lit, n)
+
+
+def lz77_ht(data: bytes, args: List[int], table: bool = False) -> bytes:
+    """What LZBuffer writes for a level 1 / 2 method with args[5] - args[0] < 21 (`data` after E8E9 where the method asks
+    for it): the hash-table parse in the codes of the level."""
+    assert uses_ht(args)
+    return _write_codes(data, args, lz77_ht_parse(data, args, table))
 
 
 def bwt_level3(data: bytes) -> bytes:
@@ -332,13 +442,16 @@ def bwt_level3(data: bytes) -> bytes:
     return bytes(out)
 
 
-def preprocess(data: bytes, args: List[int], sa: bool = False) -> bytes:
+def preprocess(data: bytes, args: List[int], sa: bool = False, ht: bool = False) -> bytes:
     """What compressBlock feeds the coder (LibZPAQ.cs:296-311): LZBuffer output for levels 1-3, E8E9 for 4-7.  `sa`: the
-    reference's suffix-array parse where the method selects it (uses_sa); no effect on any other method."""
+    reference's suffix-array parse where the method selects it (uses_sa); `ht`: its hash-table parse where the method
+    selects that (uses_ht).  Neither has an effect on any other method."""
     level, doe8 = args[1] & 3, 4 <= args[1] <= 7
     d = e8e9_forward(data) if doe8 else data
     if sa and uses_sa(args):
         return lz77_sa(d, args)
+    if ht and uses_ht(args):
+        return lz77_ht(d, args)
     if level == 1:
         return lz77_level1(d, args)
     if level == 2:
@@ -348,17 +461,17 @@ def preprocess(data: bytes, args: List[int], sa: bool = False) -> bytes:
     return d
 
 
-def compress_block(method: str, data: bytes, filename: bytes = b"", pre: bytes = None, sa: bool = False) -> bytes:
+def compress_block(method: str, data: bytes, filename: bytes = b"", pre: bytes = None, sa: bool = False, ht: bool = False) -> bytes:
     """One block the way LibZPAQ.compressBlock frames it (tag, header, segment with the size as comment, SHA-1), coded by
     this repo's CPU stream writer; n = 0 models (methods like "x0,1,4,0,3,24") use the unmodelled store layout.
     `pre`: bytes to feed the post-processor instead of preprocess(data) (tests of the PCOMP programs on input no
-    encoder writes; the size comment and SHA-1 still describe `data`).  `sa`: as for preprocess."""
+    encoder writes; the size comment and SHA-1 still describe `data`).  `sa`, `ht`: as for preprocess."""
     import hashlib
 
     from zpaqsharp_amd import synth
     model, args = model_of(method)
     if pre is None:
-        pre = preprocess(data, args, sa)
+        pre = preprocess(data, args, sa, ht)
     if model.n:
         return synth.compress_block(model, np.frombuffer(data, np.uint8) if data else np.zeros(0, np.uint8), filename=filename,
                                     pre=np.frombuffer(pre, np.uint8) if pre else np.zeros(0, np.uint8))

@@ -66,7 +66,7 @@ SYMBOLS = ("zpaqhip_version", "zpaqhip_strerror", "zpaqhip_device_count", "zpaqh
            "zpaqhip_decompress_segments", "zpaqhip_decompress_cb", "zpaqhip_decode_blocks_device", "zpaqhip_read_device_tables",
            "zpaqhip_block_pcomp", "zpaqhip_decompress_multi", "zpaqhip_decompress_multi_stats", "zpaqhip_block_costs", "zpaqhip_multi_trim",
            "zpaqhip_compress_blocks", "zpaqhip_preprocess_blocks", "zpaqhip_compress_method_blocks", "zpaqhip_bwt_blocks",
-           "zpaqhip_gap_hist_blocks", "zpaqhip_lzsa_blocks")
+           "zpaqhip_gap_hist_blocks", "zpaqhip_lzsa_blocks", "zpaqhip_lzht_blocks")
 
 _lib = None
 
@@ -116,6 +116,7 @@ def load():
     L.zpaqhip_preprocess_blocks.argtypes = [vp, vp, vp, vp, sz, vp, sz, C.POINTER(sz), vp, errp]
     L.zpaqhip_bwt_blocks.argtypes = [vp, C.c_int, vp, vp, sz, vp, sz, C.POINTER(sz), vp, errp]
     L.zpaqhip_lzsa_blocks.argtypes = [vp, vp, vp, vp, sz, vp, sz, C.POINTER(sz), vp, errp]
+    L.zpaqhip_lzht_blocks.argtypes = [vp, vp, vp, vp, sz, vp, sz, C.POINTER(sz), vp, errp]
     L.zpaqhip_compress_method_blocks.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, sz, C.POINTER(sz), vp,
                                                  C.POINTER(CompressOpts), errp]
     L.zpaqhip_gap_hist_blocks.argtypes = [vp, vp, vp, sz, vp, errp]

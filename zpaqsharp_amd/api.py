@@ -289,8 +289,32 @@ class Context:
             _raise(err, rc)
         return [out[int(oo[i]):int(oo[i + 1])].tobytes() for i in range(len(plain))]
 
+    def lzht_blocks(self, method: str, blocks) -> List[bytes]:
+        """LZBuffer's codes of each block for a level 1 / 2 method with args[5] - args[0] < 21, from the reference's
+        hash-table search (LZBuffer.cs:285-327, :349-368) on the GPU (zpaqhip_lzht_blocks), after E8E9 where the method asks
+        for it: equal to tools.methods.preprocess(..., ht=True).  ValueError for any other method, and for what the route
+        does not take (method.check_blocks): args[3] != 0, args[6] != 0, level 1 with args[2] < 4, level 2 with args[2] < 2,
+        args[2] > 255, args[0] > 11, args[4] > args[5] or > 6, args[5] > 30, a block longer than 2^24 bytes."""
+        from . import method as mth
+        args = mth.parse_args(method)[1]
+        if not mth.uses_ht(args):
+            raise ValueError("not a level 1 / 2 method with args[5] - args[0] < 21")
+        plain = [_as_u8(b) for b in blocks]
+        mth.check_blocks(args, [p.size for p in plain], ht=True)
+        buf, offs = _cat(plain)
+        a = (C.c_int32 * 9)(*args)
+        cap = sum(mth.pre_bound(args, p.size) for p in plain)
+        oo = np.zeros(len(plain) + 1, np.uint64)
+        out = np.empty(max(1, cap), np.uint8)
+        err, got = Err(), C.c_size_t(0)
+        rc = self._L.zpaqhip_lzht_blocks(self._h, a, buf.ctypes.data, offs.ctypes.data, len(plain), out.ctypes.data, cap,
+                                         C.byref(got), oo.ctypes.data, C.byref(err))
+        if rc:
+            _raise(err, rc)
+        return [out[int(oo[i]):int(oo[i + 1])].tobytes() for i in range(len(plain))]
+
     def compress_method(self, method: str, blocks, *, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 0,
-                        batch_blocks: int = 0, slot_bytes: int = 0, bwt: bool = False, sa: bool = False) -> bytes:
+                        batch_blocks: int = 0, slot_bytes: int = 0, bwt: bool = False, sa: bool = False, ht: bool = False) -> bytes:
         """LibZPAQ.compressBlock(method) for each block (LibZPAQ.cs:296-323, one segment per block) on the GPU: the bytes
         tools.methods.compress_block writes.  Levels 0, 1 and 2 with or without E8E9, and with `bwt=True` level 3; the
         model of an n >= 1 method codes the pre-processed bytes on the encoders of compress_blocks (kernel, batch_blocks,
@@ -298,20 +322,22 @@ class Context:
         n = 0 method stores them.  ValueError, before the device is touched, for level 3 without
         `bwt=True`, a level 2 `m` outside 1..64 and a block longer than 2^(args[0] + 20) bytes at level 1 or 2 (4096
         less at level 3).  `sa=True`: a level 1 / 2 method with args[5] - args[0] >= 21 gets the reference's suffix-array
-        parse (lzsa_blocks; the bytes of tools.methods.compress_block(..., sa=True)); no effect on any other method."""
-        return self._compress_method(method, blocks, filenames, sha1, tag, kernel, batch_blocks, slot_bytes, bwt, sa)[0]
+        parse (lzsa_blocks; the bytes of tools.methods.compress_block(..., sa=True)); no effect on any other method.
+        `ht=True`: one with args[5] - args[0] < 21 gets the reference's hash-table parse (lzht_blocks, with its refusals;
+        the bytes of tools.methods.compress_block(..., ht=True)); no effect on any other method.  Both may be given."""
+        return self._compress_method(method, blocks, filenames, sha1, tag, kernel, batch_blocks, slot_bytes, bwt, sa, ht)[0]
 
     def _compress_method(self, method: str, blocks, filenames, sha1: bool, tag: bool, kernel: int, batch_blocks: int,
-                         slot_bytes: int, bwt: bool, sa: bool = False):
+                         slot_bytes: int, bwt: bool, sa: bool = False, ht: bool = False):
         """compress_method: (stream bytes, block offsets)."""
         from . import method as mth
         args = mth.parse_args(method)[1]
         plain = [_as_u8(b) for b in blocks]
-        mth.check_blocks(args, [p.size for p in plain], bwt=bwt, sa=sa)
+        mth.check_blocks(args, [p.size for p in plain], bwt=bwt, sa=sa, ht=ht)
         model, _ = mth.model_of(method)
         cap = sum(mth.pre_bound(args, p.size) for p in plain) + len(plain) * (len(model.header) + 2 * len(model.pcomp) + 4096) + 4096
         return self._compress(model.header, model.pcomp or b"", plain, None, filenames,
-                              (1 if sha1 else 0) | (2 if tag else 0) | (4 if bwt else 0) | (8 if sa else 0), kernel, batch_blocks, slot_bytes, out_cap=cap,
+                              (1 if sha1 else 0) | (2 if tag else 0) | (4 if bwt else 0) | (8 if sa else 0) | (16 if ht else 0), kernel, batch_blocks, slot_bytes, out_cap=cap,
                               args=args)[:2]
 
     def gap_hist_blocks(self, blocks) -> np.ndarray:
@@ -334,7 +360,7 @@ class Context:
         return hist
 
     def compress_level(self, level: str, blocks, *, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 2,
-                       batch_blocks: int = 0, slot_bytes: int = 0, sa: bool = False) -> bytes:
+                       batch_blocks: int = 0, slot_bytes: int = 0, sa: bool = False, ht: bool = False) -> bytes:
         """LibZPAQ.compressBlock with a numeric method "LB,R,t" (LibZPAQ.cs:124-323) for each block: `level` is expanded per
         block by method.expand_level (the block's length gives the x<N> argument; at levels 5..9 its gap histogram, taken by
         gap_hist_blocks, gives the periodic models), the blocks are grouped by the string they got, each group goes through
@@ -342,7 +368,8 @@ class Context:
         the lane-per-component encoder for chain models (2): the one-lane encoder needs seconds per 64 KiB of a level 5
         model.  `level_methods` keeps the expanded string of each block of the last call, `level_ms` its wall time in ms
         spent on the analysis and on the encoding.  `sa` is compress_method's: the LZ77 strings of levels 2, 3 and 4 then
-        get the reference's suffix-array parse."""
+        get the reference's suffix-array parse.  `ht` likewise: the LZ77 strings of level 1, and those levels 2 to 4 give
+        blocks of low redundancy, then get its hash-table parse."""
         import time
 
         from . import method as mth
@@ -361,7 +388,7 @@ class Context:
         parts = [b""] * len(plain)
         for m, ids in groups.items():
             out, off = self._compress_method(m, [plain[i] for i in ids], None if filenames is None else [filenames[i] for i in ids],
-                                             sha1, tag, kernel, batch_blocks, slot_bytes, True, sa)
+                                             sha1, tag, kernel, batch_blocks, slot_bytes, True, sa, ht)
             for j, i in enumerate(ids):
                 parts[i] = out[int(off[j]):int(off[j + 1])]
         self.level_methods = expanded

@@ -5,7 +5,9 @@ Context.compress_blocks (a model; a model that needs a pre-processor other than 
 by Context.compress_method (LibZPAQ.compressBlock's pre-processing levels 0, 1 and 2, with or without E8E9, and with
 `bwt=True` level 3, the Burrows-Wheeler transform; without the keyword a level 3 method is refused).  `kernel` is the
 encoder choice of both (2: ICM / ISSE / MIX chain models on the lane-per-component encoder).  `sa=True` gives the LZ77
-methods with args[5] - args[0] >= 21 the reference's suffix-array parse (Context.compress_method), with `method` and `level`.
+methods with args[5] - args[0] >= 21 the reference's suffix-array parse (Context.compress_method), with `method` and `level`;
+`ht=True` gives those with args[5] - args[0] < 21 its hash-table parse (args[3] = args[6] = 0 and the other limits of
+Context.lzht_blocks).
 
 With `level`, a numeric method "LB,R,t" (level, block size digits, redundancy, type), this is LibZPAQ.compress as the
 reference's callers use it (LibZPAQ.cs:84-108): the block size is (2^20 << B) - 4096 unless `block_size` is given, and
@@ -22,7 +24,7 @@ from .decompresser import Reader, Writer
 
 def compress(reader: Reader, writer: Writer, model="l1", block_size: Optional[int] = None, context: Optional[api.Context] = None,
              batch_blocks: int = 64, method: Optional[str] = None, bwt: bool = False, kernel: Optional[int] = None,
-             level: Optional[str] = None, sa: bool = False) -> None:
+             level: Optional[str] = None, sa: bool = False, ht: bool = False) -> None:
     if level is not None:
         from . import method as mth
         if method is not None:
@@ -37,7 +39,7 @@ def compress(reader: Reader, writer: Writer, model="l1", block_size: Optional[in
         raise ValueError("block_size must be positive")
     if method is not None:
         from . import method as mth
-        mth.check_blocks(mth.parse_args(method)[1], [block_size], bwt=bwt, sa=sa)
+        mth.check_blocks(mth.parse_args(method)[1], [block_size], bwt=bwt, sa=sa, ht=ht)
     ctx = context or api.Context(0)
     try:
         blocks = []
@@ -45,10 +47,10 @@ def compress(reader: Reader, writer: Writer, model="l1", block_size: Optional[in
         def flush():
             if blocks:
                 if level is not None:
-                    writer.write(ctx.compress_level(level, blocks, kernel=2 if kernel is None else kernel, sa=sa))
+                    writer.write(ctx.compress_level(level, blocks, kernel=2 if kernel is None else kernel, sa=sa, ht=ht))
                 else:
                     writer.write(ctx.compress_blocks(model, blocks, kernel=kernel or 0) if method is None
-                                 else ctx.compress_method(method, blocks, bwt=bwt, kernel=kernel or 0, sa=sa))
+                                 else ctx.compress_method(method, blocks, bwt=bwt, kernel=kernel or 0, sa=sa, ht=ht))
                 blocks.clear()
 
         # A Reader may return fewer bytes than asked before its end (Reader.cs:14-25): only an empty read ends the input,

@@ -77,6 +77,8 @@ struct Method {
   uint64_t max_block = ~0ull;             // levels 1 / 2: 2^(args[0] + 20), the PCOMP's M; level 3: 4096 less (LibZPAQ.cs:289)
   // levels 1 / 2 with the reference's suffix-array search (tools/methods.lz77_sa, zh_pre_lzsa.hip): k, max_match, max_off unused
   uint32_t sa = 0, bucket = 0, lookahead = 0, win_bits = 0;
+  // levels 1 / 2 with the reference's hash-table search (tools/methods.lz77_ht, zh_pre_lzht.hip): m and bucket as above
+  uint32_t ht = 0, ht_bits = 0, checkbits = 0, shift1 = 0, search = 0;
 };
 
 struct PreBatch {                         // what DevPre::run leaves of a batch [b0, b1)

@@ -1,6 +1,6 @@
 // zh_pre.cpp — LibZPAQ.compressBlock for a method (LibZPAQ.cs:296-323): the pre-processing of levels 0, 1 and 2 and, where
-// the caller asks for it, 3 (BWT) and the reference's suffix-array parse of levels 1 / 2 (zh_pre_lzsa.hip), with or without
-// E8E9, on the GPU (zh_pre_lz.hip, zh_pre_bwt.hip).  DevPre is that stage;
+// the caller asks for it, 3 (BWT) and the reference's suffix-array and hash-table parses of levels 1 / 2 (zh_pre_lzsa.hip,
+// zh_pre_lzht.hip), with or without E8E9, on the GPU (zh_pre_lz.hip, zh_pre_bwt.hip).  DevPre is that stage;
 // compress_impl (zh_compress.cpp) runs it in place of its host copy and then codes the bytes where the kernels left them
 // (n >= 1 headers) or stores them (n = 0 headers).  zpaqhip_preprocess_blocks / zpaqhip_bwt_blocks return them as they are.
 #include <hip/hip_runtime.h>
@@ -23,6 +23,7 @@ extern "C" hipError_t zh_launch_pre_lz(const ZhPreLaunch *L, uint64_t max_n, hip
 extern "C" hipError_t zh_launch_pre_bwt(const ZhBwtLaunch *L, hipStream_t stream, uint32_t *launches, uint32_t *rounds);
 extern "C" hipError_t zh_launch_pre_sufsort(const ZhBwtLaunch *L, hipStream_t stream, uint32_t *launches, uint32_t *c);
 extern "C" hipError_t zh_launch_pre_lzsa(const ZhLzsaLaunch *L, hipStream_t stream, uint32_t *launches);
+extern "C" hipError_t zh_launch_pre_lzht(const ZhLzhtLaunch *L, const ZhBwtLaunch *W, hipStream_t stream, uint32_t *launches);
 extern "C" hipError_t zh_launch_gap_hist(const ZhGapLaunch *L, uint32_t n_blocks, uint64_t max_n, hipStream_t stream);
 
 using namespace zh;
@@ -31,16 +32,28 @@ namespace {
 
 constexpr uint32_t kFlagBwt = 4;          // zpaqhip_compress_opts.flags: accept level 3
 constexpr uint32_t kFlagSa = 8;           // ... the reference's suffix-array search where the method selects it
+constexpr uint32_t kFlagHt = 16;          // ... the reference's hash-table search where the method selects it
 
-int parse_method(const int32_t *args, bool bwt, bool sa, Method &M, zpaqhip_err *err) {
+int parse_method(const int32_t *args, bool bwt, bool sa, bool ht, Method &M, zpaqhip_err *err) {
   if (!args) { set_err(err, ZPAQHIP_E_ARG, -1, -1); return ZPAQHIP_E_ARG; }
   M.level = (uint32_t)args[1] & 3;
   M.doe8 = args[1] >= 4 && args[1] <= 7;
+  ht = ht && (M.level == 1 || M.level == 2) && args[5] - args[0] < 21;       // LZBuffer.cs:153-158
+  if (ht) {
+    const char *why = nullptr;
+    if (args[0] < 0 || args[0] > 11) why = "the hash-table search takes args[0] up to 11";
+    else if (args[3] != 0 || args[6] != 0) why = "the hash-table search takes neither a second hash order (args[3]) nor look-ahead (args[6])";
+    else if (args[2] < (M.level == 1 ? 4 : 2) || args[2] > 255)             // LZBuffer.cs:198-199, :317
+      why = "the hash-table search needs a minimum match length (args[2]) of 4 (level 1) or 2 (level 2) to 255";
+    else if (args[5] < 0 || args[5] > 30 || args[4] < 0 || args[4] > args[5] || args[4] > (int32_t)ZH_LZHT_MAX_BUCKET_BITS)
+      why = "the hash-table search takes args[5] up to 30 and args[4] up to args[5] and 6";
+    if (why) { set_err(err, ZPAQHIP_E_ARG, -1, -1, why); return ZPAQHIP_E_ARG; }
+  }
   if (M.level == 3 && !bwt) {
     set_err(err, ZPAQHIP_E_ARG, -1, -1, "BWT (level 3) pre-processing is not available on the GPU");
     return ZPAQHIP_E_ARG;
   }
-  if (M.level == 2 && (args[2] < 1 || args[2] > 64)) {
+  if (M.level == 2 && (args[2] < 1 || args[2] > 64) && !ht) {
     set_err(err, ZPAQHIP_E_ARG, -1, -1, "level 2 needs a minimum match length of 1 to 64 (args[2])");
     return ZPAQHIP_E_ARG;
   }
@@ -73,11 +86,23 @@ int parse_method(const int32_t *args, bool bwt, bool sa, Method &M, zpaqhip_err 
     M.win_bits = (uint32_t)std::min(17 + args[0], 31);
     M.max_block = std::min<uint64_t>(M.max_block, 1ull << 24);                // offsets of 2^24 and more are not written
   }
+  if (ht) {
+    M.ht = 1;
+    M.m = (uint32_t)args[2];
+    M.bucket = (1u << args[4]) - 1;
+    M.ht_bits = (uint32_t)args[5];
+    M.checkbits = (uint32_t)(12 - args[0]);
+    M.shift1 = (uint32_t)((args[5] - 1) / args[2] + 1);                       // C division: args[5] = 0 gives 1
+    M.search = M.level == 1 || args[2] <= 64;                                 // LZBuffer.cs:288
+    M.max_block = std::min<uint64_t>(M.max_block, 1ull << 24);
+  }
   return ZPAQHIP_OK;
 }
 
 // pre-processed bytes at most: a literal run of L costs 8L + 2 lg(L) + 1 <= 11L bits and a match of l >= 4 at most 8l bits
-// (level 1); a literal costs at most 2 bytes and a match piece at most 4 bytes for 3 or more bytes (level 2)
+// (level 1); a literal costs at most 2 bytes and a match piece at most 4 bytes for 3 or more bytes (level 2).  The
+// hash-table search accepts a match of l bytes at offset o only with 8 l > lg(o) + 11: at level 2 that is
+// l >= 2, 3 bytes for 2, and a piece of a split match has args[2] >= 2 bytes for at most 4
 uint64_t pre_bound(const Method &M, uint64_t n) {
   if (M.level == 1) return (11 * n + 7) / 8 + 16;
   if (M.level == 2) return 2 * n + 64;
@@ -106,7 +131,7 @@ uint64_t zh::DevPre::scratch(size_t i) const {
   const uint64_t n = n_of(i);
   uint64_t c = n + 64;
   if (M_.level == 3) return c + (M_.doe8 ? n : 0) + bwt_bytes(n) + 8;
-  if (M_.sa) return c + (M_.doe8 ? n : 0) + bwt_bytes(n) + 8 * n + 8;         // the sort's arrays and one decision array
+  if (M_.sa || M_.ht) return c + (M_.doe8 ? n : 0) + bwt_bytes(n) + 8 * n + 8;         // the sort's arrays and one decision array
   if (M_.level) c += (M_.doe8 ? n : 0) + 8 * n + (4ull << tab_bits(n));
   return c;
 }
@@ -117,7 +142,7 @@ int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, cons
   const uint64_t np = prefix.size(), base = in_off_[b0], plain = in_off_[b1] - base;
   std::vector<ZhPreBlock> desc(nb);
   uint64_t scr = 0, tab = 0, max_n = 0, max_scr = 0;
-  const bool slots = M_.level == 3 || M_.sa;        // the suffix sort's slot space (BWT, suffix-array search)
+  const bool slots = M_.level == 3 || M_.sa || M_.ht;      // the sort's slot space (BWT, suffix-array and hash-table search)
   std::vector<size_t> cut(1, 0);        // slots: first block of each launch (at most 2^31 - 1 slots per launch)
   for (size_t j = 0; j < nb; ++j) {
     ZhPreBlock &d = desc[j];
@@ -168,7 +193,7 @@ int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, cons
     HIPCHK(hipMemcpy(tab_.p, starts.data(), starts.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(chain_.alloc(16 * max_scr));             // key[2], val[2]
     HIPCHK(prev_.alloc(4 * max_scr + 1024 * bwt_tiles(max_scr) + 4 * bwt_sums(max_scr) + 4));   // rank, counts, sums, multi
-    if (M_.sa) HIPCHK(dec_.alloc(8 * max_scr));
+    if (M_.sa || M_.ht) HIPCHK(dec_.alloc(8 * max_scr));
     if (M_.doe8) HIPCHK(e8_.alloc(plain));
     L.e8 = e8_.as<uint8_t>();
   } else if (M_.level) {
@@ -207,6 +232,17 @@ int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, cons
       W.sums = W.counts + 256 * bwt_tiles(max_scr);
       W.multi = W.sums + bwt_sums(max_scr);
       uint32_t rounds = 0;                // the launcher reports its doubling rounds; nothing here uses them
+      if (M_.ht) {
+        ZhLzhtLaunch H;
+        memset(&H, 0, sizeof H);
+        H.src = W.src; H.out = d_out; H.blocks = W.blocks; H.out_len = W.out_len; H.starts = W.starts;
+        H.dec[0] = dec_.as<uint64_t>();
+        H.n_blocks = W.n_blocks; H.n = W.n;
+        H.level = M_.level; H.min_match = M_.m; H.bucket = M_.bucket; H.ht_bits = M_.ht_bits; H.checkbits = M_.checkbits;
+        H.shift1 = M_.shift1; H.search = M_.search; H.rb = M_.rb;
+        HIPCHK(zh_launch_pre_lzht(&H, &W, v.stream, &launches));
+        continue;
+      }
       if (!M_.sa) {
         HIPCHK(zh_launch_pre_bwt(&W, v.stream, &launches, &rounds));
         continue;
@@ -258,6 +294,7 @@ int check_blocks(const Method &M, const uint8_t *in, const uint64_t *in_off, siz
       set_err(err, ZPAQHIP_E_ARG, (int)i, -1,
               M.level == 3 ? "block longer than the BWT method allows (2^(args[0] + 20) - 4096, at most 2^31 - 1 bytes)"
               : M.sa       ? "block longer than the suffix-array search takes (2^(args[0] + 20), at most 2^24 bytes)"
+              : M.ht       ? "block longer than the hash-table search takes (2^(args[0] + 20), at most 2^24 bytes)"
                            : "block longer than the post-processor's M (2^(args[0] + 20) bytes)");
       return ZPAQHIP_E_ARG;
     }
@@ -381,7 +418,7 @@ extern "C" int zpaqhip_preprocess_blocks(zpaqhip_ctx *ctx, const int32_t *args, 
   }
   *out_len = 0;
   Method M;
-  const int rc = parse_method(args, false, false, M, err);
+  const int rc = parse_method(args, false, false, false, M, err);
   if (rc) return rc;
   return preprocess_impl(ctx, M, in, in_off, n_blocks, out, out_cap, out_len, out_off, err);
 }
@@ -394,10 +431,27 @@ extern "C" int zpaqhip_lzsa_blocks(zpaqhip_ctx *ctx, const int32_t *args, const 
   }
   *out_len = 0;
   Method M;
-  const int rc = parse_method(args, false, true, M, err);
+  const int rc = parse_method(args, false, true, false, M, err);
   if (rc) return rc;
   if (!M.sa) {
     set_err(err, ZPAQHIP_E_ARG, -1, -1, "not a level 1 / 2 method with args[5] - args[0] >= 21");
+    return ZPAQHIP_E_ARG;
+  }
+  return preprocess_impl(ctx, M, in, in_off, n_blocks, out, out_cap, out_len, out_off, err);
+}
+
+extern "C" int zpaqhip_lzht_blocks(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
+                                   uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off, zpaqhip_err *err) {
+  if (!ctx || !out_len || (!out && out_cap) || (n_blocks && !in_off)) {
+    set_err(err, ZPAQHIP_E_ARG, -1, -1);
+    return ZPAQHIP_E_ARG;
+  }
+  *out_len = 0;
+  Method M;
+  const int rc = parse_method(args, false, false, true, M, err);
+  if (rc) return rc;
+  if (!M.ht) {
+    set_err(err, ZPAQHIP_E_ARG, -1, -1, "not a level 1 / 2 method with args[5] - args[0] < 21");
     return ZPAQHIP_E_ARG;
   }
   return preprocess_impl(ctx, M, in, in_off, n_blocks, out, out_cap, out_len, out_off, err);
@@ -429,7 +483,7 @@ extern "C" int zpaqhip_compress_method_blocks(zpaqhip_ctx *ctx, const int32_t *a
   *out_len = 0;
   Method M;
   const uint32_t flags = resolve_compress_opts(opts).flags;
-  int rc = parse_method(args, (flags & kFlagBwt) != 0, (flags & kFlagSa) != 0, M, err);
+  int rc = parse_method(args, (flags & kFlagBwt) != 0, (flags & kFlagSa) != 0, (flags & kFlagHt) != 0, M, err);
   if (rc) return rc;
   if ((rc = check_blocks(M, in, in_off, n_blocks, err))) return rc;
   DevPre P(M, in, in_off);

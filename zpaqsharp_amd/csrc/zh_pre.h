@@ -63,7 +63,8 @@ struct ZhBwtLaunch {
 #define ZH_LZSA_MAX_MATCH 49152u   // maxMatch = BUFSIZE * 3 (LZBuffer.cs:45, :172)
 #define ZH_LZSA_MAX_LITERAL 4096u  // maxLiteral = BUFSIZE / 4 (LZBuffer.cs:174)
 
-// a decision: offset (24 bits, 0 = a literal) | blen << 24 (16 bits) | blit << 40 (8 bits)
+// a decision: offset (24 bits, 0 = a literal) | blen << 24 (16 bits) | blit << 40 (8 bits) | 1 << 48 where the compare
+// stopped at blen and the walk extends the match (zh_pre_lzht.hip only)
 struct ZhLzsaLaunch {
   const uint8_t *src;        // block b's bytes at src + blocks[b].in_off (the E8E9 copy when the method asks for it)
   uint8_t *out;              // block b's codes at out + blocks[b].out_off
@@ -82,3 +83,34 @@ struct ZhLzsaLaunch {
   uint32_t win_bits;         // 17 + args[0]: the window of the reference's inverse array
   uint32_t rb;               // level 1: args[0] - 4 when args[0] > 4, else 0
 };
+
+// LZBuffer's hash-table search for levels 1 / 2 (zh_pre_lzht.hip, LZBuffer.cs:285-327, :349-368) with minMatch2 = lookahead
+// = 0.  The table is never built: the positions of a launch are sorted by the slot they are stored in, and ht[s] when i
+// is searched is the predecessor of (s, i) in that order.
+#define ZH_LZHT_CMP 256u           // bytes a lane of zh_lzht_search compares at most; a match that reaches it is extended by the walk
+#define ZH_LZHT_MAX_BUCKET_BITS 6  // args[4] at most on this route
+
+struct ZhLzhtLaunch {
+  const uint8_t *src;        // block b's bytes at src + blocks[b].in_off (the E8E9 copy when the method asks for it)
+  uint8_t *out;              // block b's codes at out + blocks[b].out_off
+  const ZhPreBlock *blocks;
+  uint64_t *out_len;         // per block (counted past out_cap)
+  const uint32_t *starts;    // n_blocks + 1, as in ZhBwtLaunch
+  const uint32_t *key;       // n: the slots of the stored positions in ascending order, then `absent` for the others
+  const uint32_t *val;       // n: the position (as a slot number of the launch) of each key; ascending among equal keys
+  uint64_t *dec[2];          // n each: the decision of a position visited with lit == 0 ([0]) or lit > 0 ([1]); key, val and
+                             // dec[1] are set by zh_launch_pre_lzht
+  uint32_t n_blocks, n;
+  uint32_t level;            // 1 or 2
+  uint32_t min_match;        // args[2]
+  uint32_t bucket;           // 2^args[4] - 1: slots h1 ^ 0 .. h1 ^ bucket are searched
+  uint32_t ht_bits;          // args[5]: a slot has this many bits; the key of a position that is not stored is 1 << ht_bits
+  uint32_t checkbits;        // 12 - args[0]
+  uint32_t shift1;           // (args[5] - 1) / args[2] + 1
+  uint32_t search;           // 0: level 2 with args[2] > 64, all literals (LZBuffer.cs:288)
+  uint32_t rb;               // level 1: args[0] - 4 when args[0] > 4, else 0
+};
+
+// zh_pre_bwt.hip's stable radix sort of the pairs (key[*c], val[*c]) of a launch by the low `bits` bits of the key; the
+// result is in key[*c] / val[*c] again (rank, multi and out are not touched).  *launches grows by the kernels launched.
+extern "C" hipError_t zh_launch_pre_sort(const ZhBwtLaunch *L, hipStream_t stream, uint32_t *launches, uint32_t *c, uint32_t bits);

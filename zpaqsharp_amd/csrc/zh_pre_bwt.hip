@@ -363,3 +363,12 @@ extern "C" hipError_t zh_launch_pre_sufsort(const ZhBwtLaunch *L, hipStream_t st
   if (launches) *launches += R.launches;
   return R.e;
 }
+
+// The radix passes alone (zh_pre_lzht.hip sorts positions by hash slot with them): see zh_pre.h.
+extern "C" hipError_t zh_launch_pre_sort(const ZhBwtLaunch *L, hipStream_t stream, uint32_t *launches, uint32_t *c, uint32_t bits) {
+  if (!L->n) return hipSuccess;
+  Run R{*L, stream};
+  R.sort(*c, bits);
+  if (launches) *launches += R.launches;
+  return R.e;
+}

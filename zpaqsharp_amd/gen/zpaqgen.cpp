@@ -474,6 +474,83 @@ static void pre_lzsa(const uint8_t *d, size_t n, const int *args, std::vector<ui
   }
 }
 
+// ---------------------------------------------------------------------------
+// The reference's parse for a level 1 / 2 method with args[5] - args[0] < 21: LZBuffer's hash-table search with
+// minMatch2 = lookahead = 0 (LZBuffer.cs:285-327), its table update per position passed (:352-367), accept rule, literal
+// flush and end, as tools/methods.lz77_ht ports it.  ht[] is the reference's array: one word per slot, 0 = empty.
+// ---------------------------------------------------------------------------
+static bool uses_ht(const int *args) { return ((args[1] & 3) == 1 || (args[1] & 3) == 2) && args[5] - args[0] < 21; }
+
+template <class Lit, class Match>
+static void ht_parse(const uint8_t *d, size_t n_, const int *args, Lit lit_out, Match match_out) {
+  const uint32_t n = (uint32_t)n_;
+  const int level = args[1] & 3, min_match = args[2];
+  const uint32_t checkbits = (uint32_t)(12 - args[0]), mask = (1u << checkbits) - 1;
+  const uint32_t bucket = (1u << args[4]) - 1, htsize = 1u << args[5];
+  const int shift1 = min_match > 0 ? (args[5] - 1) / min_match + 1 : 1;
+  const uint32_t both = (uint32_t)min_match + 4;                      // minMatchBoth
+  const uint32_t max_match = 49152, max_literal = 4096;
+  std::vector<uint32_t> ht(htsize, 0);
+  uint32_t i = 0, lit = 0, h1 = 0;
+  while (i < n) {
+    uint32_t blen = (uint32_t)min_match - 1, bp = 0;
+    int bscore = 0;
+    if (level == 1 || min_match <= 64) {
+      for (uint32_t k = 0; k <= bucket; ++k) {
+        uint32_t p = ht[h1 ^ k];
+        if (p && i + 3 < n && (p & mask) == (d[i + 3] & mask)) {
+          p >>= checkbits;
+          if (p < i && i + blen <= n && d[p + blen - 1] == d[i + blen - 1]) {
+            uint32_t l = 0;
+            while (i + l < n && l < max_match && d[p + l] == d[i + l]) ++l;
+            const int score = (int)l * 8 - lg32(i - p) - 2 * (lit > 0) - 11;
+            if (score > bscore) { blen = l; bp = p; bscore = score; }
+          }
+        }
+        if (blen >= 128) break;
+      }
+    }
+    const uint32_t off = i - bp;
+    if (off > 0 && bscore > 0 && blen >= (uint32_t)min_match + (level == 2) * ((off >= (1u << 16)) + (off >= (1u << 24)))) {
+      if (lit) lit_out((size_t)(i - lit), (size_t)i);
+      lit = 0;
+      match_out(blen, off);
+    } else {
+      blen = 1;
+      ++lit;
+    }
+    while (blen--) {
+      if (i + both < n) {
+        const uint32_t ih = ((i * 1234547u) >> 19) & bucket;
+        ht[h1 ^ ih] = (i << checkbits) | (d[i + 3] & mask);
+        h1 = (((h1 * 5) << shift1) + (d[i + min_match] + 1) * 123456791u) & (htsize - 1);
+      }
+      ++i;
+    }
+    if (lit >= max_literal) { lit_out((size_t)(i - lit), (size_t)i); lit = 0; }
+  }
+  if (lit) lit_out((size_t)(n - lit), (size_t)n);
+}
+
+// whether ht_parse takes the method (method.check_blocks(ht=True) refuses the rest)
+static bool ht_args_ok(const int *args) {
+  const int level = args[1] & 3;
+  return args[0] >= 0 && args[0] <= 11 && args[3] == 0 && args[6] == 0 && args[2] >= (level == 1 ? 4 : 2) && args[2] <= 255 &&
+         args[4] >= 0 && args[4] <= args[5] && args[4] <= 6 && args[5] <= 30;
+}
+
+static void pre_lzht(const uint8_t *d, size_t n, const int *args, std::vector<uint8_t> &out) {
+  if ((args[1] & 3) == 1) {
+    const int rb = args[0] > 4 ? args[0] - 4 : 0;
+    BitW w(out);
+    ht_parse(d, n, args, [&](size_t a, size_t b) { lz1_lit(w, d, a, b); }, [&](uint32_t ln, uint32_t off) { lz1_match(w, ln, off, rb); });
+    w.flush();
+  } else {
+    const uint32_t m = (uint32_t)args[2];
+    ht_parse(d, n, args, [&](size_t a, size_t b) { lz2_lit(out, d, a, b); }, [&](uint32_t ln, uint32_t off) { lz2_match(out, ln, off, m); });
+  }
+}
+
 // level 3 (bwtrle's input): BWT, end of string coded as 255, its position in the last 4 bytes (LZBuffer.cs:113-115, :228-240)
 static void pre_bwt(const uint8_t *d, size_t n, std::vector<uint8_t> &out) {
   if (n == 0) { out.assign({255, 0, 0, 0, 0}); return; }
@@ -503,10 +580,11 @@ static void pre_bwt(const uint8_t *d, size_t n, std::vector<uint8_t> &out) {
   for (int k = 0; k < 4; ++k) out.push_back((uint8_t)(idx >> (8 * k)));
 }
 
-static void preprocess(const uint8_t *d, size_t n, const int *args, std::vector<uint8_t> &out, bool sa = false) {
+static void preprocess(const uint8_t *d, size_t n, const int *args, std::vector<uint8_t> &out, bool sa = false, bool ht = false) {
   out.clear();
   const int level = args[1] & 3;
   if (sa && uses_sa(args)) pre_lzsa(d, n, args, out);
+  else if (ht && uses_ht(args)) pre_lzht(d, n, args, out);
   else if (level == 1) pre_lz1(d, n, args, out);
   else if (level == 2) pre_lz2(d, n, args, out);
   else if (level == 3) pre_bwt(d, n, out);
@@ -605,10 +683,12 @@ void *zpaqgen_stream_new(const uint8_t *hdr, size_t hdrlen, const uint8_t *pcomp
 
 // What the pre-processor of a method makes of `data` (args[0..8] = the method's numbers, args[1] & 3 = level; the E8E9
 // variants expect the caller to have applied the forward transform).  Returns the size, or -20 with *need set.
-// sa != 0: a level 1 / 2 method with args[5] - args[0] >= 21 gets the reference's suffix-array parse.
+// sa bit 0: a level 1 / 2 method with args[5] - args[0] >= 21 gets the reference's suffix-array parse; sa bit 1: one with
+// args[5] - args[0] < 21 its hash-table parse (ZPAQHIP_E_ARG where tools/methods.lz77_ht does not port it).
 long zpaqgen_preprocess_sa(const int *args, const uint8_t *data, size_t n, uint8_t *out, size_t cap, size_t *need, int sa) {
   std::vector<uint8_t> v;
-  preprocess(data, n, args, v, sa != 0);
+  if ((sa & 2) && uses_ht(args) && !ht_args_ok(args)) return ZPAQHIP_E_ARG;
+  preprocess(data, n, args, v, (sa & 1) != 0, (sa & 2) != 0);
   if (need) *need = v.size();
   if (v.size() > cap) return ZPAQHIP_E_OUTPUT_FULL;
   if (!v.empty()) memcpy(out, v.data(), v.size());
@@ -621,11 +701,12 @@ long zpaqgen_preprocess(const int *args, const uint8_t *data, size_t n, uint8_t 
 
 // Synthetic stream of a METHOD (LibZPAQ.compressBlock's framing): every block's plaintext goes through the method's
 // pre-processor and is then coded with the model of `hdr` — or, for n = 0, stored in length-prefixed chunks
-// (Encoder.cs:39-73) behind the selector and the PCOMP program.  sa as for zpaqgen_preprocess_sa.
+// (Encoder.cs:39-73) behind the selector and the PCOMP program.  sa (bits 0 and 1) as for zpaqgen_preprocess_sa.
 void *zpaqgen_method_stream_new_sa(const uint8_t *hdr, size_t hdrlen, const uint8_t *pcomp, size_t plen, const int *args, int kind,
                                    uint64_t first_block, uint32_t nblocks, size_t block_size, int threads, int sa) {
   Stream *s = new Stream();
   if (!zh::host_tables_ok()) { s->error = "table pins failed"; return s; }
+  if ((sa & 2) && uses_ht(args) && !ht_args_ok(args)) { s->error = "method not taken by the hash-table parse"; return s; }
   const bool stored = hdrlen > 6 && hdr[6] == 0;
   const bool doe8 = args[1] >= 4 && args[1] <= 7;
   std::vector<std::vector<uint8_t>> parts(nblocks);
@@ -646,7 +727,7 @@ void *zpaqgen_method_stream_new_sa(const uint8_t *hdr, size_t hdrlen, const uint
         zh::sha1(plain.data(), block_size, sha);
         const uint8_t *src = plain.data();
         if (doe8) { enc = plain; e8e9_forward(enc.data(), enc.size()); src = enc.data(); }
-        preprocess(src, block_size, args, pre, sa != 0);
+        preprocess(src, block_size, args, pre, (sa & 1) != 0, (sa & 2) != 0);
         char comment[32];
         snprintf(comment, sizeof comment, "%zu", block_size);
         Out o;

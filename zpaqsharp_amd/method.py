@@ -601,28 +601,48 @@ def uses_sa(args: List[int]) -> bool:
     return (args[1] & 3) in (1, 2) and args[5] - args[0] >= 21
 
 
-def check_blocks(args: List[int], sizes, bwt: bool = False, sa: bool = False) -> None:
+def uses_ht(args: List[int]) -> bool:
+    """The level 1 / 2 method strings whose LZBuffer searches a hash table (LZBuffer.cs:153-158, :285-327)."""
+    return (args[1] & 3) in (1, 2) and args[5] - args[0] < 21
+
+
+HT_MAX_BUCKET_BITS = 6                                      # args[4] at most, on the hash-table route: 64 slots per search
+
+
+def check_blocks(args: List[int], sizes, bwt: bool = False, sa: bool = False, ht: bool = False) -> None:
     """ValueError for what the C ABI refuses with ZPAQHIP_E_ARG: level 3 (BWT) unless `bwt` opts in, level 2 with args[2]
     outside 1..64, and a block longer than 2^(args[0] + 20) bytes at level 1 or 2 (its offsets would wrap the PCOMP's M),
     than 2^(args[0] + 20) - 4096 bytes at level 3 (compressBlock's own assertion, LibZPAQ.cs:289; it keeps the n + 5
     bytes inside bwtrle's M), or than 2^31 - 1 bytes.  With `sa` and a method that uses_sa (the suffix-array search):
-    level 1 with args[2] < 4, args[2] or args[6] above 255, args[4] above 30 and a block longer than 2^24 bytes."""
+    level 1 with args[2] < 4, args[2] or args[6] above 255, args[4] above 30 and a block longer than 2^24 bytes.
+    With `ht` and a method that uses_ht (the hash-table search): args[3] != 0 (the second hash order, which compressBlock
+    never writes and whose loop reads past the block's end), args[6] != 0 (look-ahead only acts through that loop), level 1
+    with args[2] < 4, level 2 with args[2] < 2 (from 65 on level 2 does no search: all literals), args[2] > 255,
+    args[0] > 11, args[4] > args[5] or > HT_MAX_BUCKET_BITS, args[5] > 30 and a block longer than 2^24 bytes."""
     level = args[1] & 3
     sa = sa and uses_sa(args)
+    ht = ht and uses_ht(args)
+    if ht:
+        if args[3] != 0 or args[6] != 0:
+            raise ValueError("the hash-table search takes neither a second hash order (args[3]) nor look-ahead (args[6])")
+        if args[2] < (4 if level == 1 else 2) or args[2] > 255:
+            raise ValueError(f"the hash-table search needs a minimum match length of {4 if level == 1 else 2} to 255, not {args[2]}")
+        if args[0] > 11 or args[5] > 30 or args[4] > args[5] or args[4] > HT_MAX_BUCKET_BITS:
+            raise ValueError(f"the hash-table search takes args[0] up to 11, args[5] up to 30 and args[4] up to args[5] and {HT_MAX_BUCKET_BITS}")
     if sa and level == 1 and args[2] < 4:
         raise ValueError(f"level 1 needs a minimum match length of 4 or more, not {args[2]}")
     if sa and (args[2] > 255 or args[6] > 255 or args[4] > 30):
         raise ValueError("the suffix-array search takes args[2] and args[6] up to 255 and args[4] up to 30")
     if level == 3 and not bwt:
         raise ValueError("BWT (level 3) pre-processing is not available on the GPU")
-    if level == 2 and not 1 <= args[2] <= 64:
+    if level == 2 and not 1 <= args[2] <= 64 and not ht:
         raise ValueError(f"level 2 needs a minimum match length of 1 to 64, not {args[2]}")
     if level:
-        limit = min((1 << min(args[0] + 20, 62)) - (4096 if level == 3 else 0), (1 << 31) - 1, (1 << 24) if sa else 1 << 31)
+        limit = min((1 << min(args[0] + 20, 62)) - (4096 if level == 3 else 0), (1 << 31) - 1, (1 << 24) if sa or ht else 1 << 31)
         for i, n in enumerate(sizes):
             if n > limit:
                 raise ValueError(f"block {i} has {n} bytes; at level {level} a block holds at most {limit} "
-                                 f"(2^(args[0] + 20){' - 4096' if level == 3 else ', 2^24 with the suffix-array search' if sa else ''})")
+                                 f"(2^(args[0] + 20){' - 4096' if level == 3 else ', 2^24 with the suffix-array search' if sa else ', 2^24 with the hash-table search' if ht else ''})")
 
 
 def pre_bound(args: List[int], n: int) -> int:

@@ -171,12 +171,14 @@ def stream(model, kind: str = "T", nblocks: int = 1, block_size: int = 1 << 16, 
         L.zpaqgen_stream_free(h)
 
 
-def preprocess(args, data, sa: bool = False) -> bytes:
+def preprocess(args, data, sa: bool = False, ht: bool = False) -> bytes:
     """What the pre-processor of a method (LZBuffer.cs:96-115 formats: level = args[1] & 3) makes of `data`: the fast C++
     twin of tools/methods.preprocess for benchmark-sized inputs (same formats, its own greedy parse).  With `sa`, a level
     1 / 2 method with args[5] - args[0] >= 21 gets the reference's suffix-array parse: the bytes of tools/methods.lz77_sa.
+    With `ht`, one with args[5] - args[0] < 21 gets its hash-table parse: the bytes of tools/methods.lz77_ht.
     As there, `data` is what the parse reads (after E8E9 where the method asks for it)."""
     L = load()
+    sa = int(bool(sa)) | 2 * int(bool(ht))
     d = _u8(data)
     a = (C.c_int * 9)(*[int(x) for x in list(args)[:9]] + [0] * (9 - min(9, len(args))))
     need = C.c_size_t(0)
@@ -185,16 +187,18 @@ def preprocess(args, data, sa: bool = False) -> bytes:
     if rc == -20:
         out = np.empty(need.value, np.uint8)
         rc = L.zpaqgen_preprocess_sa(a, d.ctypes.data if d.size else None, d.size, out.ctypes.data, out.size, C.byref(need), int(sa))
+    if rc == -25:
+        raise ValueError("the hash-table parse does not take this method (method.check_blocks)")
     if rc < 0:
         raise RuntimeError(f"zpaqgen_preprocess failed: {rc}")
     return out[:rc].tobytes()
 
 
 def method_stream(model, args, kind: str = "T", nblocks: int = 1, block_size: int = 1 << 16, first_block: int = 0,
-                  threads: Optional[int] = None, sa: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+                  threads: Optional[int] = None, sa: bool = False, ht: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """`nblocks` distinct blocks written with a METHOD of the reference (LibZPAQ.compressBlock framing): plaintext
     generator `kind`, the method's pre-processor (args as tools/methods.make_config returns them), then the model of
-    `model` — stored chunks for n = 0.  `sa` as for preprocess.  Returns (stream, block offsets)."""
+    `model` — stored chunks for n = 0.  `sa`, `ht` as for preprocess.  Returns (stream, block offsets)."""
     L = load()
     hdr, pc = _u8(model.header), _u8(model.pcomp or b"")
     a = (C.c_int * 9)(*[int(x) for x in list(args)[:9]] + [0] * (9 - min(9, len(args))))
@@ -204,7 +208,7 @@ def method_stream(model, args, kind: str = "T", nblocks: int = 1, block_size: in
     if threads is None:
         threads = min(32, os.cpu_count() or 1)
     h = L.zpaqgen_method_stream_new_sa(hdr.ctypes.data, hdr.size, pc.ctypes.data if pc.size else None, pc.size, a, KINDS[kind],
-                                       first_block, nblocks, block_size, threads, int(sa))
+                                       first_block, nblocks, block_size, threads, int(bool(sa)) | 2 * int(bool(ht)))
     try:
         err = L.zpaqgen_stream_error(h)
         if err:

@@ -2,7 +2,7 @@
 tools.methods.preprocess(..., ht=True) byte for byte on the catalogue of tests/lzht_cases.py, at levels 1 and 2, with and
 without E8E9; Context.compress_method(ht=True) writes the streams of tools.methods.compress_block(ht=True), which the GPU
 decoder and the oracle read back; without the keyword nothing changes; the numeric levels take the keyword; the C ABI's
-capacity contract."""
+capacity contract; both searches over several batches of one call."""
 import ctypes as C
 
 import numpy as np
@@ -87,6 +87,15 @@ def test_the_keyword_has_no_effect_on_other_methods(ctx):
     offs = np.array([0, d.size], np.uint64)
     out, n, err = np.empty(64, np.uint8), C.c_size_t(0), _lib.Err()
     assert _lib.load().zpaqhip_lzht_blocks(ctx._h, a, d.ctypes.data, offs.ctypes.data, 1, out.ctypes.data, 64, C.byref(n), None, C.byref(err)) == -25
+
+
+@pytest.mark.parametrize("m", ["x4,6,12,0,7,25,1", cases.L1])        # the suffix-array search behind E8E9, the hash-table search
+def test_batches_of_one_call_reuse_the_sort_arena(ctx, m):
+    # batches of 20 000 + 0, 1 + 4 097 and 777 slots: the arena is laid out anew for each
+    blocks = [cases.text(20000, 9), b"", b"q", cases.x86(4097, 8), cases.text(777, 7)]
+    got = ctx.compress_method(m, blocks, sa=True, ht=True, batch_blocks=2)
+    assert got == ctx.compress_method(m, blocks, sa=True, ht=True)
+    assert got == b"".join(methods.compress_block(m, b, sa=True, ht=True) for b in blocks)
 
 
 @pytest.mark.parametrize("level", ["1", "1,128,0", "2,40,0", "3,30,0", "2,10,0", "3,6,0", "4,4,0"])

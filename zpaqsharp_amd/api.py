@@ -224,6 +224,25 @@ class Context:
         flags = (1 if sha1 else 0) | (2 if tag else 0)
         return self._compress(m.header, m.pcomp or b"", coded, orig, filenames, flags, kernel, batch_blocks, slot_bytes)[0]
 
+    def _pre_blocks(self, fn, first, plain, cap: int, retry: bool = False) -> List[bytes]:
+        """A zpaqhip_*_blocks entry point `fn` (`first` is its argument after the context: the method's args or the E8E9 flag) on
+        a list of blocks: their pre-processed bytes.  `retry`: once more when `cap` was too small (ZPAQHIP_E_OUTPUT_FULL
+        tells the size)."""
+        buf, offs = _cat(plain)
+        oo = np.zeros(len(plain) + 1, np.uint64)
+        for _ in range(2 if retry else 1):
+            out = np.empty(max(1, cap), np.uint8)
+            err, got = Err(), C.c_size_t(0)
+            rc = fn(self._h, first, buf.ctypes.data, offs.ctypes.data, len(plain), out.ctypes.data, cap, C.byref(got), oo.ctypes.data,
+                    C.byref(err))
+            if retry and rc == -20 and got.value > cap:
+                cap = got.value
+                continue
+            if rc:
+                _raise(err, rc)
+            return [out[int(oo[i]):int(oo[i + 1])].tobytes() for i in range(len(plain))]
+        _raise(err, rc)
+
     def preprocess_blocks(self, method: str, blocks) -> List[bytes]:
         """What LibZPAQ.compressBlock feeds the coder for `method` (LibZPAQ.cs:296-311: E8E9, LZBuffer levels 1 / 2), computed
         on the GPU for each block: equal to tools.methods.preprocess.  Useful on its own as `pre=` of compress_blocks."""
@@ -231,22 +250,8 @@ class Context:
         args = mth.parse_args(method)[1]
         plain = [_as_u8(b) for b in blocks]
         mth.check_blocks(args, [p.size for p in plain])
-        buf, offs = _cat(plain)
-        a = (C.c_int32 * 9)(*args)
-        cap = sum(mth.pre_bound(args, p.size) for p in plain)
-        oo = np.zeros(len(plain) + 1, np.uint64)
-        for _ in range(2):
-            out = np.empty(max(1, cap), np.uint8)
-            err, got = Err(), C.c_size_t(0)
-            rc = self._L.zpaqhip_preprocess_blocks(self._h, a, buf.ctypes.data, offs.ctypes.data, len(plain), out.ctypes.data, cap,
-                                                   C.byref(got), oo.ctypes.data, C.byref(err))
-            if rc == -20 and got.value > cap:
-                cap = got.value
-                continue
-            if rc:
-                _raise(err, rc)
-            return [out[int(oo[i]):int(oo[i + 1])].tobytes() for i in range(len(plain))]
-        _raise(err, rc)
+        return self._pre_blocks(self._L.zpaqhip_preprocess_blocks, (C.c_int32 * 9)(*args), plain,
+                                sum(mth.pre_bound(args, p.size) for p in plain), retry=True)
 
     def bwt_blocks(self, blocks, e8e9: bool = False) -> List[bytes]:
         """LZBuffer's level 3 (LZBuffer.cs:228-240) of each block on the GPU (zpaqhip_bwt_blocks): the Burrows-Wheeler
@@ -256,16 +261,7 @@ class Context:
         for i, p in enumerate(plain):
             if p.size > (1 << 31) - 1:
                 raise ValueError(f"block {i} has {p.size} bytes; a BWT block holds at most 2^31 - 1")
-        buf, offs = _cat(plain)
-        cap = sum(p.size + 5 for p in plain)
-        oo = np.zeros(len(plain) + 1, np.uint64)
-        out = np.empty(max(1, cap), np.uint8)
-        err, got = Err(), C.c_size_t(0)
-        rc = self._L.zpaqhip_bwt_blocks(self._h, int(bool(e8e9)), buf.ctypes.data, offs.ctypes.data, len(plain), out.ctypes.data, cap,
-                                        C.byref(got), oo.ctypes.data, C.byref(err))
-        if rc:
-            _raise(err, rc)
-        return [out[int(oo[i]):int(oo[i + 1])].tobytes() for i in range(len(plain))]
+        return self._pre_blocks(self._L.zpaqhip_bwt_blocks, int(bool(e8e9)), plain, sum(p.size + 5 for p in plain))
 
     def lzsa_blocks(self, method: str, blocks) -> List[bytes]:
         """LZBuffer's codes of each block for a level 1 / 2 method with args[5] - args[0] >= 21, from the reference's
@@ -277,17 +273,8 @@ class Context:
             raise ValueError("not a level 1 / 2 method with args[5] - args[0] >= 21")
         plain = [_as_u8(b) for b in blocks]
         mth.check_blocks(args, [p.size for p in plain], sa=True)
-        buf, offs = _cat(plain)
-        a = (C.c_int32 * 9)(*args)
-        cap = sum(mth.pre_bound(args, p.size) for p in plain)
-        oo = np.zeros(len(plain) + 1, np.uint64)
-        out = np.empty(max(1, cap), np.uint8)
-        err, got = Err(), C.c_size_t(0)
-        rc = self._L.zpaqhip_lzsa_blocks(self._h, a, buf.ctypes.data, offs.ctypes.data, len(plain), out.ctypes.data, cap,
-                                         C.byref(got), oo.ctypes.data, C.byref(err))
-        if rc:
-            _raise(err, rc)
-        return [out[int(oo[i]):int(oo[i + 1])].tobytes() for i in range(len(plain))]
+        return self._pre_blocks(self._L.zpaqhip_lzsa_blocks, (C.c_int32 * 9)(*args), plain,
+                                sum(mth.pre_bound(args, p.size) for p in plain))
 
     def lzht_blocks(self, method: str, blocks) -> List[bytes]:
         """LZBuffer's codes of each block for a level 1 / 2 method with args[5] - args[0] < 21, from the reference's
@@ -301,17 +288,8 @@ class Context:
             raise ValueError("not a level 1 / 2 method with args[5] - args[0] < 21")
         plain = [_as_u8(b) for b in blocks]
         mth.check_blocks(args, [p.size for p in plain], ht=True)
-        buf, offs = _cat(plain)
-        a = (C.c_int32 * 9)(*args)
-        cap = sum(mth.pre_bound(args, p.size) for p in plain)
-        oo = np.zeros(len(plain) + 1, np.uint64)
-        out = np.empty(max(1, cap), np.uint8)
-        err, got = Err(), C.c_size_t(0)
-        rc = self._L.zpaqhip_lzht_blocks(self._h, a, buf.ctypes.data, offs.ctypes.data, len(plain), out.ctypes.data, cap,
-                                         C.byref(got), oo.ctypes.data, C.byref(err))
-        if rc:
-            _raise(err, rc)
-        return [out[int(oo[i]):int(oo[i + 1])].tobytes() for i in range(len(plain))]
+        return self._pre_blocks(self._L.zpaqhip_lzht_blocks, (C.c_int32 * 9)(*args), plain,
+                                sum(mth.pre_bound(args, p.size) for p in plain))
 
     def compress_method(self, method: str, blocks, *, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 0,
                         batch_blocks: int = 0, slot_bytes: int = 0, bwt: bool = False, sa: bool = False, ht: bool = False) -> bytes:

@@ -71,14 +71,27 @@ int sha1_segments(const CtxView &v, const uint8_t *d_base, const std::vector<uin
 int finish_call(const CtxView &v, zpaqhip_stats st, uint64_t pos, size_t n_blocks, uint64_t *off, size_t out_cap, size_t *out_len,
                 zpaqhip_err *err);
 
+// How a method's blocks are pre-processed (zh_pre.cpp): what args[1] and the caller's opt-ins select
+enum class Route : uint32_t {
+  Copy,                                   // level 0: the plaintext is the coded data
+  E8E9,                                   // level 0 with E8E9: the transform is the coded data
+  Greedy,                                 // levels 1 / 2, the parse of tools/methods._matches (zh_pre_lz.hip)
+  Bwt,                                    // level 3 (zh_pre_bwt.hip)
+  Sa,                                     // levels 1 / 2, the reference's suffix-array search (tools/methods.lz77_sa, zh_pre_lzsa.hip)
+  Ht,                                     // levels 1 / 2, the reference's hash-table search (tools/methods.lz77_ht, zh_pre_lzht.hip)
+};
+
 // the method's numbers (tools/methods.preprocess / lz77_level1 / lz77_level2)
 struct Method {
-  uint32_t level = 0, doe8 = 0, k = 0, m = 0, rb = 0, max_match = 0, max_off = 0;
+  Route route = Route::Copy;
+  uint32_t level = 0;                     // args[1] & 3: the format of the codes
+  uint32_t doe8 = 0;                      // 4 <= args[1] <= 7; from Greedy on the route reads the E8E9 copy of a block
+  uint32_t k = 0, m = 0, rb = 0, max_match = 0, max_off = 0;        // k, max_match, max_off: Greedy only
   uint64_t max_block = ~0ull;             // levels 1 / 2: 2^(args[0] + 20), the PCOMP's M; level 3: 4096 less (LibZPAQ.cs:289)
-  // levels 1 / 2 with the reference's suffix-array search (tools/methods.lz77_sa, zh_pre_lzsa.hip): k, max_match, max_off unused
-  uint32_t sa = 0, bucket = 0, lookahead = 0, win_bits = 0;
-  // levels 1 / 2 with the reference's hash-table search (tools/methods.lz77_ht, zh_pre_lzht.hip): m and bucket as above
-  uint32_t ht = 0, ht_bits = 0, checkbits = 0, shift1 = 0, search = 0;
+  uint32_t bucket = 0, lookahead = 0, win_bits = 0;                 // Sa (bucket: Ht too)
+  uint32_t ht_bits = 0, checkbits = 0, shift1 = 0, search = 0;      // Ht
+  bool slots() const { return route == Route::Bwt || route == Route::Sa || route == Route::Ht; }   // routes in the sort's slot space
+  bool e8_copy() const { return doe8 && route != Route::E8E9; }
 };
 
 struct PreBatch {                         // what DevPre::run leaves of a batch [b0, b1)
@@ -103,7 +116,9 @@ class DevPre {
   Method M_;
   const uint8_t *in_;
   const uint64_t *in_off_;
-  DevMem plain_, e8_, tab_, chain_, prev_, dec_, len_, desc_, pref_;
+  DevMem plain_, e8_, len_, desc_, pref_;
+  DevMem tab_, chain_, prev_;             // Greedy: ZhPreLaunch's table, chain and prev
+  DevMem starts_, arena_;                 // slot routes: the slot starts of every launch; zh_pre.cpp's SortArena
 };
 
 // The batch loop.  Without `pre`, block i's coded bytes are in[in_off[i], in_off[i+1]) and `orig`, when given, is what the

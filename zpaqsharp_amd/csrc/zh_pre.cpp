@@ -1,8 +1,10 @@
-// zh_pre.cpp — LibZPAQ.compressBlock for a method (LibZPAQ.cs:296-323): the pre-processing of levels 0, 1 and 2 and, where
-// the caller asks for it, 3 (BWT) and the reference's suffix-array and hash-table parses of levels 1 / 2 (zh_pre_lzsa.hip,
-// zh_pre_lzht.hip), with or without E8E9, on the GPU (zh_pre_lz.hip, zh_pre_bwt.hip).  DevPre is that stage;
-// compress_impl (zh_compress.cpp) runs it in place of its host copy and then codes the bytes where the kernels left them
-// (n >= 1 headers) or stores them (n = 0 headers).  zpaqhip_preprocess_blocks / zpaqhip_bwt_blocks return them as they are.
+// zh_pre.cpp — LibZPAQ.compressBlock for a method (LibZPAQ.cs:296-323): the pre-processing of a method's blocks on the GPU,
+// by one of the routes of zh_compress.h's Route.  parse_method turns args and the caller's opt-ins into a Method (the route
+// and its numbers); DevPre is the stage: compress_impl (zh_compress.cpp) runs it in place of its host copy and then codes
+// the bytes where the kernels left them (n >= 1 headers) or stores them (n = 0 headers); zpaqhip_preprocess_blocks,
+// zpaqhip_bwt_blocks, zpaqhip_lzsa_blocks and zpaqhip_lzht_blocks return them as they are.  DevPre::run is a sequence:
+// describe the batch, upload, prefix / E8E9, the route's launches, read the lengths back.  The device arrays of the sort
+// that the Bwt, Sa and Ht routes share are laid out by SortArena below, and nowhere else.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -17,13 +19,15 @@
 #include "zh_ctx_view.h"
 #include "zh_pre.h"
 
-extern "C" hipError_t zh_launch_pre_prefix(const ZhPreLaunch *L, const uint8_t *prefix, uint32_t np, hipStream_t stream);
-extern "C" hipError_t zh_launch_pre_e8e9(const ZhPreLaunch *L, hipStream_t stream);
-extern "C" hipError_t zh_launch_pre_lz(const ZhPreLaunch *L, uint64_t max_n, hipStream_t stream);
+// every launcher adds the kernels it launched to *launches
+extern "C" hipError_t zh_launch_pre_prefix(const ZhPreLaunch *L, const uint8_t *prefix, uint32_t np, hipStream_t stream, uint32_t *launches);
+extern "C" hipError_t zh_launch_pre_e8e9(const ZhPreLaunch *L, hipStream_t stream, uint32_t *launches);
+extern "C" hipError_t zh_launch_pre_lz(const ZhPreLaunch *L, uint64_t max_n, hipStream_t stream, uint32_t *launches);
 extern "C" hipError_t zh_launch_pre_bwt(const ZhBwtLaunch *L, hipStream_t stream, uint32_t *launches, uint32_t *rounds);
 extern "C" hipError_t zh_launch_pre_sufsort(const ZhBwtLaunch *L, hipStream_t stream, uint32_t *launches, uint32_t *c);
 extern "C" hipError_t zh_launch_pre_lzsa(const ZhLzsaLaunch *L, hipStream_t stream, uint32_t *launches);
-extern "C" hipError_t zh_launch_pre_lzht(const ZhLzhtLaunch *L, const ZhBwtLaunch *W, hipStream_t stream, uint32_t *launches);
+extern "C" hipError_t zh_launch_pre_lzht(const ZhLzhtLaunch *L, const ZhBwtLaunch *W, uint64_t *const words[2], hipStream_t stream,
+                                         uint32_t *launches);
 extern "C" hipError_t zh_launch_gap_hist(const ZhGapLaunch *L, uint32_t n_blocks, uint64_t max_n, hipStream_t stream);
 
 using namespace zh;
@@ -34,30 +38,54 @@ constexpr uint32_t kFlagBwt = 4;          // zpaqhip_compress_opts.flags: accept
 constexpr uint32_t kFlagSa = 8;           // ... the reference's suffix-array search where the method selects it
 constexpr uint32_t kFlagHt = 16;          // ... the reference's hash-table search where the method selects it
 
-int parse_method(const int32_t *args, bool bwt, bool sa, bool ht, Method &M, zpaqhip_err *err) {
-  if (!args) { set_err(err, ZPAQHIP_E_ARG, -1, -1); return ZPAQHIP_E_ARG; }
-  M.level = (uint32_t)args[1] & 3;
-  M.doe8 = args[1] >= 4 && args[1] <= 7;
-  ht = ht && (M.level == 1 || M.level == 2) && args[5] - args[0] < 21;       // LZBuffer.cs:153-158
-  if (ht) {
-    const char *why = nullptr;
-    if (args[0] < 0 || args[0] > 11) why = "the hash-table search takes args[0] up to 11";
-    else if (args[3] != 0 || args[6] != 0) why = "the hash-table search takes neither a second hash order (args[3]) nor look-ahead (args[6])";
-    else if (args[2] < (M.level == 1 ? 4 : 2) || args[2] > 255)             // LZBuffer.cs:198-199, :317
-      why = "the hash-table search needs a minimum match length (args[2]) of 4 (level 1) or 2 (level 2) to 255";
-    else if (args[5] < 0 || args[5] > 30 || args[4] < 0 || args[4] > args[5] || args[4] > (int32_t)ZH_LZHT_MAX_BUCKET_BITS)
-      why = "the hash-table search takes args[5] up to 30 and args[4] up to args[5] and 6";
-    if (why) { set_err(err, ZPAQHIP_E_ARG, -1, -1, why); return ZPAQHIP_E_ARG; }
-  }
-  if (M.level == 3 && !bwt) {
-    set_err(err, ZPAQHIP_E_ARG, -1, -1, "BWT (level 3) pre-processing is not available on the GPU");
-    return ZPAQHIP_E_ARG;
-  }
-  if (M.level == 2 && (args[2] < 1 || args[2] > 64) && !ht) {
-    set_err(err, ZPAQHIP_E_ARG, -1, -1, "level 2 needs a minimum match length of 1 to 64 (args[2])");
-    return ZPAQHIP_E_ARG;
-  }
-  if (M.level && (args[0] < 0 || args[2] < 0)) { set_err(err, ZPAQHIP_E_ARG, -1, -1); return ZPAQHIP_E_ARG; }
+int refuse(zpaqhip_err *err, const char *why = nullptr) {
+  set_err(err, ZPAQHIP_E_ARG, -1, -1, why);
+  return ZPAQHIP_E_ARG;
+}
+
+// ---- the method: its route, the route's rules, its numbers ------------------------------------------------------------
+Route route_of(const int32_t *args, uint32_t flags) {
+  const uint32_t level = (uint32_t)args[1] & 3;
+  if (level == 0) return args[1] >= 4 && args[1] <= 7 ? Route::E8E9 : Route::Copy;
+  if (level == 3) return Route::Bwt;
+  if (!(flags & (kFlagSa | kFlagHt))) return Route::Greedy;
+  if (args[5] - args[0] >= 21) return flags & kFlagSa ? Route::Sa : Route::Greedy;      // LZBuffer.cs:153-158
+  return flags & kFlagHt ? Route::Ht : Route::Greedy;
+}
+
+int check_bwt(const int32_t *args, uint32_t flags, zpaqhip_err *err) {
+  if (!(flags & kFlagBwt)) return refuse(err, "BWT (level 3) pre-processing is not available on the GPU");
+  if (args[0] < 0 || args[2] < 0) return refuse(err);
+  return ZPAQHIP_OK;
+}
+
+int check_greedy(const int32_t *args, uint32_t level, zpaqhip_err *err) {
+  if (level == 2 && (args[2] < 1 || args[2] > 64)) return refuse(err, "level 2 needs a minimum match length of 1 to 64 (args[2])");
+  if (args[0] < 0 || args[2] < 0) return refuse(err);
+  return ZPAQHIP_OK;
+}
+
+int check_sa(const int32_t *args, uint32_t level, zpaqhip_err *err) {             // LZBuffer.cs:205
+  if (const int rc = check_greedy(args, level, err)) return rc;                  // the rules of the greedy route hold here too
+  if (level == 1 && args[2] < 4)                                                 // LZBuffer.cs:198-199
+    return refuse(err, "level 1 needs a minimum match length of 4 or more (args[2])");
+  if (args[3] < 0 || args[4] < 0 || args[4] > 30 || args[6] < 0 || args[6] > 255 || args[2] > 255)
+    return refuse(err, "the suffix-array search takes args[2] and args[6] up to 255 and args[4] up to 30");
+  return ZPAQHIP_OK;
+}
+
+int check_ht(const int32_t *args, uint32_t level, zpaqhip_err *err) {
+  if (args[0] < 0 || args[0] > 11) return refuse(err, "the hash-table search takes args[0] up to 11");
+  if (args[3] != 0 || args[6] != 0)
+    return refuse(err, "the hash-table search takes neither a second hash order (args[3]) nor look-ahead (args[6])");
+  if (args[2] < (level == 1 ? 4 : 2) || args[2] > 255)                           // LZBuffer.cs:198-199, :317
+    return refuse(err, "the hash-table search needs a minimum match length (args[2]) of 4 (level 1) or 2 (level 2) to 255");
+  if (args[5] < 0 || args[5] > 30 || args[4] < 0 || args[4] > args[5] || args[4] > (int32_t)ZH_LZHT_MAX_BUCKET_BITS)
+    return refuse(err, "the hash-table search takes args[5] up to 30 and args[4] up to args[5] and 6");
+  return ZPAQHIP_OK;
+}
+
+void fill_numbers(const int32_t *args, Method &M) {
   if (M.level == 1) {
     M.k = (uint32_t)std::max(4, args[2]);
     M.rb = args[0] > 4 ? (uint32_t)(args[0] - 4) : 0;
@@ -70,33 +98,36 @@ int parse_method(const int32_t *args, bool bwt, bool sa, bool ht, Method &M, zpa
     M.max_off = (1u << 24) - 1;
   }
   if (M.level) M.max_block = std::min<uint64_t>((1ull << std::min(args[0] + 20, 62)) - (M.level == 3 ? 4096 : 0), (1ull << 31) - 1);
-  if (sa && (M.level == 1 || M.level == 2) && args[5] - args[0] >= 21) {    // LZBuffer.cs:153-158, :205
-    if (M.level == 1 && args[2] < 4) {                                        // LZBuffer.cs:198-199
-      set_err(err, ZPAQHIP_E_ARG, -1, -1, "level 1 needs a minimum match length of 4 or more (args[2])");
-      return ZPAQHIP_E_ARG;
-    }
-    if (args[3] < 0 || args[4] < 0 || args[4] > 30 || args[6] < 0 || args[6] > 255 || args[2] > 255) {
-      set_err(err, ZPAQHIP_E_ARG, -1, -1, "the suffix-array search takes args[2] and args[6] up to 255 and args[4] up to 30");
-      return ZPAQHIP_E_ARG;
-    }
-    M.sa = 1;
-    M.m = (uint32_t)args[2];
-    M.bucket = (1u << args[4]) - 1;
+  if (M.route != Route::Sa && M.route != Route::Ht) return;
+  M.m = (uint32_t)args[2];
+  M.bucket = (1u << args[4]) - 1;
+  M.max_block = std::min<uint64_t>(M.max_block, 1ull << 24);                    // offsets of 2^24 and more are not written
+  if (M.route == Route::Sa) {
     M.lookahead = (uint32_t)args[6];
     M.win_bits = (uint32_t)std::min(17 + args[0], 31);
-    M.max_block = std::min<uint64_t>(M.max_block, 1ull << 24);                // offsets of 2^24 and more are not written
-  }
-  if (ht) {
-    M.ht = 1;
-    M.m = (uint32_t)args[2];
-    M.bucket = (1u << args[4]) - 1;
+  } else {
     M.ht_bits = (uint32_t)args[5];
     M.checkbits = (uint32_t)(12 - args[0]);
-    M.shift1 = (uint32_t)((args[5] - 1) / args[2] + 1);                       // C division: args[5] = 0 gives 1
-    M.search = M.level == 1 || args[2] <= 64;                                 // LZBuffer.cs:288
-    M.max_block = std::min<uint64_t>(M.max_block, 1ull << 24);
+    M.shift1 = (uint32_t)((args[5] - 1) / args[2] + 1);                         // C division: args[5] = 0 gives 1
+    M.search = M.level == 1 || args[2] <= 64;                                   // LZBuffer.cs:288
   }
-  return ZPAQHIP_OK;
+}
+
+int parse_method(const int32_t *args, uint32_t flags, Method &M, zpaqhip_err *err) {
+  if (!args) return refuse(err);
+  M.level = (uint32_t)args[1] & 3;
+  M.doe8 = args[1] >= 4 && args[1] <= 7;
+  M.route = route_of(args, flags);
+  int rc = ZPAQHIP_OK;
+  switch (M.route) {
+    case Route::Copy: case Route::E8E9: break;
+    case Route::Greedy: rc = check_greedy(args, M.level, err); break;
+    case Route::Bwt: rc = check_bwt(args, flags, err); break;
+    case Route::Sa: rc = check_sa(args, M.level, err); break;
+    case Route::Ht: rc = check_ht(args, M.level, err); break;
+  }
+  if (!rc) fill_numbers(args, M);
+  return rc;
 }
 
 // pre-processed bytes at most: a literal run of L costs 8L + 2 lg(L) + 1 <= 11L bits and a match of l >= 4 at most 8l bits
@@ -110,40 +141,136 @@ uint64_t pre_bound(const Method &M, uint64_t n) {
   return n;
 }
 
-uint32_t tab_bits(uint64_t n) {           // at least two table entries per position
+uint32_t tab_bits(uint64_t n) {           // Greedy: at least two table entries per position
   uint32_t b = 10;
   while (b < 30 && (1ull << b) < 2 * n) ++b;
   return b;
 }
 
-// zh_pre_bwt.hip's buffers for n slots: two key and two position arrays and the ranks (20 bytes per slot), the digit
-// counts of the radix tiles (1 / 4 byte per slot) and the partial results of the scans
-constexpr uint64_t kBwtSlots = (1ull << 31) - 1;
-uint64_t bwt_tiles(uint64_t n) { return (n + 4095) / 4096; }
-uint64_t bwt_sums(uint64_t n) { return 2 * ((std::max<uint64_t>(n, 256 * bwt_tiles(n)) + 4095) / 4096) + 2; }
-uint64_t bwt_bytes(uint64_t n) { return 20 * n + 1024 * bwt_tiles(n) + 4 * bwt_sums(n) + 5 * 256; }
+// ---- the sort's arena ---------------------------------------------------------------------------------------------------
+// The device arrays of zh_pre_bwt.hip's sort over a slot space of n slots, in one allocation, in this order:
+//   key[0], val[0], key[1], val[1]   4n bytes each: the pairs of the radix sort, ping and pong
+//   dec                              8n bytes, Sa and Ht only: the decisions of positions reached with lit == 0
+//   rank                             4n bytes
+//   counts                           1024 bytes per radix tile of 4096 pairs: the digit counts
+//   sums                             4 bytes per partial result of a scan
+//   multi                            4 bytes
+// Every offset is a multiple of 4, and those of the pairs and of dec multiples of 8.
+struct SortArena {
+  uint64_t n, tiles, nsums;
+  bool has_dec;
+  uint8_t *base = nullptr;                // set once the arena is allocated
+  SortArena(uint64_t n, bool has_dec)
+      : n(n), tiles((n + 4095) / 4096), nsums(2 * ((std::max<uint64_t>(n, 256 * tiles) + 4095) / 4096) + 2), has_dec(has_dec) {}
+  uint64_t pair_at(uint32_t q) const { return 8 * n * q; }
+  uint64_t dec_at() const { return 16 * n; }
+  uint64_t rank_at() const { return dec_at() + (has_dec ? 8 * n : 0); }
+  uint64_t counts_at() const { return rank_at() + 4 * n; }
+  uint64_t sums_at() const { return counts_at() + 1024 * tiles; }
+  uint64_t multi_at() const { return sums_at() + 4 * nsums; }
+  uint64_t bytes() const { return multi_at() + 4; }
+  // what DevPre::scratch plans with: DevMem hands out at least 256 bytes per buffer, and the estimate has always carried 4 more
+  uint64_t budget() const { return bytes() + 5 * 256 + 4; }
+  template <class T> T *at(uint64_t off) const { return reinterpret_cast<T *>(base + off); }
+  uint64_t *dec() const { return at<uint64_t>(dec_at()); }
+  // key[q] and val[q] are adjacent, so a pair the sort is done with is one array of n 64-bit words: the routes that search
+  // a finished sort keep the decisions of positions reached with lit > 0 in the pair the sort did not end in
+  uint64_t *pair_words(uint32_t q) const { return at<uint64_t>(pair_at(q)); }
+  void fill(ZhBwtLaunch &W) const {
+    for (uint32_t q = 0; q < 2; ++q) {
+      W.key[q] = at<uint32_t>(pair_at(q));
+      W.val[q] = W.key[q] + n;
+    }
+    W.rank = at<uint32_t>(rank_at());
+    W.counts = at<uint32_t>(counts_at());
+    W.sums = at<uint32_t>(sums_at());
+    W.multi = at<uint32_t>(multi_at());
+  }
+};
+
+// ---- the launches of a batch in the slot space --------------------------------------------------------------------------
+constexpr uint64_t kMaxSlots = (1ull << 31) - 1;
+
+struct LaunchCuts {
+  std::vector<size_t> cut;                // first block of each launch, then the number of blocks
+  std::vector<uint32_t> starts;           // ZhSlotSpace::starts of launch u at starts[cut[u] + u ..]
+  uint64_t max_slots = 0;                 // of the largest launch
+};
+
+// Cuts the blocks of a batch into launches of at most kMaxSlots slots and sets every block's scr_off, its first slot
+LaunchCuts cut_launches(std::vector<ZhPreBlock> &desc) {
+  LaunchCuts C;
+  C.cut.push_back(0);
+  uint64_t scr = 0;
+  for (size_t j = 0; j < desc.size(); ++j) {
+    if (scr + desc[j].n > kMaxSlots) {    // the next launch starts here
+      C.cut.push_back(j);
+      C.max_slots = std::max(C.max_slots, scr);
+      scr = 0;
+    }
+    desc[j].scr_off = scr;
+    scr += desc[j].n;
+  }
+  C.max_slots = std::max(C.max_slots, scr);
+  C.cut.push_back(desc.size());
+  for (size_t u = 0; u + 1 < C.cut.size(); ++u) {
+    for (size_t j = C.cut[u]; j < C.cut[u + 1]; ++j) C.starts.push_back((uint32_t)desc[j].scr_off);
+    C.starts.push_back((uint32_t)(desc[C.cut[u + 1] - 1].scr_off + desc[C.cut[u + 1] - 1].n));
+  }
+  return C;
+}
+
+// ---- the routes in the slot space: one launch W each --------------------------------------------------------------------
+int run_bwt(const ZhBwtLaunch &W, const CtxView &v, uint32_t &launches, zpaqhip_err *err) {
+  uint32_t rounds = 0;                    // the launcher reports its doubling rounds; nothing here uses them
+  HIPCHK(zh_launch_pre_bwt(&W, v.stream, &launches, &rounds));
+  return ZPAQHIP_OK;
+}
+
+int run_sa(const Method &M, const ZhBwtLaunch &W, const SortArena &A, const CtxView &v, uint32_t &launches, zpaqhip_err *err) {
+  uint32_t c = 0;
+  HIPCHK(zh_launch_pre_sufsort(&W, v.stream, &launches, &c));
+  ZhLzsaLaunch S{};
+  static_cast<ZhSlotSpace &>(S) = W;
+  S.sa = W.val[c];
+  S.rank = W.rank;
+  S.lcp = W.key[c];                       // the sort is done with its keys and with the other pair of arrays
+  S.dec[0] = A.dec();
+  S.dec[1] = A.pair_words(c ^ 1);
+  S.level = M.level; S.min_match = M.m; S.bucket = M.bucket; S.lookahead = M.lookahead; S.win_bits = M.win_bits; S.rb = M.rb;
+  HIPCHK(zh_launch_pre_lzsa(&S, v.stream, &launches));
+  return ZPAQHIP_OK;
+}
+
+int run_ht(const Method &M, const ZhBwtLaunch &W, const SortArena &A, const CtxView &v, uint32_t &launches, zpaqhip_err *err) {
+  ZhLzhtLaunch H{};
+  static_cast<ZhSlotSpace &>(H) = W;
+  H.dec[0] = A.dec();
+  H.level = M.level; H.min_match = M.m; H.bucket = M.bucket; H.ht_bits = M.ht_bits; H.checkbits = M.checkbits;
+  H.shift1 = M.shift1; H.search = M.search; H.rb = M.rb;
+  uint64_t *const words[2] = {A.pair_words(0), A.pair_words(1)};
+  HIPCHK(zh_launch_pre_lzht(&H, &W, words, v.stream, &launches));
+  return ZPAQHIP_OK;
+}
 
 }  // namespace
 
 uint64_t zh::DevPre::bound(size_t i) const { return pre_bound(M_, n_of(i)); }
 
 uint64_t zh::DevPre::scratch(size_t i) const {
-  const uint64_t n = n_of(i);
-  uint64_t c = n + 64;
-  if (M_.level == 3) return c + (M_.doe8 ? n : 0) + bwt_bytes(n) + 8;
-  if (M_.sa || M_.ht) return c + (M_.doe8 ? n : 0) + bwt_bytes(n) + 8 * n + 8;         // the sort's arrays and one decision array
-  if (M_.level) c += (M_.doe8 ? n : 0) + 8 * n + (4ull << tab_bits(n));
+  const uint64_t n = n_of(i), c = n + 64 + (M_.e8_copy() ? n : 0);
+  if (M_.slots()) return c + SortArena(n, M_.route != Route::Bwt).budget();
+  if (M_.route == Route::Greedy) return c + 8 * n + (4ull << tab_bits(n));
   return c;
 }
 
 int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, const std::vector<uint64_t> &off,
                     const std::vector<uint8_t> &prefix, PreBatch &r, zpaqhip_err *err) {
+  // the batch: its blocks and, in the slot space, the launches they are cut into
   const size_t nb = b1 - b0;
   const uint64_t np = prefix.size(), base = in_off_[b0], plain = in_off_[b1] - base;
   std::vector<ZhPreBlock> desc(nb);
-  uint64_t scr = 0, tab = 0, max_n = 0, max_scr = 0;
-  const bool slots = M_.level == 3 || M_.sa || M_.ht;      // the sort's slot space (BWT, suffix-array and hash-table search)
-  std::vector<size_t> cut(1, 0);        // slots: first block of each launch (at most 2^31 - 1 slots per launch)
+  uint64_t scr = 0, tab = 0, max_n = 0;
   for (size_t j = 0; j < nb; ++j) {
     ZhPreBlock &d = desc[j];
     memset(&d, 0, sizeof d);
@@ -151,11 +278,6 @@ int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, cons
     d.n = n_of(b0 + j);
     d.out_off = off[j] + np;
     d.out_cap = pre_bound(M_, d.n);
-    if (slots && scr + d.n > kBwtSlots) {      // the next launch of zh_launch_pre_bwt starts here
-      cut.push_back(j);
-      max_scr = std::max(max_scr, scr);
-      scr = 0;
-    }
     d.scr_off = scr;
     scr += d.n;
     d.tab_bits = tab_bits(d.n);
@@ -163,114 +285,79 @@ int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, cons
     tab += 1ull << d.tab_bits;
     max_n = std::max<uint64_t>(max_n, d.n);
   }
+  const LaunchCuts C = M_.slots() ? cut_launches(desc) : LaunchCuts();
+  SortArena A(C.max_slots, M_.route != Route::Bwt);
+
+  // upload, and every buffer the route needs
   HIPCHK(plain_.alloc(plain));
   HIPCHK(desc_.alloc(nb * sizeof(ZhPreBlock)));
   HIPCHK(len_.alloc(nb * 8));
   if (plain) HIPCHK(hipMemcpy(plain_.p, in_ + base, plain, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(desc_.p, desc.data(), nb * sizeof(ZhPreBlock), hipMemcpyHostToDevice));
-  ZhPreLaunch L;
-  memset(&L, 0, sizeof L);
-  L.in = plain_.as<uint8_t>();
-  L.out = d_out;
-  L.blocks = desc_.as<ZhPreBlock>();
-  L.out_len = len_.as<uint64_t>();
-  L.n_blocks = (uint32_t)nb;
-  L.level = M_.level; L.doe8 = M_.doe8; L.k = M_.k; L.m = M_.m; L.rb = M_.rb;
-  L.max_match = M_.max_match; L.max_off = M_.max_off;
   if (np) {
     HIPCHK(pref_.alloc(np));
     HIPCHK(hipMemcpy(pref_.p, prefix.data(), np, hipMemcpyHostToDevice));
   }
-  std::vector<uint32_t> starts;
-  if (slots) {
-    max_scr = std::max(max_scr, scr);
-    cut.push_back(nb);
-    for (size_t u = 0; u + 1 < cut.size(); ++u) {      // starts of launch u at starts[cut[u] + u ..]
-      for (size_t j = cut[u]; j < cut[u + 1]; ++j) starts.push_back((uint32_t)desc[j].scr_off);
-      starts.push_back((uint32_t)(desc[cut[u + 1] - 1].scr_off + desc[cut[u + 1] - 1].n));
-    }
-    HIPCHK(tab_.alloc(starts.size() * 4));
-    HIPCHK(hipMemcpy(tab_.p, starts.data(), starts.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(chain_.alloc(16 * max_scr));             // key[2], val[2]
-    HIPCHK(prev_.alloc(4 * max_scr + 1024 * bwt_tiles(max_scr) + 4 * bwt_sums(max_scr) + 4));   // rank, counts, sums, multi
-    if (M_.sa || M_.ht) HIPCHK(dec_.alloc(8 * max_scr));
-    if (M_.doe8) HIPCHK(e8_.alloc(plain));
-    L.e8 = e8_.as<uint8_t>();
-  } else if (M_.level) {
+  if (M_.e8_copy()) HIPCHK(e8_.alloc(plain));
+  if (M_.slots()) {
+    HIPCHK(starts_.alloc(C.starts.size() * 4));
+    HIPCHK(hipMemcpy(starts_.p, C.starts.data(), C.starts.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(arena_.alloc(A.bytes()));
+    A.base = arena_.as<uint8_t>();
+  } else if (M_.route == Route::Greedy) {
     HIPCHK(tab_.alloc(tab * 4));
     HIPCHK(chain_.alloc(scr * 4));
     HIPCHK(prev_.alloc(scr * 4));
-    if (M_.doe8) HIPCHK(e8_.alloc(plain));
-    L.e8 = e8_.as<uint8_t>(); L.table = tab_.as<int32_t>(); L.chain = chain_.as<int32_t>(); L.prev = prev_.as<uint32_t>();
   }
+  ZhPreLaunch L;
+  memset(&L, 0, sizeof L);
+  L.in = plain_.as<uint8_t>();
+  L.e8 = e8_.as<uint8_t>();
+  L.out = d_out;
+  L.blocks = desc_.as<ZhPreBlock>();
+  L.out_len = len_.as<uint64_t>();
+  L.table = tab_.as<int32_t>(); L.chain = chain_.as<int32_t>(); L.prev = prev_.as<uint32_t>();
+  L.n_blocks = (uint32_t)nb;
+  L.level = M_.level; L.doe8 = M_.doe8; L.k = M_.k; L.m = M_.m; L.rb = M_.rb;
+  L.max_match = M_.max_match; L.max_off = M_.max_off;
+
+  // prefix and E8E9, then the route
   HIPCHK(hipMemsetAsync(len_.p, 0, nb * 8, v.stream));
   HIPCHK(hipEventRecord(v.ev0, v.stream));
-  HIPCHK(zh_launch_pre_prefix(&L, pref_.as<uint8_t>(), (uint32_t)np, v.stream));
-  if (M_.doe8) HIPCHK(zh_launch_pre_e8e9(&L, v.stream));
-  else if (!M_.level)                   // no pre-processing: the plaintext is the coded data
+  HIPCHK(zh_launch_pre_prefix(&L, pref_.as<uint8_t>(), (uint32_t)np, v.stream, &launches));
+  if (M_.doe8) HIPCHK(zh_launch_pre_e8e9(&L, v.stream, &launches));
+  if (M_.route == Route::Copy) {          // no pre-processing: the plaintext is the coded data
     for (size_t j = 0; j < nb; ++j)
       if (desc[j].n)
         HIPCHK(hipMemcpyAsync(d_out + desc[j].out_off, plain_.as<uint8_t>() + desc[j].in_off, desc[j].n, hipMemcpyDeviceToDevice, v.stream));
-  if (slots) {
-    for (size_t u = 0; u + 1 < cut.size(); ++u) {
-      ZhBwtLaunch W;
-      memset(&W, 0, sizeof W);
-      W.src = M_.doe8 ? e8_.as<uint8_t>() : plain_.as<uint8_t>();
-      W.out = d_out;
-      W.blocks = desc_.as<ZhPreBlock>() + cut[u];
-      W.out_len = len_.as<uint64_t>() + cut[u];
-      W.starts = tab_.as<uint32_t>() + cut[u] + u;
-      W.n_blocks = (uint32_t)(cut[u + 1] - cut[u]);
-      W.n = starts[cut[u + 1] + u];
-      for (size_t j = cut[u]; j < cut[u + 1]; ++j) W.max_n = std::max<uint32_t>(W.max_n, (uint32_t)desc[j].n);
-      for (int q = 0; q < 2; ++q) {
-        W.key[q] = chain_.as<uint32_t>() + (2 * q) * max_scr;
-        W.val[q] = chain_.as<uint32_t>() + (2 * q + 1) * max_scr;
-      }
-      W.rank = prev_.as<uint32_t>();
-      W.counts = W.rank + max_scr;
-      W.sums = W.counts + 256 * bwt_tiles(max_scr);
-      W.multi = W.sums + bwt_sums(max_scr);
-      uint32_t rounds = 0;                // the launcher reports its doubling rounds; nothing here uses them
-      if (M_.ht) {
-        ZhLzhtLaunch H;
-        memset(&H, 0, sizeof H);
-        H.src = W.src; H.out = d_out; H.blocks = W.blocks; H.out_len = W.out_len; H.starts = W.starts;
-        H.dec[0] = dec_.as<uint64_t>();
-        H.n_blocks = W.n_blocks; H.n = W.n;
-        H.level = M_.level; H.min_match = M_.m; H.bucket = M_.bucket; H.ht_bits = M_.ht_bits; H.checkbits = M_.checkbits;
-        H.shift1 = M_.shift1; H.search = M_.search; H.rb = M_.rb;
-        HIPCHK(zh_launch_pre_lzht(&H, &W, v.stream, &launches));
-        continue;
-      }
-      if (!M_.sa) {
-        HIPCHK(zh_launch_pre_bwt(&W, v.stream, &launches, &rounds));
-        continue;
-      }
-      uint32_t c = 0;
-      HIPCHK(zh_launch_pre_sufsort(&W, v.stream, &launches, &c));
-      ZhLzsaLaunch S;
-      memset(&S, 0, sizeof S);
-      S.src = W.src; S.out = d_out; S.blocks = W.blocks; S.out_len = W.out_len; S.starts = W.starts;
-      S.sa = W.val[c];
-      S.rank = W.rank;
-      S.lcp = W.key[c];                   // the sort is done with its keys and with the other pair of arrays
-      S.dec[0] = dec_.as<uint64_t>();
-      S.dec[1] = reinterpret_cast<uint64_t *>(W.key[c ^ 1]);      // key and val of a pair are adjacent: n 64-bit words
-      S.n_blocks = W.n_blocks; S.n = W.n;
-      S.level = M_.level; S.min_match = M_.m; S.bucket = M_.bucket; S.lookahead = M_.lookahead; S.win_bits = M_.win_bits; S.rb = M_.rb;
-      HIPCHK(zh_launch_pre_lzsa(&S, v.stream, &launches));
-    }
-  } else if (M_.level) {
+  } else if (M_.route == Route::Greedy) {
     HIPCHK(hipMemsetAsync(tab_.p, 0xFF, tab * 4, v.stream));
-    HIPCHK(zh_launch_pre_lz(&L, max_n, v.stream));
+    HIPCHK(zh_launch_pre_lz(&L, max_n, v.stream, &launches));
+  }
+  for (size_t u = 0; M_.slots() && u + 1 < C.cut.size(); ++u) {
+    const size_t j0 = C.cut[u], j1 = C.cut[u + 1];
+    ZhBwtLaunch W{};
+    W.src = M_.doe8 ? e8_.as<uint8_t>() : plain_.as<uint8_t>();
+    W.out = d_out;
+    W.blocks = desc_.as<ZhPreBlock>() + j0;
+    W.out_len = len_.as<uint64_t>() + j0;
+    W.starts = starts_.as<uint32_t>() + j0 + u;
+    W.n_blocks = (uint32_t)(j1 - j0);
+    W.n = C.starts[j1 + u];
+    for (size_t j = j0; j < j1; ++j) W.max_n = std::max<uint32_t>(W.max_n, (uint32_t)desc[j].n);
+    A.fill(W);
+    const int rc = M_.route == Route::Bwt ? run_bwt(W, v, launches, err)
+                 : M_.route == Route::Sa  ? run_sa(M_, W, A, v, launches, err)
+                                          : run_ht(M_, W, A, v, launches, err);
+    if (rc) return rc;
   }
   HIPCHK(hipEventRecord(v.ev1, v.stream));
   HIPCHK(hipStreamSynchronize(v.stream));
   HIPCHK(hipEventElapsedTime(&r.ms, v.ev0, v.ev1));
-  launches += (np ? 1 : 0) + (M_.doe8 ? 1 : 0) + (slots ? 0 : M_.level ? 3 : 0);
+
+  // the lengths, and their bounds
   r.len.assign(nb, 0);
-  if (M_.level || M_.doe8) HIPCHK(hipMemcpy(r.len.data(), len_.p, nb * 8, hipMemcpyDeviceToHost));
+  if (M_.route != Route::Copy) HIPCHK(hipMemcpy(r.len.data(), len_.p, nb * 8, hipMemcpyDeviceToHost));
   else
     for (size_t j = 0; j < nb; ++j) r.len[j] = desc[j].n;
   for (size_t j = 0; j < nb; ++j)
@@ -284,22 +371,28 @@ int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, cons
 
 namespace {
 
-int check_blocks(const Method &M, const uint8_t *in, const uint64_t *in_off, size_t n_blocks, zpaqhip_err *err) {
+// offsets must not decrease (nor advance without data), and no block may be longer than max_block
+int check_offsets(const uint8_t *in, const uint64_t *in_off, size_t n_blocks, uint64_t max_block, const char *too_long, zpaqhip_err *err) {
   for (size_t i = 0; i < n_blocks; ++i) {
     if (in_off[i + 1] < in_off[i] || (!in && in_off[i + 1] > in_off[i])) {
       set_err(err, ZPAQHIP_E_ARG, (int)i, -1, "block offsets must not decrease");
       return ZPAQHIP_E_ARG;
     }
-    if (in_off[i + 1] - in_off[i] > M.max_block) {
-      set_err(err, ZPAQHIP_E_ARG, (int)i, -1,
-              M.level == 3 ? "block longer than the BWT method allows (2^(args[0] + 20) - 4096, at most 2^31 - 1 bytes)"
-              : M.sa       ? "block longer than the suffix-array search takes (2^(args[0] + 20), at most 2^24 bytes)"
-              : M.ht       ? "block longer than the hash-table search takes (2^(args[0] + 20), at most 2^24 bytes)"
-                           : "block longer than the post-processor's M (2^(args[0] + 20) bytes)");
+    if (in_off[i + 1] - in_off[i] > max_block) {
+      set_err(err, ZPAQHIP_E_ARG, (int)i, -1, too_long);
       return ZPAQHIP_E_ARG;
     }
   }
   return ZPAQHIP_OK;
+}
+
+int check_blocks(const Method &M, const uint8_t *in, const uint64_t *in_off, size_t n_blocks, zpaqhip_err *err) {
+  return check_offsets(in, in_off, n_blocks, M.max_block,
+                       M.route == Route::Bwt  ? "block longer than the BWT method allows (2^(args[0] + 20) - 4096, at most 2^31 - 1 bytes)"
+                       : M.route == Route::Sa ? "block longer than the suffix-array search takes (2^(args[0] + 20), at most 2^24 bytes)"
+                       : M.route == Route::Ht ? "block longer than the hash-table search takes (2^(args[0] + 20), at most 2^24 bytes)"
+                                              : "block longer than the post-processor's M (2^(args[0] + 20) bytes)",
+                       err);
 }
 
 // the pre-processed bytes of a method's blocks, back to back (zpaqhip_preprocess_blocks, zpaqhip_bwt_blocks)
@@ -338,18 +431,22 @@ int preprocess_impl(zpaqhip_ctx *ctx, const Method &M, const uint8_t *in, const 
   return finish_call(v, st, pos, n_blocks, out_off, out_cap, out_len, err);
 }
 
+// What the four pre-processing entry points share.  `wrong_route`, when given, refuses a method that does not select `want`.
+int preprocess_entry(zpaqhip_ctx *ctx, const int32_t *args, uint32_t flags, Route want, const char *wrong_route, const uint8_t *in,
+                     const uint64_t *in_off, size_t n_blocks, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off,
+                     zpaqhip_err *err) {
+  if (!ctx || !out_len || (!out && out_cap) || (n_blocks && !in_off)) return refuse(err);
+  *out_len = 0;
+  Method M;
+  if (const int rc = parse_method(args, flags, M, err)) return rc;
+  if (wrong_route && M.route != want) return refuse(err, wrong_route);
+  return preprocess_impl(ctx, M, in, in_off, n_blocks, out, out_cap, out_len, out_off, err);
+}
+
 // the repetition-gap histograms of compressBlock's levels 5..9 (LibZPAQ.cs:242-255), zh_analyze.hip
 int gap_hist_impl(zpaqhip_ctx *ctx, const uint8_t *in, const uint64_t *in_off, size_t n_blocks, uint32_t *hist, zpaqhip_err *err) {
-  for (size_t i = 0; i < n_blocks; ++i) {
-    if (in_off[i + 1] < in_off[i] || (!in && in_off[i + 1] > in_off[i])) {
-      set_err(err, ZPAQHIP_E_ARG, (int)i, -1, "block offsets must not decrease");
-      return ZPAQHIP_E_ARG;
-    }
-    if (in_off[i + 1] - in_off[i] > (1ull << 31) - 1) {      // 32-bit positions and counters
-      set_err(err, ZPAQHIP_E_ARG, (int)i, -1, "block longer than 2^31 - 1 bytes");
-      return ZPAQHIP_E_ARG;
-    }
-  }
+  // 32-bit positions and counters
+  if (const int rc = check_offsets(in, in_off, n_blocks, (1ull << 31) - 1, "block longer than 2^31 - 1 bytes", err)) return rc;
   CtxView v = ctx_view(ctx);
   HIPCHK(hipSetDevice(v.device));
   uint64_t budget = 0;
@@ -402,73 +499,33 @@ int gap_hist_impl(zpaqhip_ctx *ctx, const uint8_t *in, const uint64_t *in_off, s
 
 extern "C" int zpaqhip_gap_hist_blocks(zpaqhip_ctx *ctx, const uint8_t *in, const uint64_t *in_off, size_t n_blocks, uint32_t *hist,
                                        zpaqhip_err *err) {
-  if (!ctx || (n_blocks && (!in_off || !hist))) {
-    set_err(err, ZPAQHIP_E_ARG, -1, -1);
-    return ZPAQHIP_E_ARG;
-  }
+  if (!ctx || (n_blocks && (!in_off || !hist))) return refuse(err);
   return gap_hist_impl(ctx, in, in_off, n_blocks, hist, err);
 }
 
 extern "C" int zpaqhip_preprocess_blocks(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *in, const uint64_t *in_off,
                                          size_t n_blocks, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off,
                                          zpaqhip_err *err) {
-  if (!ctx || !out_len || (!out && out_cap) || (n_blocks && !in_off)) {
-    set_err(err, ZPAQHIP_E_ARG, -1, -1);
-    return ZPAQHIP_E_ARG;
-  }
-  *out_len = 0;
-  Method M;
-  const int rc = parse_method(args, false, false, false, M, err);
-  if (rc) return rc;
-  return preprocess_impl(ctx, M, in, in_off, n_blocks, out, out_cap, out_len, out_off, err);
+  return preprocess_entry(ctx, args, 0, Route::Copy, nullptr, in, in_off, n_blocks, out, out_cap, out_len, out_off, err);
 }
 
 extern "C" int zpaqhip_lzsa_blocks(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
                                    uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off, zpaqhip_err *err) {
-  if (!ctx || !out_len || (!out && out_cap) || (n_blocks && !in_off)) {
-    set_err(err, ZPAQHIP_E_ARG, -1, -1);
-    return ZPAQHIP_E_ARG;
-  }
-  *out_len = 0;
-  Method M;
-  const int rc = parse_method(args, false, true, false, M, err);
-  if (rc) return rc;
-  if (!M.sa) {
-    set_err(err, ZPAQHIP_E_ARG, -1, -1, "not a level 1 / 2 method with args[5] - args[0] >= 21");
-    return ZPAQHIP_E_ARG;
-  }
-  return preprocess_impl(ctx, M, in, in_off, n_blocks, out, out_cap, out_len, out_off, err);
+  return preprocess_entry(ctx, args, kFlagSa, Route::Sa, "not a level 1 / 2 method with args[5] - args[0] >= 21", in, in_off, n_blocks,
+                          out, out_cap, out_len, out_off, err);
 }
 
 extern "C" int zpaqhip_lzht_blocks(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
                                    uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off, zpaqhip_err *err) {
-  if (!ctx || !out_len || (!out && out_cap) || (n_blocks && !in_off)) {
-    set_err(err, ZPAQHIP_E_ARG, -1, -1);
-    return ZPAQHIP_E_ARG;
-  }
-  *out_len = 0;
-  Method M;
-  const int rc = parse_method(args, false, false, true, M, err);
-  if (rc) return rc;
-  if (!M.ht) {
-    set_err(err, ZPAQHIP_E_ARG, -1, -1, "not a level 1 / 2 method with args[5] - args[0] < 21");
-    return ZPAQHIP_E_ARG;
-  }
-  return preprocess_impl(ctx, M, in, in_off, n_blocks, out, out_cap, out_len, out_off, err);
+  return preprocess_entry(ctx, args, kFlagHt, Route::Ht, "not a level 1 / 2 method with args[5] - args[0] < 21", in, in_off, n_blocks,
+                          out, out_cap, out_len, out_off, err);
 }
 
 extern "C" int zpaqhip_bwt_blocks(zpaqhip_ctx *ctx, int doe8, const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
                                   uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *out_off, zpaqhip_err *err) {
-  if (!ctx || !out_len || (!out && out_cap) || (n_blocks && !in_off)) {
-    set_err(err, ZPAQHIP_E_ARG, -1, -1);
-    return ZPAQHIP_E_ARG;
-  }
-  *out_len = 0;
-  Method M;
-  M.level = 3;
-  M.doe8 = doe8 != 0;
-  M.max_block = (1ull << 31) - 1;         // no post-processor here: the suffix array's 32-bit slots are the only limit
-  return preprocess_impl(ctx, M, in, in_off, n_blocks, out, out_cap, out_len, out_off, err);
+  // no post-processor here: args[0] = 12 lifts the method's limit to that of the suffix array's 32-bit slots, 2^31 - 1 bytes
+  const int32_t args[9] = {12, doe8 ? 7 : 3};
+  return preprocess_entry(ctx, args, kFlagBwt, Route::Bwt, nullptr, in, in_off, n_blocks, out, out_cap, out_len, out_off, err);
 }
 
 extern "C" int zpaqhip_compress_method_blocks(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *hdr, size_t hdr_len,
@@ -476,14 +533,11 @@ extern "C" int zpaqhip_compress_method_blocks(zpaqhip_ctx *ctx, const int32_t *a
                                               size_t n_blocks, const char *const *filenames, uint8_t *out, size_t out_cap,
                                               size_t *out_len, uint64_t *block_off, const zpaqhip_compress_opts *opts,
                                               zpaqhip_err *err) {
-  if (!ctx || !hdr || !out_len || (!out && out_cap) || (n_blocks && !in_off) || (pcomp_len && !pcomp) || pcomp_len > 65535) {
-    set_err(err, ZPAQHIP_E_ARG, -1, -1);
-    return ZPAQHIP_E_ARG;
-  }
+  if (!ctx || !hdr || !out_len || (!out && out_cap) || (n_blocks && !in_off) || (pcomp_len && !pcomp) || pcomp_len > 65535)
+    return refuse(err);
   *out_len = 0;
   Method M;
-  const uint32_t flags = resolve_compress_opts(opts).flags;
-  int rc = parse_method(args, (flags & kFlagBwt) != 0, (flags & kFlagSa) != 0, (flags & kFlagHt) != 0, M, err);
+  int rc = parse_method(args, resolve_compress_opts(opts).flags, M, err);
   if (rc) return rc;
   if ((rc = check_blocks(M, in, in_off, n_blocks, err))) return rc;
   DevPre P(M, in, in_off);

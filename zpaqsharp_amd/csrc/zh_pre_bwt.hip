@@ -34,16 +34,6 @@ namespace {
 constexpr uint32_t kTile = 4096;          // pairs per wave and radix pass
 constexpr uint32_t kChunk = 4096;         // words per workgroup of a scan
 
-__device__ __forceinline__ uint32_t block_of(const ZhBwtLaunch &L, uint32_t slot) {   // the block that owns a slot
-  uint32_t lo = 0, hi = L.n_blocks - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (L.starts[mid] <= slot) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 __device__ __forceinline__ uint32_t key4(const uint8_t *p, uint32_t l, uint32_t n) {
   uint32_t k = 0;
   for (uint32_t t = 0; t < 4; ++t) k = k << 8 | (l + t < n ? p[l + t] : 0u);
@@ -180,7 +170,7 @@ __global__ __launch_bounds__(64) void zh_bwt_scatter(const uint32_t *key, const 
 __global__ __launch_bounds__(256) void zh_bwt_init(ZhBwtLaunch L) {
   const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= L.n) return;
-  const uint32_t b = block_of(L, (uint32_t)j), s = L.starts[b], nb = L.starts[b + 1] - s;
+  const uint32_t b = block_of(L.starts, L.n_blocks, (uint32_t)j), s = L.starts[b], nb = L.starts[b + 1] - s;
   const uint32_t l = nb - 1 - ((uint32_t)j - s);
   L.val[0][j] = s + l;
   L.key[0][j] = key4(L.src + L.blocks[b].in_off, l, nb);
@@ -189,13 +179,13 @@ __global__ __launch_bounds__(256) void zh_bwt_init(ZhBwtLaunch L) {
 __global__ __launch_bounds__(256) void zh_bwt_blockkey(ZhBwtLaunch L, uint32_t c) {
   const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= L.n) return;
-  L.key[c][j] = block_of(L, L.val[c][j]);
+  L.key[c][j] = block_of(L.starts, L.n_blocks, L.val[c][j]);
 }
 
 __global__ __launch_bounds__(256) void zh_bwt_build(ZhBwtLaunch L, uint32_t c, uint32_t h) {
   const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= L.n) return;
-  const uint32_t b = block_of(L, (uint32_t)j), s = L.starts[b], nb = L.starts[b + 1] - s;
+  const uint32_t b = block_of(L.starts, L.n_blocks, (uint32_t)j), s = L.starts[b], nb = L.starts[b + 1] - s;
   const uint32_t l = L.val[c][j] - s;
   const uint32_t i = l >= h ? l - h : nb >= h ? nb - h + l : l;
   L.val[c][j] = s + i;
@@ -206,7 +196,7 @@ __global__ __launch_bounds__(256) void zh_bwt_build(ZhBwtLaunch L, uint32_t c, u
 __global__ __launch_bounds__(256) void zh_bwt_flags(ZhBwtLaunch L, uint32_t c, uint32_t h, uint32_t first) {
   const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (j >= L.n) return;
-  const uint32_t b = block_of(L, (uint32_t)j), s = L.starts[b], nb = L.starts[b + 1] - s;
+  const uint32_t b = block_of(L.starts, L.n_blocks, (uint32_t)j), s = L.starts[b], nb = L.starts[b + 1] - s;
   bool head = j == s;
   if (!head) {
     const uint32_t a = L.val[c][j], p = L.val[c][j - 1];
@@ -235,7 +225,7 @@ __global__ __launch_bounds__(256) void zh_bwt_rank(ZhBwtLaunch L, uint32_t c) {
 __global__ __launch_bounds__(256) void zh_bwt_emit(ZhBwtLaunch L, uint32_t c) {
   const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (j < L.n) {
-    const uint32_t b = block_of(L, (uint32_t)j), s = L.starts[b];
+    const uint32_t b = block_of(L.starts, L.n_blocks, (uint32_t)j), s = L.starts[b];
     const ZhPreBlock B = L.blocks[b];
     const uint32_t l = L.val[c][j] - s;
     const uint64_t slot = j - s;

@@ -10,7 +10,8 @@
 //   zh_pre_lz_verify one thread per position follows chain[] to the nearest position whose k bytes are equal (so
 //                    prev[] is exact whatever the hash does) and measures up to ZH_PRE_EXT more matching bytes
 //   zh_pre_lz_parse  one wave per block walks the greedy parse, 64 prev[] entries per ballot, extends the rare long
-//                    matches 64 bytes per step, and writes the codes as it goes (literal runs 64 bytes per store)
+//                    matches 64 bytes per step, and writes the codes as it goes through LzCodes (zh_pre_lzcodes.h:
+//                    literal runs 64 bytes per store)
 //
 // Every store is a plain C++ store to global memory or LDS; out_cap bounds every write to ::out.
 #include <hip/hip_runtime.h>
@@ -18,6 +19,7 @@
 #include <algorithm>
 
 #include "zh_pre.h"
+#include "zh_pre_lzcodes.h"
 
 namespace {
 
@@ -33,28 +35,6 @@ __device__ __forceinline__ uint32_t bucket_of(const uint8_t *p, uint32_t k, uint
   h ^= h >> 32;
   return (uint32_t)(h >> (64 - bits));
 }
-
-__device__ __forceinline__ int lg(uint64_t x) { return x ? 64 - __clzll((long long)x) : 0; }   // LZBuffer.cs:116-126
-
-// the bit writer of LZBuffer level 1 (LSB first, LZBuffer.cs:50-63); every lane holds the same state, lane 0 stores
-struct Bits {
-  uint8_t *out;
-  uint64_t cap, pos;
-  uint64_t acc;
-  int n;
-  __device__ void put(uint64_t x, int k) {
-    if (k == 0) return;
-    x &= (1ull << k) - 1;
-    acc |= x << n;
-    n += k;
-    while (n > 7) {
-      if (threadIdx.x == 0 && pos < cap) out[pos] = (uint8_t)acc;
-      ++pos;
-      acc >>= 8;
-      n -= 8;
-    }
-  }
-};
 
 }  // namespace
 
@@ -213,78 +193,8 @@ __global__ __launch_bounds__(64) void zh_pre_lz_parse(ZhPreLaunch L) {
   const uint8_t *d = src_of(L, B);
   const int64_t n = (int64_t)B.n, k = L.k;
   const uint32_t *prev = L.prev + B.scr_off;
-  uint8_t *out = L.out + B.out_off;
-  const uint64_t cap = B.out_cap;
   const int lane = threadIdx.x;
-  const int m = (int)L.m, rb = (int)L.rb;
-  Bits w{out, cap, 0, 0, 0};                      // level 1 writer; level 2 uses w.pos only
-
-  auto literals = [&](int64_t a, int64_t b) {
-    if (b <= a) return;
-    if (L.level == 1) {
-      const uint64_t lit = (uint64_t)(b - a);
-      int ll = lg(lit);
-      w.put(0, 2);
-      --ll;
-      while (ll > 0) {
-        --ll;
-        w.put(1, 1);
-        w.put((lit >> ll) & 1, 1);
-      }
-      w.put(0, 1);
-      for (int64_t s = a; s < b; s += 64) {       // whole bytes at a bit offset of w.n
-        const int cnt = (int)min((int64_t)64, b - s);
-        const uint32_t v = lane < cnt ? d[s + lane] : 0;
-        const uint32_t lo = __shfl(v, lane > 0 ? lane - 1 : 0);
-        const uint32_t byte = ((v << w.n) | (lane == 0 ? (uint32_t)w.acc : lo >> (8 - w.n))) & 255;
-        if (lane < cnt && w.pos + lane < cap) out[w.pos + lane] = (uint8_t)byte;
-        w.acc = __shfl(v, cnt - 1) >> (8 - w.n);
-        w.pos += cnt;
-      }
-    } else {
-      for (int64_t s = a; s < b; s += 64) {       // 64-byte chunks, each after its length - 1
-        const int cnt = (int)min((int64_t)64, b - s);
-        if (lane == 0 && w.pos < cap) out[w.pos] = (uint8_t)(cnt - 1);
-        if (lane < cnt && w.pos + 1 + lane < cap) out[w.pos + 1 + lane] = d[s + lane];
-        w.pos += cnt + 1;
-      }
-    }
-  };
-  auto match = [&](uint64_t ln, uint64_t off) {
-    if (L.level == 1) {
-      int ll = lg(ln) - 1;
-      off += (1ull << rb) - 1;
-      const int lo = lg(off) - 1 - rb;
-      w.put((uint64_t)(lo + 8) >> 3, 2);
-      w.put((uint64_t)lo & 7, 3);
-      while (ll > 2) {
-        --ll;
-        w.put(1, 1);
-        w.put((ln >> ll) & 1, 1);
-      }
-      w.put(0, 1);
-      w.put(ln & 3, 2);
-      w.put(off, rb);
-      w.put(off >> rb, lo);
-    } else {
-      --off;
-      while (ln > 0) {
-        const uint64_t len1 = ln > (uint64_t)(2 * m + 63) ? (uint64_t)(m + 63) : ln > (uint64_t)(m + 63) ? ln - m : ln;
-        uint8_t c[4];
-        int nc;
-        if (off < (1u << 16)) {
-          c[0] = (uint8_t)(64 + len1 - m); c[1] = (uint8_t)(off >> 8); c[2] = (uint8_t)off; nc = 3;
-        } else {
-          c[0] = (uint8_t)(128 + len1 - m); c[1] = (uint8_t)(off >> 16); c[2] = (uint8_t)(off >> 8); c[3] = (uint8_t)off; nc = 4;
-        }
-        if (lane == 0)
-          for (int t = 0; t < nc; ++t)
-            if (w.pos + t < cap) out[w.pos + t] = c[t];
-        w.pos += nc;
-        ln -= len1;
-      }
-    }
-  };
+  LzCodes w(L.out + B.out_off, B.out_cap, L.level, (int)L.m, (int)L.rb);
 
   int64_t cur = 0, lit0 = 0, wbase = -64;
   uint32_t wv = 0;
@@ -316,16 +226,13 @@ __global__ __launch_bounds__(64) void zh_pre_lz_parse(ZhPreLaunch L) {
         }
         len += 64;
       }
-    literals(lit0, i);
-    match((uint64_t)len, (uint64_t)dist);
+    w.literals(d, lit0, i);
+    w.match((uint64_t)len, (uint64_t)dist);
     cur = lit0 = i + len;
   }
-  literals(lit0, n);
-  if (L.level == 1 && w.n > 0) {                  // flush
-    if (lane == 0 && w.pos < cap) out[w.pos] = (uint8_t)w.acc;
-    ++w.pos;
-  }
-  if (lane == 0) L.out_len[blockIdx.x] = w.pos;
+  w.literals(d, lit0, n);
+  const uint64_t pos = w.finish();
+  if (lane == 0) L.out_len[blockIdx.x] = pos;
 }
 
 // the coded sequence's post-processor header in front of each block's pre-processed bytes (Compressor.postProcess)
@@ -334,19 +241,22 @@ __global__ __launch_bounds__(64) void zh_pre_prefix(ZhPreLaunch L, const uint8_t
   for (uint32_t t = threadIdx.x; t < np; t += blockDim.x) L.out[B.out_off - np + t] = prefix[t];
 }
 
-extern "C" hipError_t zh_launch_pre_prefix(const ZhPreLaunch *L, const uint8_t *prefix, uint32_t np, hipStream_t stream) {
+// Each launcher adds the kernels it launched to *launches.
+extern "C" hipError_t zh_launch_pre_prefix(const ZhPreLaunch *L, const uint8_t *prefix, uint32_t np, hipStream_t stream, uint32_t *launches) {
   if (!L->n_blocks || !np) return hipSuccess;
   hipLaunchKernelGGL(zh_pre_prefix, dim3(L->n_blocks), dim3(64), 0, stream, *L, prefix, np);
+  ++*launches;
   return hipGetLastError();
 }
 
-extern "C" hipError_t zh_launch_pre_e8e9(const ZhPreLaunch *L, hipStream_t stream) {
+extern "C" hipError_t zh_launch_pre_e8e9(const ZhPreLaunch *L, hipStream_t stream, uint32_t *launches) {
   if (!L->n_blocks) return hipSuccess;
   hipLaunchKernelGGL(zh_pre_e8e9, dim3(L->n_blocks), dim3(64), 0, stream, *L);
+  ++*launches;
   return hipGetLastError();
 }
 
-extern "C" hipError_t zh_launch_pre_lz(const ZhPreLaunch *L, uint64_t max_n, hipStream_t stream) {
+extern "C" hipError_t zh_launch_pre_lz(const ZhPreLaunch *L, uint64_t max_n, hipStream_t stream, uint32_t *launches) {
   if (!L->n_blocks) return hipSuccess;
   hipLaunchKernelGGL(zh_pre_lz_prev, dim3(L->n_blocks), dim3(64), 0, stream, *L);
   hipError_t e = hipGetLastError();
@@ -356,5 +266,6 @@ extern "C" hipError_t zh_launch_pre_lz(const ZhPreLaunch *L, uint64_t max_n, hip
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(zh_pre_lz_parse, dim3(L->n_blocks), dim3(64), 0, stream, *L);
+  *launches += 3;
   return hipGetLastError();
 }

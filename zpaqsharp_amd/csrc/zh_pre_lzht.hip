@@ -33,16 +33,6 @@
 
 namespace {
 
-__device__ __forceinline__ uint32_t block_of(const ZhLzhtLaunch &L, uint32_t slot) {   // the block that owns a slot
-  uint32_t lo = 0, hi = L.n_blocks - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (L.starts[mid] <= slot) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 // h1 before the step at position e <= max(0, n - minMatchBoth) (LZBuffer.cs:364): the last min(e, minMatch) steps
 __device__ __forceinline__ uint32_t h1_at(const ZhLzhtLaunch &L, const uint8_t *d, uint32_t e) {
   const uint32_t mm = L.min_match;
@@ -102,7 +92,7 @@ __device__ uint64_t decide(const ZhLzhtLaunch &L, const uint8_t *d, uint32_t s, 
 __global__ __launch_bounds__(256) void zh_lzht_keys(ZhLzhtLaunch L, uint32_t *key, uint32_t *val) {
   const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (x >= L.n) return;
-  const uint32_t b = block_of(L, (uint32_t)x), s = L.starts[b], n = L.starts[b + 1] - s, j = (uint32_t)x - s;
+  const uint32_t b = block_of(L.starts, L.n_blocks, (uint32_t)x), s = L.starts[b], n = L.starts[b + 1] - s, j = (uint32_t)x - s;
   uint32_t k = 1u << L.ht_bits;                   // not stored (LZBuffer.cs:353)
   if ((uint64_t)j + L.min_match + 4 < n) k = h1_at(L, L.src + L.blocks[b].in_off, j) ^ (((j * 1234547u) >> 19) & L.bucket);
   key[x] = k;
@@ -115,7 +105,7 @@ __global__ __launch_bounds__(256) void zh_lzht_search(ZhLzhtLaunch L) {
   if (x >= L.n) return;
   uint64_t v0 = 0, v1 = 0;
   if (L.search) {
-    const uint32_t b = block_of(L, (uint32_t)x), s = L.starts[b], n = L.starts[b + 1] - s, i = (uint32_t)x - s;
+    const uint32_t b = block_of(L.starts, L.n_blocks, (uint32_t)x), s = L.starts[b], n = L.starts[b + 1] - s, i = (uint32_t)x - s;
     const uint8_t *d = L.src + L.blocks[b].in_off;
     const uint32_t both = L.min_match + 4, frozen = n > both ? n - both : 0;
     const uint32_t h1 = h1_at(L, d, min(i, frozen));
@@ -135,11 +125,12 @@ __global__ __launch_bounds__(64) void zh_lzht_walk(ZhLzhtLaunch L) {
   if (threadIdx.x == 0) L.out_len[blockIdx.x] = pos;
 }
 
-// The codes of L_->n_blocks blocks.  W holds the sort's buffers for the same slot space (key and val of a pair adjacent, as
-// zh_pre.cpp lays them out): the pairs are written to W->key[0] / val[0] and sorted; the pair of arrays the sort ends in
-// becomes ::key / ::val, the other one, 8 bytes per slot, ::dec[1].  The caller sets everything else.  *launches grows by
-// the kernels launched.
-extern "C" hipError_t zh_launch_pre_lzht(const ZhLzhtLaunch *L_, const ZhBwtLaunch *W, hipStream_t stream, uint32_t *launches) {
+// The codes of L_->n_blocks blocks.  W holds the sort's buffers for the same slot space and words[q] its pair q as one array
+// of 64-bit words (zh_pre.cpp's SortArena): the pairs are written to W->key[0] / val[0] and sorted; the pair of arrays the
+// sort ends in becomes ::key / ::val, the other one ::dec[1].  The caller sets everything else.  *launches grows by the
+// kernels launched.
+extern "C" hipError_t zh_launch_pre_lzht(const ZhLzhtLaunch *L_, const ZhBwtLaunch *W, uint64_t *const words[2], hipStream_t stream,
+                                         uint32_t *launches) {
   ZhLzhtLaunch L = *L_;
   if (!L.n_blocks) return hipSuccess;
   hipError_t e;
@@ -154,7 +145,7 @@ extern "C" hipError_t zh_launch_pre_lzht(const ZhLzhtLaunch *L_, const ZhBwtLaun
     }
     L.key = W->key[c];
     L.val = W->val[c];
-    L.dec[1] = reinterpret_cast<uint64_t *>(W->key[c ^ 1]);
+    L.dec[1] = words[c ^ 1];
     hipLaunchKernelGGL(zh_lzht_search, grid, dim3(256), 0, stream, L);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (launches) ++*launches;

@@ -30,16 +30,6 @@ namespace {
 
 constexpr uint32_t kLcpChunk = 1024;      // positions per wave of zh_lzsa_lcp
 
-__device__ __forceinline__ uint32_t block_of(const ZhLzsaLaunch &L, uint32_t slot) {   // the block that owns a slot
-  uint32_t lo = 0, hi = L.n_blocks - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (L.starts[mid] <= slot) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 // LZBuffer.cs:249-283 and the accept rule :332-346 at position i of a block of n bytes whose first slot is s.
 // Returns the decision; *dep is set when a candidate with look-ahead and leading literals was scored.
 __device__ uint64_t decide(const ZhLzsaLaunch &L, const uint8_t *d, uint32_t s, uint32_t n, uint32_t i, bool lit0, bool *dep) {
@@ -92,7 +82,7 @@ __global__ __launch_bounds__(64) void zh_lzsa_lcp(ZhLzsaLaunch L) {
   const uint64_t base = (uint64_t)blockIdx.x * kLcpChunk;
   if (base >= L.n) return;
   const uint32_t end = (uint32_t)min<uint64_t>(base + kLcpChunk, L.n);
-  uint32_t b = block_of(L, (uint32_t)base), s = L.starts[b], e = L.starts[b + 1];
+  uint32_t b = block_of(L.starts, L.n_blocks, (uint32_t)base), s = L.starts[b], e = L.starts[b + 1];
   const uint8_t *d = L.src + L.blocks[b].in_off - s;          // d[x] = the byte of slot-numbered position x
   uint32_t carry = 0;
   for (uint32_t g = (uint32_t)base; g < end; g += 64) {
@@ -135,7 +125,7 @@ __global__ __launch_bounds__(64) void zh_lzsa_lcp(ZhLzsaLaunch L) {
 __global__ __launch_bounds__(256) void zh_lzsa_search(ZhLzsaLaunch L) {
   const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (x >= L.n) return;
-  const uint32_t b = block_of(L, (uint32_t)x), s = L.starts[b], n = L.starts[b + 1] - s;
+  const uint32_t b = block_of(L.starts, L.n_blocks, (uint32_t)x), s = L.starts[b], n = L.starts[b + 1] - s;
   const uint8_t *d = L.src + L.blocks[b].in_off;
   bool dep = false;
   const uint64_t v1 = decide(L, d, s, n, (uint32_t)x - s, false, &dep);

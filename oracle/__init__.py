@@ -275,8 +275,11 @@ class Compressor:
 def compress_block(header: bytes, data: bytes, pcomp: bytes = b"", filename: bytes = b"",
                    comment: Optional[bytes] = None, with_sha1: bool = True, tag: bool = True) -> bytes:
     """One block, one segment — the framing LibZPAQ.compressBlock produces
-    (LibZPAQ.cs:296-323): tag, header, segment(filename, comment=size), sha1."""
-    c = Compressor(len(data) * 2 + len(header) + len(pcomp) * 2 + 4096)
+    (LibZPAQ.cs:296-323): tag, header, segment(filename, comment=size), sha1.
+    Room for the worst case of any model: the coder emits at most 2 bytes per coded bit (a 16-bit probability), so 16 per
+    byte of the selector-prefixed sequence, plus header, framing and the end of segment."""
+    coded = len(data) + (len(pcomp) + 3 if pcomp else 1)
+    c = Compressor(16 * coded + len(header) + len(filename) + (len(comment) if comment is not None else 24) + 4096)
     if tag:
         c.write_tag()
     c.start_block(header)

@@ -9,6 +9,7 @@ import pytest
 
 import oracle
 from tests import util
+from tests.chain_cases import LEVEL5
 from tools import methods
 from zpaqsharp_amd import compressor, decompresser, method, models, synth
 from zpaqsharp_amd.zpaql import assemble
@@ -18,7 +19,6 @@ pytestmark = pytest.mark.gpu
 SIZES = (0, 1, 255, 256, 4097, 65536)
 KINDS = ("T", "X", "R")
 NAMED = ["min", "mid", "max", "max+e8e9"]
-LEVEL5 = "x0,0w1i1c256ci1,1,1,1,1,1,2ac0,2,0,255i1c0,3,0,0,255i1c0,4,0,0,0,255i1mm16ts19t0"
 METHOD_MODELS = ["x0,3ci1", "x0,2,12,0,7,16,1c0,0,511i2", "x0,0ci1,1,1,1,2am", "x0,0ci1,1,1,1,2awm", "x0,6,5,0,3,16c0,0,511", LEVEL5]
 MODELS = NAMED + METHOD_MODELS
 

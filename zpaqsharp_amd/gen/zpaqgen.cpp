@@ -28,13 +28,15 @@ using namespace zhcore;
 namespace {
 
 // ---------------------------------------------------------------------------
-// Host-side Predictor.init (Predictor.cs:82-171) for one arena slot.
+// Host-side Predictor.init (Predictor.cs:82-171) for one arena slot.  `zeroed`: the
+// slot comes straight from calloc, so the tables that start as zeros are left alone
+// (a short block then touches only the pages its contexts reach).
 // ---------------------------------------------------------------------------
 uint32_t cminit(const ZhTables &t, int j) {          // StateTable.cs:158-162
   return (uint32_t)(((t.ns[j * 4 + 3] * 2 + 1) << 22) / (t.ns[j * 4 + 2] + t.ns[j * 4 + 3] + 1));
 }
 
-void host_init_slot(const ZhModel &M, uint8_t *slot, GenLds &S) {
+void host_init_slot(const ZhModel &M, uint8_t *slot, GenLds &S, bool zeroed) {
   const ZhTables &t = S.t;
   for (uint32_t i = 0; i < M.n; ++i) {
     const ZhComp &cp = M.comp[i];
@@ -45,12 +47,11 @@ void host_init_slot(const ZhModel &M, uint8_t *slot, GenLds &S) {
         for (uint64_t j = 0; j < cp.cm_bytes / 4; ++j) cm[j] = 0x80000000u;
         break;
       case ZH_ICM:
-        memset(ht, 0, cp.ht_bytes);
+        if (!zeroed) memset(ht, 0, cp.ht_bytes);
         for (int j = 0; j < 256; ++j) cm[j] = cminit(t, j);
         break;
       case ZH_MATCH:
-        memset(cm, 0, cp.cm_bytes);
-        memset(ht, 0, cp.ht_bytes);
+        if (!zeroed) { memset(cm, 0, cp.cm_bytes); memset(ht, 0, cp.ht_bytes); }
         ht[0] = 1;
         break;
       case ZH_MIX2:
@@ -60,7 +61,7 @@ void host_init_slot(const ZhModel &M, uint8_t *slot, GenLds &S) {
         for (uint64_t j = 0; j < cp.cm_bytes / 4; ++j) cm[j] = 65536u / cp.arg[2];
         break;
       case ZH_ISSE:
-        memset(ht, 0, cp.ht_bytes);
+        if (!zeroed) memset(ht, 0, cp.ht_bytes);
         for (int j = 0; j < 256; ++j) {
           ((int *)cm)[j * 2] = 1 << 15;
           ((int *)cm)[j * 2 + 1] = clamp512k(t.stretch[cminit(t, j) >> 8] * 1024);
@@ -73,7 +74,7 @@ void host_init_slot(const ZhModel &M, uint8_t *slot, GenLds &S) {
       default: break;
     }
   }
-  memset(slot + M.h_off, 0, M.arena_bytes - M.h_off);
+  if (!zeroed) memset(slot + M.h_off, 0, M.arena_bytes - M.h_off);
   for (int i = 0; i < 256; ++i) {
     S.p[i] = 0; S.h[i] = 0; S.r[i] = 0; S.pr[i] = 0;
     S.cs[i] = CompSt{0, 0, 0, 0, 0};
@@ -102,7 +103,9 @@ struct BlockWriter {
   ZhModel M;
   std::vector<uint8_t> code, hdr;
   std::unique_ptr<GenLds> S;
-  std::vector<uint8_t> slot;
+  struct Free { void operator()(uint8_t *p) const { free(p); } };
+  std::unique_ptr<uint8_t, Free> slot;
+  bool zeroed = false;                                 // nothing has been written to the slot since calloc
   Pred P;
   uint32_t low = 1, high = 0xFFFFFFFFu;
 
@@ -114,22 +117,25 @@ struct BlockWriter {
     if (M.n == 0) return ZPAQHIP_E_ARG;               // unmodelled store blocks are not generated here
     S.reset(new GenLds);
     S->t = zh::host_tables();
-    slot.resize(M.arena_bytes);
+    slot.reset((uint8_t *)calloc(M.arena_bytes, 1));
+    if (!slot) return ZPAQHIP_E_DEVICE_MEM;
+    zeroed = true;
     return 0;
   }
 
   void start_block() {                                 // Encoder.init, Encoder.cs:26-37 + Predictor.init
-    host_init_slot(M, slot.data(), *S);
+    host_init_slot(M, slot.get(), *S, zeroed);
+    zeroed = false;
     P.S = S.get();
     P.cd = M.comp;
-    P.slot = slot.data();
+    P.slot = slot.get();
     P.n = M.n;
     P.c8 = 1; P.hmap4 = 1;
     P.z.a = P.z.b = P.z.c = P.z.d = P.z.f = 0;
     P.z.prog = code.data() + M.code_off + ZH_CODE_PAD;
     P.z.len = M.hcomp_len;
-    P.z.m = slot.data() + M.m_off; P.z.mmask = (uint32_t)((1ull << M.hm) - 1);
-    P.z.h = (uint32_t *)(slot.data() + M.h_off); P.z.hmask = (uint32_t)((1ull << M.hh) - 1);
+    P.z.m = slot.get() + M.m_off; P.z.mmask = (uint32_t)((1ull << M.hm) - 1);
+    P.z.h = (uint32_t *)(slot.get() + M.h_off); P.z.hmask = (uint32_t)((1ull << M.hh) - 1);
     P.z.r = S->r;
     low = 1; high = 0xFFFFFFFFu;
   }
@@ -676,6 +682,47 @@ void *zpaqgen_stream_new(const uint8_t *hdr, size_t hdrlen, const uint8_t *pcomp
     s->offsets.push_back(s->bytes.size());
     s->bytes.insert(s->bytes.end(), p.begin(), p.end());
     std::vector<uint8_t>().swap(p);
+  }
+  s->offsets.push_back(s->bytes.size());
+  return s;
+}
+
+// The caller's blocks, data[offsets[b] .. offsets[b + 1]), each compressed as zpaqgen_compress_block does with its
+// defaults (no file name, the size as comment, SHA-1, tag), on `threads` host threads that keep their model's memory
+// from block to block: many short blocks of a large model cost an initialisation each, not an allocation each.
+void *zpaqgen_blocks_new(const uint8_t *hdr, size_t hdrlen, const uint8_t *pcomp, size_t plen, const uint8_t *data,
+                         const uint64_t *offsets, uint32_t nblocks, int threads) {
+  Stream *s = new Stream();
+  if (!zh::host_tables_ok()) { s->error = "table pins failed"; return s; }
+  std::vector<std::vector<uint8_t>> parts(nblocks);
+  std::atomic<uint32_t> next{0};
+  std::atomic<int> failed{0};
+  if (threads < 1) threads = 1;
+  std::vector<std::thread> th;
+  for (int t = 0; t < threads; ++t)
+    th.emplace_back([&] {
+      BlockWriter w;
+      if (w.setup(hdr, hdrlen)) { failed = 1; return; }
+      for (;;) {
+        uint32_t b = next.fetch_add(1);
+        if (b >= nblocks || failed) break;
+        const uint8_t *src = data + offsets[b];
+        const size_t n = (size_t)(offsets[b + 1] - offsets[b]);
+        uint8_t sha[20];
+        zh::sha1(src, n, sha);
+        Out o;
+        o.v.reserve(n / 2 + 4096);
+        char comment[32];
+        snprintf(comment, sizeof comment, "%zu", n);
+        if (w.write_block(o, pcomp, plen, src, n, "", comment, sha, true)) { failed = 1; break; }
+        parts[b].swap(o.v);
+      }
+    });
+  for (auto &t : th) t.join();
+  if (failed) { s->error = "block compression failed"; return s; }
+  for (auto &p : parts) {
+    s->offsets.push_back(s->bytes.size());
+    s->bytes.insert(s->bytes.end(), p.begin(), p.end());
   }
   s->offsets.push_back(s->bytes.size());
   return s;

@@ -39,6 +39,8 @@ def load():
         L.zpaqgen_compress_block.restype = C.c_long
         L.zpaqgen_stream_new.argtypes = [vp, sz, vp, sz, C.c_int, C.c_int, C.c_uint64, C.c_uint32, sz, C.c_int]
         L.zpaqgen_stream_new.restype = vp
+        L.zpaqgen_blocks_new.argtypes = [vp, sz, vp, sz, vp, vp, C.c_uint32, C.c_int]
+        L.zpaqgen_blocks_new.restype = vp
         L.zpaqgen_preprocess.argtypes = [C.POINTER(C.c_int), vp, sz, vp, sz, C.POINTER(sz)]
         L.zpaqgen_preprocess.restype = C.c_long
         L.zpaqgen_method_stream_new.argtypes = [vp, sz, vp, sz, C.POINTER(C.c_int), C.c_int, C.c_uint64, C.c_uint32, sz, C.c_int]
@@ -147,6 +149,33 @@ def compress_block(model, data, filename: bytes = b"", comment: Optional[bytes] 
             raise RuntimeError(f"zpaqgen_compress_block failed: {n}")
         return out[:n].tobytes()
     raise RuntimeError("zpaqgen_compress_block: capacity")
+
+
+def compress_blocks(model, blocks, threads: Optional[int] = None) -> list:
+    """compress_block(model, b) of every block, on `threads` host threads that keep the model's memory from block to block
+    (for many short blocks of a large model).  Models whose PCOMP wants pre-processed bytes are not taken."""
+    m: Model = models.get(model) if isinstance(model, str) else model
+    if m.pcomp_cmd:
+        raise ValueError("compress_blocks codes the blocks as they are: no pre-processing")
+    L = load()
+    parts = [_u8(b).reshape(-1) for b in blocks]
+    offs = np.zeros(len(parts) + 1, np.uint64)
+    offs[1:] = np.cumsum([p.size for p in parts], dtype=np.uint64) if parts else []
+    buf = np.ascontiguousarray(np.concatenate(parts)) if parts and offs[-1] else np.zeros(1, np.uint8)
+    hdr, pc = _u8(m.header), _u8(m.pcomp) if m.pcomp else None
+    h = L.zpaqgen_blocks_new(hdr.ctypes.data, hdr.size, pc.ctypes.data if pc is not None else None,
+                             pc.size if pc is not None else 0, buf.ctypes.data, offs.ctypes.data, len(parts),
+                             threads or min(16, os.cpu_count() or 1))
+    try:
+        e = L.zpaqgen_stream_error(h)
+        if e:
+            raise RuntimeError(e.decode())
+        out = np.empty(L.zpaqgen_stream_size(h), np.uint8)
+        o = np.zeros(len(parts) + 1, np.uint64)
+        L.zpaqgen_stream_copy(h, out.ctypes.data, o.ctypes.data)
+        return [out[int(o[i]):int(o[i + 1])].tobytes() for i in range(len(parts))]
+    finally:
+        L.zpaqgen_stream_free(h)
 
 
 def stream(model, kind: str = "T", nblocks: int = 1, block_size: int = 1 << 16, first_block: int = 0,

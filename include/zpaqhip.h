@@ -292,7 +292,12 @@ typedef struct zpaqhip_compress_opts {
                                2 as 0, but models that fit the lane-per-component kernel (ICM / ISSE / MATCH / MIX chains of at
                                most 64 components and 4 mixers: min, mid, max, the models of the method strings) on the
                                lane-per-component encoder (zh_enc_chain.hip); an opt-in until it becomes the default */
-  uint32_t reserved0;
+  uint32_t enc_waves;       /* lane-per-component encoder: encoder waves (blocks in flight) per compute unit.  0 automatic: a
+                               launch of more blocks than the device has compute units puts up to four waves, one per SIMD,
+                               on a unit, as many as the model's LDS plan allows (zpaqhip_enc_chain_plan) and the blocks
+                               and device memory call for; 1 one wave per unit; 2 to 4 a cap on the automatic choice; above
+                               4 ZPAQHIP_E_ARG.  The coded bytes never depend on it.  No effect unless kernel == 2 routes a
+                               block to that encoder */
   uint64_t batch_blocks;    /* blocks per device batch; 0 = sized from free device memory */
   uint64_t slot_bytes;      /* test knob: device bytes reserved per block for coded data before the overflow path; 0 = auto
                                (coded bytes + 1/8 + 4096).  A block that does not fit is coded again with a worst-case slot:
@@ -312,12 +317,19 @@ typedef struct zpaqhip_compress_opts {
  * and the generic encoder), launches = encoder launches (one more per batch with an overflowed block), in_bytes =
  * plaintext, out_bytes = the stream, kernel_kind = 3 when a block ran on the lane-per-component encoder (opts.kernel
  * == 2; its time is part of kernel_ms, an overflowed block of it is coded again on the same encoder), 2 when one ran on
- * the window-parallel CM encoder, else 1. */
+ * the window-parallel CM encoder, else 1; concurrent = the blocks in flight (encoder waves with a block) of the call's
+ * largest launch of the lane-per-component encoder, 0 when no block ran there. */
 int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
                             const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
                             const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
                             uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
                             const zpaqhip_compress_opts *opts, zpaqhip_err *err);
+
+/* The lane-per-component encoder's LDS plan for the model of a block header (`hdr` as for zpaqhip_compress_blocks):
+ * *waves = the most encoder waves one compute unit holds for it, 1 to 4 (what opts.enc_waves == 0 uses at most), or 0 for
+ * a model that encoder does not take; *lds_bytes = the LDS of a workgroup of that many waves (the shared tables and, per
+ * wave, the model's ICM / ISSE tables and a fixed part), at most 163 840, or 0.  Host-side, no GPU needed. */
+int zpaqhip_enc_chain_plan(const uint8_t *hdr, size_t hdr_len, uint32_t *waves, uint32_t *lds_bytes, zpaqhip_err *err);
 
 /* ---- compression with a method: LibZPAQ.compressBlock (LibZPAQ.cs:296-323) with the pre-processing of LZBuffer and E8E9 ----
  * args are the nine numbers of an expanded method string as LibZPAQ.makeConfig reads them (LibZPAQ.cs:394-416; what

@@ -1,7 +1,7 @@
 """Compression rate of Context.compress_blocks (or, with --method, Context.compress_method) against the CPU stream writer.
 
     python3 tools/compress_rate.py [--blocks 256] [--block-size 4194304] [--kinds T,R] [--model l1] [--method M] [--bwt] [--sa | --ht]
-                                   [--level L [--analysis-only]] [--kernel 0] [--rounds 1] [--decode-kernel K] [--no-cpu]
+                                   [--level L [--analysis-only]] [--kernel 0] [--enc-waves 0] [--rounds 1] [--decode-kernel K] [--no-cpu]
 
 Per kind: plaintext MB/s from wall time, the time of each pass (zpaqhip_last_stats: init_ms = model pass, kernel_ms -
 init_ms = coder pass), and the CPU writer
@@ -26,7 +26,9 @@ Context.decompress(verify_sha1=True).  --kernel defaults to 2 here.
 --model takes any models name (l1, min, mid, max, ...), --method any expanded method string, modelled ones included.
 --kernel K[,K...]: the encoder choice (zpaqhip_compress_opts.kernel; 2 = lane-per-component encoder for chain models).
 Several values are run ALTERNATED inside one process on the same blocks, --rounds times each, one JSON line per run, and
-their outputs are compared with each other.  --decode-kernel K adds the kernel time of Context.decompress of the stream
+their outputs are compared with each other.  --enc-waves W[,W...] (with --model or --method): the lane-per-component encoder's
+waves per compute unit (zpaqhip_compress_opts.enc_waves; 0 automatic, 1 one wave per unit as before the waves existed), several
+values alternated in the same way, inside each --kernel value; "in_flight" is stats().concurrent.  --decode-kernel K adds the kernel time of Context.decompress of the stream
 with that decoder kernel (4 = zh_chain.hip, level walk at run time).  --no-cpu skips the CPU writer and with it every
 comparison with it (cpu16_MBps, identical, cpu16_ratio); the round trip and same_as_first remain.
 """
@@ -67,13 +69,13 @@ def run_method(ctx, a, kernels):
             for sa in (False, True) if a.sa or a.ht else (False,):
                 ctx.compress_method(a.method, blocks[:1], bwt=a.bwt, kernel=k, sa=sa and a.sa, ht=sa and a.ht)    # warm-up
         for rnd in range(a.rounds):
-            for k, sa in [(k, sa) for k in kernels for sa in ((False, True) if a.sa or a.ht else (False,))]:
+            for k, w, sa in [(k, w, sa) for k in kernels for w in a.waves for sa in ((False, True) if a.sa or a.ht else (False,))]:
                 t = time.perf_counter()
-                got = ctx.compress_method(a.method, blocks, bwt=a.bwt, kernel=k, sa=sa and a.sa, ht=sa and a.ht)
+                got = ctx.compress_method(a.method, blocks, bwt=a.bwt, kernel=k, sa=sa and a.sa, ht=sa and a.ht, enc_waves=w)
                 gpu_s = time.perf_counter() - t
                 st = ctx.stats()
                 row = {"method": a.method, "kind": kind, "blocks": a.blocks, "block_size": a.block_size, "kernel": k, "round": rnd,
-                       "ht" if a.ht else "sa": sa,
+                       "enc_waves": w, "in_flight": st.concurrent, "ht" if a.ht else "sa": sa,
                        "gpu_MBps": mb / gpu_s, "gpu_wall_s": gpu_s, "kernel_ms": st.kernel_ms, "pre_ms": st.init_ms,
                        "encoder_ms": st.kernel_ms - st.init_ms, "launches": st.launches, "kernel_kind": st.kernel_kind,
                        "ratio": len(got) / (mb * 1e6)}
@@ -146,11 +148,13 @@ def main():
     ap.add_argument("--level", default=None, help='numeric method "LB,R,t" (Context.compress_level)')
     ap.add_argument("--analysis-only", action="store_true", help="with --level: only the gap histogram, GPU against the host loop")
     ap.add_argument("--kernel", default=None, help="encoder choice(s), comma separated; several are alternated (default 0; 2 with --level)")
+    ap.add_argument("--enc-waves", default="0", help="chain encoder waves per compute unit, comma separated; several are alternated")
     ap.add_argument("--rounds", type=int, default=1, help="runs of each --kernel value")
     ap.add_argument("--decode-kernel", type=int, default=None, help="also time the decoder with this opts.kernel")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU writer")
     a = ap.parse_args()
     kernels = [int(k) for k in (a.kernel or ("2" if a.level else "0")).split(",")]
+    a.waves = [int(w) for w in a.enc_waves.split(",")]
     with z.Context(0) as ctx:
         if a.level:
             return run_level(ctx, a, kernels)
@@ -168,13 +172,13 @@ def main():
                 ctx.compress_blocks(a.model, blocks[:1], kernel=k)       # warm-up
             first = None
             for rnd in range(a.rounds):
-                for k in kernels:
+                for k, w in [(k, w) for k in kernels for w in a.waves]:
                     t = time.perf_counter()
-                    got = ctx.compress_blocks(a.model, blocks, kernel=k)
+                    got = ctx.compress_blocks(a.model, blocks, kernel=k, enc_waves=w)
                     gpu_s = time.perf_counter() - t
                     st = ctx.stats()
                     row = {"model": a.model, "kind": kind, "blocks": a.blocks, "block_size": a.block_size, "kernel": k, "round": rnd,
-                           "gpu_MBps": mb / gpu_s, "gpu_wall_s": gpu_s, "kernel_ms": st.kernel_ms, "model_pass_ms": st.init_ms,
+                           "enc_waves": w, "in_flight": st.concurrent, "gpu_MBps": mb / gpu_s, "gpu_wall_s": gpu_s, "kernel_ms": st.kernel_ms, "model_pass_ms": st.init_ms,
                            "coder_pass_ms": st.kernel_ms - st.init_ms, "launches": st.launches,
                            "kernel_kind": st.kernel_kind, "ratio": len(got) / (mb * 1e6)}
                     if want is not None:

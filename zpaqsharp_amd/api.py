@@ -139,6 +139,22 @@ def decompress_multi(devices: Sequence[int], stream, out_cap: Optional[int] = No
     return out[:n.value]
 
 
+def enc_chain_plan(model):
+    """zpaqhip_enc_chain_plan: (waves, lds_bytes) of the lane-per-component encoder for a model (a models name, a zpaql.Model
+    or header bytes): the most encoder waves one compute unit holds for it (1 to 4; what enc_waves=0 uses at most) and the
+    LDS of such a workgroup, or (0, 0) for a model that encoder does not take.  Host-side."""
+    from . import models
+    L = _lib.load()
+    if isinstance(model, str):
+        model = models.get(model)
+    hdr = _as_u8(model if isinstance(model, (bytes, bytearray, np.ndarray)) else model.header)
+    waves, lds, err = C.c_uint32(0), C.c_uint32(0), Err()
+    rc = L.zpaqhip_enc_chain_plan(hdr.ctypes.data, hdr.size, C.byref(waves), C.byref(lds), C.byref(err))
+    if rc:
+        _raise(err, rc)
+    return waves.value, lds.value
+
+
 def multi_trim() -> None:
     """zpaqhip_multi_trim: destroy the contexts decompress_multi keeps between calls."""
     _lib.load().zpaqhip_multi_trim()
@@ -200,7 +216,7 @@ class Context:
         return sq, st, dt, dt2k, ns
 
     def compress_blocks(self, model, blocks, *, pre=None, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 0,
-                        batch_blocks: int = 0, slot_bytes: int = 0) -> bytes:
+                        batch_blocks: int = 0, slot_bytes: int = 0, enc_waves: int = 0) -> bytes:
         """Compressor.startBlock .. endBlock for each block (LibZPAQ.cs:296-323 framing, one segment per block), coded on
         the GPU: the same bytes the CPU stream writer (synth.compress_block) produces.  `model` is a models name or a
         zpaql.Model.  A `+e8e9` model codes the forward E8E9 transform of each block; a `+lz77` model needs `pre`, the
@@ -208,7 +224,9 @@ class Context:
         on the window-parallel encoder, the rest on the one-lane generic encoder; 1 everything on the generic encoder;
         2 as 0, but models that fit the lane-per-component kernel (ICM / ISSE / MATCH / MIX chains of at most 64
         components and 4 mixers: min, mid, max, the method models) on the lane-per-component encoder
-        (stats().kernel_kind == 3)."""
+        (stats().kernel_kind == 3).  `enc_waves`: that encoder's waves (blocks in flight) per compute unit: 0 as many as
+        the model's LDS plan (enc_chain_plan), the blocks and device memory allow, up to four; 1 one; 2 to 4 a cap; more is
+        an error.  The bytes never depend on it; stats().concurrent tells the blocks in flight of the largest launch."""
         from . import e8e9, models
         m = models.get(model) if isinstance(model, str) else model
         plain = [_as_u8(b) for b in blocks]
@@ -222,7 +240,8 @@ class Context:
         elif m.pcomp_cmd.startswith("lz77"):
             raise ValueError("a +lz77 model needs the pre-processed blocks (pre=)")
         flags = (1 if sha1 else 0) | (2 if tag else 0)
-        return self._compress(m.header, m.pcomp or b"", coded, orig, filenames, flags, kernel, batch_blocks, slot_bytes)[0]
+        return self._compress(m.header, m.pcomp or b"", coded, orig, filenames, flags, kernel, batch_blocks, slot_bytes,
+                              enc_waves=enc_waves)[0]
 
     def _pre_blocks(self, fn, first, plain, cap: int, retry: bool = False) -> List[bytes]:
         """A zpaqhip_*_blocks entry point `fn` (`first` is its argument after the context: the method's args or the E8E9 flag) on
@@ -292,21 +311,22 @@ class Context:
                                 sum(mth.pre_bound(args, p.size) for p in plain))
 
     def compress_method(self, method: str, blocks, *, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 0,
-                        batch_blocks: int = 0, slot_bytes: int = 0, bwt: bool = False, sa: bool = False, ht: bool = False) -> bytes:
+                        batch_blocks: int = 0, slot_bytes: int = 0, bwt: bool = False, sa: bool = False, ht: bool = False,
+                        enc_waves: int = 0) -> bytes:
         """LibZPAQ.compressBlock(method) for each block (LibZPAQ.cs:296-323, one segment per block) on the GPU: the bytes
         tools.methods.compress_block writes.  Levels 0, 1 and 2 with or without E8E9, and with `bwt=True` level 3; the
         model of an n >= 1 method codes the pre-processed bytes on the encoders of compress_blocks (kernel, batch_blocks,
-        slot_bytes as there: kernel=2 puts the chain models of levels 3 and 4 on the lane-per-component encoder), an
+        slot_bytes, enc_waves as there: kernel=2 puts the chain models of levels 3 and 4 on the lane-per-component encoder), an
         n = 0 method stores them.  ValueError, before the device is touched, for level 3 without
         `bwt=True`, a level 2 `m` outside 1..64 and a block longer than 2^(args[0] + 20) bytes at level 1 or 2 (4096
         less at level 3).  `sa=True`: a level 1 / 2 method with args[5] - args[0] >= 21 gets the reference's suffix-array
         parse (lzsa_blocks; the bytes of tools.methods.compress_block(..., sa=True)); no effect on any other method.
         `ht=True`: one with args[5] - args[0] < 21 gets the reference's hash-table parse (lzht_blocks, with its refusals;
         the bytes of tools.methods.compress_block(..., ht=True)); no effect on any other method.  Both may be given."""
-        return self._compress_method(method, blocks, filenames, sha1, tag, kernel, batch_blocks, slot_bytes, bwt, sa, ht)[0]
+        return self._compress_method(method, blocks, filenames, sha1, tag, kernel, batch_blocks, slot_bytes, bwt, sa, ht, enc_waves)[0]
 
     def _compress_method(self, method: str, blocks, filenames, sha1: bool, tag: bool, kernel: int, batch_blocks: int,
-                         slot_bytes: int, bwt: bool, sa: bool = False, ht: bool = False):
+                         slot_bytes: int, bwt: bool, sa: bool = False, ht: bool = False, enc_waves: int = 0):
         """compress_method: (stream bytes, block offsets)."""
         from . import method as mth
         args = mth.parse_args(method)[1]
@@ -316,7 +336,7 @@ class Context:
         cap = sum(mth.pre_bound(args, p.size) for p in plain) + len(plain) * (len(model.header) + 2 * len(model.pcomp) + 4096) + 4096
         return self._compress(model.header, model.pcomp or b"", plain, None, filenames,
                               (1 if sha1 else 0) | (2 if tag else 0) | (4 if bwt else 0) | (8 if sa else 0) | (16 if ht else 0), kernel, batch_blocks, slot_bytes, out_cap=cap,
-                              args=args)[:2]
+                              args=args, enc_waves=enc_waves)[:2]
 
     def gap_hist_blocks(self, blocks) -> np.ndarray:
         """The repetition-gap histogram LibZPAQ.compressBlock takes of a block at levels 5..9 (LibZPAQ.cs:242-255), of each
@@ -338,7 +358,7 @@ class Context:
         return hist
 
     def compress_level(self, level: str, blocks, *, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 2,
-                       batch_blocks: int = 0, slot_bytes: int = 0, sa: bool = False, ht: bool = False) -> bytes:
+                       batch_blocks: int = 0, slot_bytes: int = 0, sa: bool = False, ht: bool = False, enc_waves: int = 0) -> bytes:
         """LibZPAQ.compressBlock with a numeric method "LB,R,t" (LibZPAQ.cs:124-323) for each block: `level` is expanded per
         block by method.expand_level (the block's length gives the x<N> argument; at levels 5..9 its gap histogram, taken by
         gap_hist_blocks, gives the periodic models), the blocks are grouped by the string they got, each group goes through
@@ -347,7 +367,7 @@ class Context:
         model.  `level_methods` keeps the expanded string of each block of the last call, `level_ms` its wall time in ms
         spent on the analysis and on the encoding.  `sa` is compress_method's: the LZ77 strings of levels 2, 3 and 4 then
         get the reference's suffix-array parse.  `ht` likewise: the LZ77 strings of level 1, and those levels 2 to 4 give
-        blocks of low redundancy, then get its hash-table parse."""
+        blocks of low redundancy, then get its hash-table parse.  `enc_waves` is compress_blocks'."""
         import time
 
         from . import method as mth
@@ -366,7 +386,7 @@ class Context:
         parts = [b""] * len(plain)
         for m, ids in groups.items():
             out, off = self._compress_method(m, [plain[i] for i in ids], None if filenames is None else [filenames[i] for i in ids],
-                                             sha1, tag, kernel, batch_blocks, slot_bytes, True, sa, ht)
+                                             sha1, tag, kernel, batch_blocks, slot_bytes, True, sa, ht, enc_waves)
             for j, i in enumerate(ids):
                 parts[i] = out[int(off[j]):int(off[j + 1])]
         self.level_methods = expanded
@@ -374,7 +394,7 @@ class Context:
         return b"".join(parts)
 
     def _compress(self, header: bytes, pcomp: bytes, coded, orig, filenames, flags: int, kernel: int, batch_blocks: int,
-                  slot_bytes: int, out_cap: Optional[int] = None, args: Optional[List[int]] = None):
+                  slot_bytes: int, out_cap: Optional[int] = None, args: Optional[List[int]] = None, enc_waves: int = 0):
         """zpaqhip_compress_blocks (zpaqhip_compress_method_blocks with `args`: `coded` is then the plaintext) on lists of
         blocks: (stream bytes, block offsets, status of the first call)."""
         n = len(coded)
@@ -387,7 +407,7 @@ class Context:
             names = (C.c_char_p * max(1, n))(*[(f.encode() if isinstance(f, str) else f) for f in filenames])
         o = CompressOpts()
         o.struct_size = C.sizeof(CompressOpts)
-        o.flags, o.kernel, o.batch_blocks, o.slot_bytes = flags, kernel, batch_blocks, slot_bytes
+        o.flags, o.kernel, o.batch_blocks, o.slot_bytes, o.enc_waves = flags, kernel, batch_blocks, slot_bytes, enc_waves
         hdr = _as_u8(header)
         pc = _as_u8(pcomp) if pcomp else None
         boffs = np.zeros(n + 1, np.uint64)

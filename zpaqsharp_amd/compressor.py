@@ -4,7 +4,8 @@ The input is cut into blocks of `block_size` bytes; each becomes one block with 
 Context.compress_blocks (a model; a model that needs a pre-processor other than E8E9 is refused there) or, with `method`,
 by Context.compress_method (LibZPAQ.compressBlock's pre-processing levels 0, 1 and 2, with or without E8E9, and with
 `bwt=True` level 3, the Burrows-Wheeler transform; without the keyword a level 3 method is refused).  `kernel` is the
-encoder choice of both (2: ICM / ISSE / MIX chain models on the lane-per-component encoder).  `sa=True` gives the LZ77
+encoder choice of both (2: ICM / ISSE / MIX chain models on the lane-per-component encoder) and `enc_waves` that encoder's
+waves per compute unit (0 automatic, 1 to 4; Context.compress_blocks).  `sa=True` gives the LZ77
 methods with args[5] - args[0] >= 21 the reference's suffix-array parse (Context.compress_method), with `method` and `level`;
 `ht=True` gives those with args[5] - args[0] < 21 its hash-table parse (args[3] = args[6] = 0 and the other limits of
 Context.lzht_blocks).
@@ -24,7 +25,7 @@ from .decompresser import Reader, Writer
 
 def compress(reader: Reader, writer: Writer, model="l1", block_size: Optional[int] = None, context: Optional[api.Context] = None,
              batch_blocks: int = 64, method: Optional[str] = None, bwt: bool = False, kernel: Optional[int] = None,
-             level: Optional[str] = None, sa: bool = False, ht: bool = False) -> None:
+             level: Optional[str] = None, sa: bool = False, ht: bool = False, enc_waves: int = 0) -> None:
     if level is not None:
         from . import method as mth
         if method is not None:
@@ -47,10 +48,12 @@ def compress(reader: Reader, writer: Writer, model="l1", block_size: Optional[in
         def flush():
             if blocks:
                 if level is not None:
-                    writer.write(ctx.compress_level(level, blocks, kernel=2 if kernel is None else kernel, sa=sa, ht=ht))
+                    writer.write(ctx.compress_level(level, blocks, kernel=2 if kernel is None else kernel, sa=sa, ht=ht,
+                                                      enc_waves=enc_waves))
                 else:
-                    writer.write(ctx.compress_blocks(model, blocks, kernel=kernel or 0) if method is None
-                                 else ctx.compress_method(method, blocks, bwt=bwt, kernel=kernel or 0, sa=sa, ht=ht))
+                    writer.write(ctx.compress_blocks(model, blocks, kernel=kernel or 0, enc_waves=enc_waves) if method is None
+                                 else ctx.compress_method(method, blocks, bwt=bwt, kernel=kernel or 0, sa=sa, ht=ht,
+                                                          enc_waves=enc_waves))
                 blocks.clear()
 
         # A Reader may return fewer bytes than asked before its end (Reader.cs:14-25): only an empty read ends the input,

@@ -130,6 +130,18 @@ EncKernel route_encode(const ZhModel &m, const zpaqhip_compress_opts &o, uint64_
   return EncKernel::Generic;
 }
 
+// The chain encoder's LDS plan for a model: its ICM / ISSE units, and the most waves of one workgroup (one per SIMD) whose
+// regions fit next to the shared tables (zh_enc.h).  Models outside the chain family get no wave.
+struct ChainPlan { uint32_t waves = 0, units = 0, lds_bytes = 0; };
+ChainPlan plan_chain(const ZhModel &m) {
+  ChainPlan p;
+  if (!chain_family(m.kind & 255u)) return p;
+  for (uint32_t i = 0; i < m.n; ++i) p.units += m.comp[i].type == ZH_ICM ? 1u : m.comp[i].type == ZH_ISSE ? 2u : 0u;
+  p.waves = zh_enc_chain_fit(p.units);
+  p.lds_bytes = p.waves ? ZH_ENC_CHAIN_TABLES + p.waves * zh_enc_chain_stride(p.units) : 0;
+  return p;
+}
+
 uint64_t auto_slot(uint64_t coded) { return coded + coded / 8 + 4096; }
 uint64_t worst_slot(uint64_t coded) { return 16 * coded + 4096; }    // 2 bytes per coded bit, plus the end of segment
 
@@ -182,7 +194,8 @@ struct Call {
   zpaqhip_stats st{};
   uint64_t pos = 0;                       // bytes of the stream so far
   bool any_cm = false, any_chain = false;
-  int cus = 0;                            // compute units: the chain encoder's LDS lets one of its waves live on each
+  int cus = 0;                            // compute units: the chain encoder's LDS lets one of its workgroups live on each
+  ChainPlan chain;                        // ... with this many waves at most
 
   bool want_sha() const { return (o.flags & 1) != 0; }
   uint64_t in_len(size_t i) const { return in_off[i + 1] - in_off[i]; }
@@ -227,6 +240,7 @@ int Call::open(zpaqhip_ctx *ctx) {
   HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, v.device));
   HIPCHK(device_budget(v.mem_share, 0, &budget));
   arena_stride = align_up(M.arena_bytes, 256);
+  chain = plan_chain(M);
   return ZPAQHIP_OK;
 }
 
@@ -308,7 +322,7 @@ int Call::encode(const Batch &B, EncRun &r) {
   L.budget = 1ull << 32;
   L.limit = (uint32_t)M.comp[0].arg[1] * 4;
   L.wmask = wmask;
-  uint32_t grid = 0, chain_grid = 0;
+  uint32_t grid = 0, chain_grid = 0, chain_waves = 1;
   if (r.n_cm) {
     HIPCHK(r.la.alloc(r.scr_total * 4));
     HIPCHK(r.lb.alloc(r.scr_total * 4));
@@ -329,10 +343,18 @@ int Call::encode(const Batch &B, EncRun &r) {
   }
   if (r.n_chain) {
     // (half the budget for these arenas: a batch's own buffers are planned within the other half, and max's 22 tables
-    // would otherwise leave most compute units without a wave)
+    // would otherwise leave most compute units without a wave).  The blocks spread over the compute units first; only a
+    // launch with more blocks than units puts a second, third and fourth wave into a workgroup, as many as the model's
+    // LDS plan, opts.enc_waves and the blocks per workgroup allow; where memory is short of an arena slot per wave the
+    // waves go before the workgroups.
     const uint64_t chain_mem = std::max<uint64_t>(1, (budget / 2) / arena_stride);
-    chain_grid = (uint32_t)std::min<uint64_t>({(uint64_t)r.n_chain, (uint64_t)std::max(1, cus), chain_mem});
-    HIPCHK(r.chain_arena.alloc(chain_grid * arena_stride));
+    chain_grid = (uint32_t)std::min<uint64_t>((uint64_t)r.n_chain, (uint64_t)std::max(1, cus));
+    const uint32_t cap = o.enc_waves ? std::min(o.enc_waves, chain.waves) : chain.waves;
+    chain_waves = (uint32_t)std::min<uint64_t>(std::max(1u, cap), (r.n_chain + chain_grid - 1) / chain_grid);
+    while (chain_waves > 1 && (uint64_t)chain_grid * chain_waves > chain_mem) --chain_waves;
+    chain_grid = (uint32_t)std::min<uint64_t>(chain_grid, chain_mem);
+    HIPCHK(r.chain_arena.alloc((uint64_t)chain_grid * chain_waves * arena_stride));
+    st.concurrent = std::max(st.concurrent, (uint32_t)std::min<uint64_t>(r.n_chain, (uint64_t)chain_grid * chain_waves));
   }
 
   HIPCHK(hipEventRecord(v.ev0, v.stream));
@@ -346,6 +368,7 @@ int Call::encode(const Batch &B, EncRun &r) {
   if (r.n_chain) {
     L.blocks = r.d_desc.as<ZhEncBlock>() + r.n_cm; L.res = r.d_res.as<ZhEncResult>() + r.n_cm; L.n_blocks = (uint32_t)r.n_chain;
     L.queue = r.queue.as<uint32_t>() + 16; L.arena = r.chain_arena.as<uint8_t>();
+    L.waves = chain_waves; L.lds_pool = chain.units * 1024u; L.lds_stride = zh_enc_chain_stride(chain.units);
     HIPCHK(zh_launch_enc_chain(&L, chain_grid, v.stream));
     st.launches += 1;
   }
@@ -467,6 +490,21 @@ int Call::frame(Batch &B) {
 
 }  // namespace
 
+extern "C" int zpaqhip_enc_chain_plan(const uint8_t *hdr, size_t hdr_len, uint32_t *waves, uint32_t *lds_bytes, zpaqhip_err *err) {
+  if (!hdr || !waves || !lds_bytes) {
+    set_err(err, ZPAQHIP_E_ARG, -1, -1);
+    return ZPAQHIP_E_ARG;
+  }
+  ZhModel m;
+  std::vector<uint8_t> code;
+  const int rc = build_model(hdr, hdr_len, m, code, err);
+  if (rc) return rc;
+  const ChainPlan p = plan_chain(m);
+  *waves = p.waves;
+  *lds_bytes = p.lds_bytes;
+  return ZPAQHIP_OK;
+}
+
 extern "C" int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
                                        const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
                                        const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
@@ -487,6 +525,10 @@ int zh::compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, cons
     return ZPAQHIP_E_ARG;
   }
   *out_len = 0;
+  if (resolve_compress_opts(opts).enc_waves > ZH_ENC_CHAIN_MAX_WAVES) {
+    set_err(err, ZPAQHIP_E_ARG, -1, -1, "enc_waves is 0 (automatic) or 1 to 4");
+    return ZPAQHIP_E_ARG;
+  }
   for (size_t i = 0; i < n_blocks; ++i)
     if (in_off[i + 1] < in_off[i] || (orig && orig_off[i + 1] < orig_off[i]) || (!in && in_off[i + 1] > in_off[i])) {
       set_err(err, ZPAQHIP_E_ARG, (int)i, -1, "block offsets must not decrease");

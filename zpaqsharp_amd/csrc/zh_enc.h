@@ -1,5 +1,5 @@
 // zh_enc.h — structures shared by the host side of zpaqhip_compress_blocks (zh_compress.cpp) and the encoder kernels
-// (zh_enc_generic.hip, zh_enc_cm.hip).
+// (zh_enc_generic.hip, zh_enc_cm.hip, zh_enc_chain.hip).
 //
 // A block's "coded sequence" is what Encoder.compress sees (Compressor.cs:156-222): the post-processor prefix
 // (PASS: 0; PROG: 1, length lo, length hi, program) followed by the block's bytes.  The host lays the coded sequences of
@@ -12,6 +12,19 @@
 #define ZH_ENC_CM_MAX_N (1u << 28)   // zh_enc_cm packs position << 4 | nibble into 32 bits
 #define ZH_ENC_CM_KEYS 4096u         // (window bin, high nibble) keys of the second-nibble chains; bin = c_prev & wmask
 #define ZH_ENC_CM_CHAINS (256u + ZH_ENC_CM_KEYS)
+
+// zh_enc_chain's LDS: one ZhTables for the workgroup, then a region per wave: the model's ICM / ISSE pool (`units` KiB, a
+// unit is ZhComp::small_unit's 256 words: ICM 1, ISSE 2), then what the kernel keeps per block at fixed sizes (its EncWaveLds).
+#define ZH_ENC_CHAIN_LDS 163840u
+#define ZH_ENC_CHAIN_TABLES 79872u       // sizeof(ZhTables)
+#define ZH_ENC_CHAIN_WAVE_FIXED 13648u   // sizeof(EncWaveLds) (both asserted in zh_enc_chain.hip)
+#define ZH_ENC_CHAIN_MAX_WAVES 4u        // one per SIMD
+inline uint32_t zh_enc_chain_stride(uint32_t units) { return units * 1024u + ZH_ENC_CHAIN_WAVE_FIXED; }
+// waves of one workgroup whose regions fit (0: not even one)
+inline uint32_t zh_enc_chain_fit(uint32_t units) {
+  const uint32_t w = (ZH_ENC_CHAIN_LDS - ZH_ENC_CHAIN_TABLES) / zh_enc_chain_stride(units);
+  return w < ZH_ENC_CHAIN_MAX_WAVES ? w : ZH_ENC_CHAIN_MAX_WAVES;
+}
 
 struct ZhEncBlock {
   uint64_t in_off;         // coded sequence in ZhEncLaunch::in
@@ -33,7 +46,7 @@ struct ZhEncLaunch {
   ZhEncResult *res;
   uint8_t *slots;
   uint32_t n_blocks;
-  uint32_t pad0;
+  uint32_t waves;          // zh_enc_chain: encoder waves per workgroup (block size / 64); arena slot (blockIdx * waves + wave)
   // zh_enc_generic
   const ZhModel *model;
   const uint8_t *code;
@@ -42,6 +55,9 @@ struct ZhEncLaunch {
   uint64_t arena_stride;
   uint32_t *queue;
   uint64_t budget;
+  // zh_enc_chain: bytes from one wave's LDS region to the next, and of the ICM / ISSE pool at its start
+  uint32_t lds_stride;
+  uint32_t lds_pool;
   // zh_enc_cm: the CM's limit (arg[1] * 4), which bits of the previous byte pick its 512-entry window, and scratch
   uint32_t limit;
   uint32_t wmask;

@@ -8,6 +8,12 @@
 // through zh_dev.h's OutBuf into the block's slot (counted past the slot, never written past it).  No P scratch, no second
 // pass.  The file repeats what it needs of zh_chain.hip (the decoders stay byte for byte what they were).
 //
+// A workgroup holds up to four such wavefronts, one per SIMD (ZhEncLaunch::waves is the launch's block size / 64): they share
+// the model-independent tables in LDS and nothing else.  Each has its own LDS region (the model's ICM / ISSE pool, then
+// EncWaveLds; zh_enc.h's layout), its own arena slot and pulls its own blocks, so the waves of a workgroup run different
+// numbers of blocks: the ONE workgroup barrier of the kernel follows the table fill, before the loop, and inside the loop
+// a wave orders its lanes' stores and loads against each other with wave_sync() only.
+//
 // What an encoder knows and a decoder does not, as used here:
 //  * the bit: update() takes y from the coded sequence, nothing is fetched two ways or selected;
 //  * the byte: both nibbles' contexts (h[i] + 16 * c8, h[i] ^ hmap4) are known when the byte starts, so the hash rows / CM
@@ -32,15 +38,12 @@ using namespace zhdev;
 
 namespace {
 
-constexpr int kSmallWords = 16384;        // LDS pool for ICM (256 words) / ISSE (512 words) tables
 constexpr int kHWords = 512;              // HCOMP H kept in LDS when 2^hh <= 512 (the method models have hh = 9)
 constexpr int kMBytes = 4096;             // HCOMP M kept in LDS when 2^hm <= 4096
 constexpr int kMaxMix = 4;
 constexpr int kCodeBytes = 2048;          // HCOMP program window kept in LDS when it fits
 
-struct alignas(16) EncChainLds {
-  ZhTables t;
-  uint32_t small[kSmallWords];
+struct alignas(16) EncWaveLds {           // what a wave keeps per block, behind its ICM (256 words) / ISSE (512 words) pool
   uint8_t slot[64][64];                   // per-lane nibble cache (hash row or CM line)
   uint32_t dummy[64];                     // per-lane sink for the stores of lanes a branch-free step does not concern
   uint32_t hreg[kHWords];
@@ -49,7 +52,21 @@ struct alignas(16) EncChainLds {
   uint8_t code[kCodeBytes];
   Vm hz;
 };
-static_assert(sizeof(EncChainLds) <= 163840, "LDS budget");
+struct alignas(16) EncChainLds {
+  ZhTables t;                             // one copy for the workgroup, read-only after the fill
+  uint8_t waves[ZH_ENC_CHAIN_LDS - sizeof(ZhTables)];   // region w at w * ZhEncLaunch::lds_stride: pool, then EncWaveLds
+};
+static_assert(sizeof(EncWaveLds) == ZH_ENC_CHAIN_WAVE_FIXED, "zh_enc.h plans with this size");
+static_assert(sizeof(ZhTables) == ZH_ENC_CHAIN_TABLES && sizeof(ZhTables) % 16 == 0, "zh_enc.h plans with this size");
+static_assert(sizeof(EncChainLds) == ZH_ENC_CHAIN_LDS && ZH_ENC_CHAIN_LDS <= 163840, "LDS budget");
+static_assert(ZH_ENC_CHAIN_TABLES + 64 * 1024 + ZH_ENC_CHAIN_WAVE_FIXED <= ZH_ENC_CHAIN_LDS, "the largest chain (64 units) fits one wave");
+
+// Orders what the lanes of THIS wave stored (LDS and the arena in global memory) before what they load next: the waits of a
+// workgroup fence and a scheduling fence, no s_barrier (the other waves of the workgroup are at other blocks).
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+}
 
 __device__ __forceinline__ int clampk(int x, int lo, int hi) { return x < lo ? lo : x > hi ? hi : x; }
 typedef __attribute__((address_space(3))) uint8_t *lds_u8_p;
@@ -110,18 +127,23 @@ __device__ __forceinline__ void encode(Enc &e, OutBuf &o, uint32_t y, uint32_t p
 
 }  // namespace
 
-extern "C" __global__ __launch_bounds__(64) void zh_enc_chain(ZhEncLaunch L) {
-  __shared__ EncChainLds S;
-  const uint32_t lane = threadIdx.x;
+extern "C" __global__ __launch_bounds__(256) void zh_enc_chain(ZhEncLaunch L) {
+  __shared__ EncChainLds T;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = uni(threadIdx.x >> 6);
 
-  {  // model-independent tables -> LDS
+  {  // model-independent tables -> LDS, by every wave of the workgroup
     const uint4 *src = reinterpret_cast<const uint4 *>(L.tables);
-    uint4 *dst = reinterpret_cast<uint4 *>(&S.t);
-    for (uint32_t i = lane; i < sizeof(ZhTables) / 16; i += 64) dst[i] = src[i];
+    uint4 *dst = reinterpret_cast<uint4 *>(&T.t);
+    for (uint32_t i = threadIdx.x; i < sizeof(ZhTables) / 16; i += blockDim.x) dst[i] = src[i];
   }
-  __syncthreads();
+  __syncthreads();                                     // the kernel's only workgroup barrier: every wave reaches it
 
-  uint8_t *slot_mem = L.arena + (uint64_t)blockIdx.x * L.arena_stride;
+  // this wave's LDS region and arena slot
+  uint8_t *const region = T.waves + wave * uni(L.lds_stride);
+  uint32_t *const small = reinterpret_cast<uint32_t *>(region);
+  EncWaveLds &S = *reinterpret_cast<EncWaveLds *>(region + uni(L.lds_pool));
+  uint8_t *slot_mem = L.arena + ((uint64_t)blockIdx.x * uni(L.waves) + wave) * L.arena_stride;
   uint8_t *myslot = &S.slot[lane][0];
   const ZhModel *M = L.model;
   const uint32_t n = uni(M->n), depth = uni(M->depth);
@@ -131,7 +153,7 @@ extern "C" __global__ __launch_bounds__(64) void zh_enc_chain(ZhEncLaunch L) {
     uint32_t bi = 0;
     if (lane == 0) bi = atomicAdd(L.queue, 1u);
     bi = uni((uint32_t)__shfl((int)bi, 0));
-    if (bi >= L.n_blocks) break;                       // every wave reaches this exit
+    if (bi >= L.n_blocks) break;                       // every wave leaves here, each at its own time
 
     const ZhEncBlock *bdp = &L.blocks[bi];
     const uint64_t b_n = uni64(bdp->n);
@@ -157,10 +179,10 @@ extern "C" __global__ __launch_bounds__(64) void zh_enc_chain(ZhEncLaunch L) {
         for (uint64_t k = lane; k < cmb / 16; k += 64) {
           const uint32_t j = (uint32_t)(k * 4) & 31;
           uint4 v;
-          v.x = (uint32_t)S.t.squash[(j + 0) * 64 - 992 + 2048] << 17 | start;
-          v.y = (uint32_t)S.t.squash[(j + 1) * 64 - 992 + 2048] << 17 | start;
-          v.z = (uint32_t)S.t.squash[(j + 2) * 64 - 992 + 2048] << 17 | start;
-          v.w = (uint32_t)S.t.squash[(j + 3) * 64 - 992 + 2048] << 17 | start;
+          v.x = (uint32_t)T.t.squash[(j + 0) * 64 - 992 + 2048] << 17 | start;
+          v.y = (uint32_t)T.t.squash[(j + 1) * 64 - 992 + 2048] << 17 | start;
+          v.z = (uint32_t)T.t.squash[(j + 2) * 64 - 992 + 2048] << 17 | start;
+          v.w = (uint32_t)T.t.squash[(j + 3) * 64 - 992 + 2048] << 17 | start;
           q[k] = v;
         }
       }
@@ -178,7 +200,7 @@ extern "C" __global__ __launch_bounds__(64) void zh_enc_chain(ZhEncLaunch L) {
       for (uint32_t i = lane; i < kMBytes / 4; i += 64) reinterpret_cast<uint32_t *>(S.mreg)[i] = 0;
     }
 
-    __syncthreads();
+    wave_sync();
     // ---- this lane's component
     Lane me;
     {
@@ -199,16 +221,16 @@ extern "C" __global__ __launch_bounds__(64) void zh_enc_chain(ZhEncLaunch L) {
         case ZH_ICM:
           me.limit = 1023;
           for (uint32_t j = 0; j < 256; ++j) {
-            const uint32_t n0 = S.t.ns[j * 4 + 2], n1 = S.t.ns[j * 4 + 3];
-            S.small[me.sbase + j] = ((n1 * 2 + 1) << 22) / (n0 + n1 + 1);                 // StateTable.cminit
+            const uint32_t n0 = T.t.ns[j * 4 + 2], n1 = T.t.ns[j * 4 + 3];
+            small[me.sbase + j] = ((n1 * 2 + 1) << 22) / (n0 + n1 + 1);                 // StateTable.cminit
           }
           break;
         case ZH_ISSE:
           for (uint32_t j = 0; j < 256; ++j) {
-            const uint32_t n0 = S.t.ns[j * 4 + 2], n1 = S.t.ns[j * 4 + 3];
+            const uint32_t n0 = T.t.ns[j * 4 + 2], n1 = T.t.ns[j * 4 + 3];
             const uint32_t ci = ((n1 * 2 + 1) << 22) / (n0 + n1 + 1);
-            S.small[me.sbase + 2 * j] = 1u << 15;
-            S.small[me.sbase + 2 * j + 1] = (uint32_t)clamp512k(S.t.stretch[ci >> 8] * 1024);
+            small[me.sbase + 2 * j] = 1u << 15;
+            small[me.sbase + 2 * j + 1] = (uint32_t)clamp512k(T.t.stretch[ci >> 8] * 1024);
           }
           break;
         case ZH_MATCH: (slot_mem + me.hto)[0] = 1; break;
@@ -257,14 +279,14 @@ extern "C" __global__ __launch_bounds__(64) void zh_enc_chain(ZhEncLaunch L) {
       if (cnt > 1) dsc |= 7u << 12;
       if (lane == lv) lvl_desc = dsc;
     }
-    __syncthreads();
+    wave_sync();
 
     // per-lane constants of the branch-free ICM / ISSE steps
     const bool is_icm = me.type == ZH_ICM, is_isse = me.type == ZH_ISSE, is_ii = is_icm || is_isse, is_match = me.type == ZH_MATCH;
     const bool is_cm = me.type == ZH_CM;
-    const uint32_t ii_tab = lds_off(&S.small[0]) + me.sbase * 4;
+    const uint32_t ii_tab = lds_off(&small[0]) + me.sbase * 4;
     const uint32_t ii_sh = is_isse ? 3u : 2u;
-    const uint32_t slot_off = lds_off(myslot), dummy_off = lds_off(&S.dummy[lane]), ns_off = lds_off(&S.t.ns[0]);
+    const uint32_t slot_off = lds_off(myslot), dummy_off = lds_off(&S.dummy[lane]), ns_off = lds_off(&T.t.ns[0]);
     int pm0 = 0, pm1 = 0;                                             // MATCH: stretch of +-dt2k[len] for this byte
 
     // HCOMP machine (ZPAQL.cs:1010-1026): H and M in LDS when they fit
@@ -297,7 +319,7 @@ extern "C" __global__ __launch_bounds__(64) void zh_enc_chain(ZhEncLaunch L) {
     OutBuf ob;
     ob.base = L.slots + uni64(bdp->slot_off); ob.cap = uni64(bdp->slot_cap); ob.len = 0; ob.stored = 0; ob.word = 0; ob.park = 0;
     out_room(ob);
-    __syncthreads();
+    wave_sync();
 
     // ---- the rows of a nibble (Predictor.find, Predictor.cs:550-567; a CM's 64-byte line), in three steps so that the
     // loads can be put in flight long before they are used: write the lane's row / line back, request the rows of the
@@ -402,8 +424,8 @@ extern "C" __global__ __launch_bounds__(64) void zh_enc_chain(ZhEncLaunch L) {
           if (is_cm) {
             me.cxt = (me.h ^ hmap4) & 15;
             pv = reinterpret_cast<const uint32_t *>(myslot)[me.cxt];
-            me.p = S.t.stretch[pv >> 17];
-            pdt = S.t.dt[pv & 0x3ff];
+            me.p = T.t.stretch[pv >> 17];
+            pdt = T.t.dt[pv & 0x3ff];
           }
           uint32_t ii_a = 0;
           {
@@ -414,7 +436,7 @@ extern "C" __global__ __launch_bounds__(64) void zh_enc_chain(ZhEncLaunch L) {
             ii_a = ii_tab + (st << ii_sh);
             const uint32_t w_x = *(lds_u32_p)ii_a, w_y = *(lds_u32_p)(ii_a + 4);
             const uint32_t nsv = *(lds_u16_p)(ns_off + st * 4);               // next(state, 0) | next(state, 1) << 8
-            const int stv = S.t.stretch[is_icm ? w_x >> 8 : 0];
+            const int stv = T.t.stretch[is_icm ? w_x >> 8 : 0];
             if (is_ii) { me.cxt = st; pns = nsv; pv = w_x; me.w0 = (int)w_x; me.w1 = (int)w_y; }
             if (is_icm) me.p = stv;
           }
@@ -455,7 +477,7 @@ extern "C" __global__ __launch_bounds__(64) void zh_enc_chain(ZhEncLaunch L) {
                 me.cxt += (uint32_t)pq;
                 const uint32_t *cm = reinterpret_cast<const uint32_t *>(slot_mem + me.cmo);
                 const uint32_t e0 = cm[me.cxt & me.cm_mask], e1 = cm[(me.cxt + 1) & me.cm_mask];
-                me.p = S.t.stretch[((e0 >> 10) * (uint32_t)(64 - wt) + (e1 >> 10) * (uint32_t)wt) >> 13];
+                me.p = T.t.stretch[((e0 >> 10) * (uint32_t)(64 - wt) + (e1 >> 10) * (uint32_t)wt) >> 13];
                 me.cxt += (uint32_t)(wt >> 5);
                 me.w0 = (int)((wt >> 5) ? e1 : e0);    // the entry train() will update
               }
@@ -477,7 +499,7 @@ extern "C" __global__ __launch_bounds__(64) void zh_enc_chain(ZhEncLaunch L) {
                     me.cxt += (uint32_t)pq;
                     const uint32_t *cm = reinterpret_cast<const uint32_t *>(slot_mem + me.cmo);
                     const uint32_t e0 = cm[me.cxt & me.cm_mask], e1 = cm[(me.cxt + 1) & me.cm_mask];
-                    me.p = S.t.stretch[((e0 >> 10) * (uint32_t)(64 - wt) + (e1 >> 10) * (uint32_t)wt) >> 13];
+                    me.p = T.t.stretch[((e0 >> 10) * (uint32_t)(64 - wt) + (e1 >> 10) * (uint32_t)wt) >> 13];
                     me.cxt += (uint32_t)(wt >> 5);
                     me.w0 = (int)((wt >> 5) ? e1 : e0);
                     break;
@@ -499,7 +521,7 @@ extern "C" __global__ __launch_bounds__(64) void zh_enc_chain(ZhEncLaunch L) {
             }
           }
           // ================= code the bit =================
-          const int sqp = (int)S.t.squash[me.p + 2048];          // squash(p[i]) of every lane, one LDS pass
+          const int sqp = (int)T.t.squash[me.p + 2048];          // squash(p[i]) of every lane, one LDS pass
           const uint32_t pr = rdlane((uint32_t)sqp, n - 1);
           encode(e, ob, y, (pr * 2 + 1) << 16, lane);
 
@@ -524,7 +546,7 @@ extern "C" __global__ __launch_bounds__(64) void zh_enc_chain(ZhEncLaunch L) {
             const uint32_t v = (uint32_t)me.w0, cnt_ = v & 0x3ff;
             const int er = ey - (int)(v >> 17);
             reinterpret_cast<uint32_t *>(slot_mem + me.cmo)[me.cxt & me.cm_mask] =
-                v + (((uint32_t)er * (uint32_t)S.t.dt[cnt_]) & 0xFFFFFC00u) + (cnt_ < me.limit);
+                v + (((uint32_t)er * (uint32_t)T.t.dt[cnt_]) & 0xFFFFFC00u) + (cnt_ < me.limit);
           }
           {                                              // ICM / ISSE: all lanes, stores of unconcerned lanes go to their dummy cell
             *(lds_u8_p)(is_ii ? slot_off + hm15 : dummy_off) = (uint8_t)(pns >> (y * 8));   // StateTable.next
@@ -603,9 +625,9 @@ extern "C" __global__ __launch_bounds__(64) void zh_enc_chain(ZhEncLaunch L) {
           }
           if (is_match) me.mbyte = (slot_mem + me.hto)[(me.limit - me.b) & me.ht_mask];
           {                                              // the two predictions a match of this length can make (Predictor.cs:273-287)
-            const int dk = S.t.dt2k[is_match ? me.a : 0];
-            pm0 = S.t.stretch[dk & 32767];
-            pm1 = S.t.stretch[(-dk) & 32767];
+            const int dk = T.t.dt2k[is_match ? me.a : 0];
+            pm0 = T.t.stretch[dk & 32767];
+            pm1 = T.t.stretch[(-dk) & 32767];
           }
           rows_finish(1u, a0, a1, a2, a3, ah);
         }
@@ -620,11 +642,16 @@ extern "C" __global__ __launch_bounds__(64) void zh_enc_chain(ZhEncLaunch L) {
       r.len = ob.len; r.status = status; r.overflow = ob.len > ob.cap;
       L.res[bi] = r;
     }
-    __syncthreads();
+    wave_sync();
   }
 }
 
 extern "C" hipError_t zh_launch_enc_chain(const ZhEncLaunch *L, uint32_t grid, hipStream_t stream) {
-  hipLaunchKernelGGL(zh_enc_chain, dim3(grid), dim3(64), 0, stream, *L);
+  // the regions of the launch's waves lie inside the kernel's LDS block, and the pool in front of each is whole units
+  if (L->waves < 1 || L->waves > ZH_ENC_CHAIN_MAX_WAVES || L->lds_pool % 1024 || L->lds_stride % 16 ||
+      L->lds_stride < L->lds_pool + ZH_ENC_CHAIN_WAVE_FIXED ||
+      (uint64_t)L->waves * L->lds_stride > ZH_ENC_CHAIN_LDS - ZH_ENC_CHAIN_TABLES)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(zh_enc_chain, dim3(grid), dim3(64 * L->waves), 0, stream, *L);
   return hipGetLastError();
 }

@@ -137,7 +137,17 @@ typedef struct zpaqhip_opts {
   uint64_t queue_blocks;      /* zpaqhip_decompress_multi: blocks per pull from the shared work queue; 0 = default: 256 (one block per
                                  CU of the device that takes the chunk; 512 where every block is a single-CM one), but no more than a
                                  quarter of a device's share of the blocks, so that every device pulls at least four times */
-  uint64_t reserved[2];
+  uint64_t dec_waves;         /* zh_chain with the level walk at run time (kernel 0's "other models", every chain model with kernel 4):
+                                 decoder waves (blocks in flight) per compute unit.  0 or 1: one, as before the field existed (it
+                                 was reserved[0]).  2 to 4: a launch of more blocks than the device has compute units puts up to
+                                 that many waves, one per SIMD, on a unit, as many as the LDS plan of the launch's models allows
+                                 (zpaqhip_dec_chain_plan; the smallest of them), and as the blocks, device memory and
+                                 max_concurrent call for; above 4 is taken as 4.  The plaintext and the per-segment results never
+                                 depend on it; stats.concurrent then counts the blocks in flight (waves with a block).  No effect
+                                 on blocks of any other kernel, nor with kernel 3 or 5, nor in the diagnostic build with in-kernel
+                                 stamps (ZPAQHIP_PROF set).  The whole-stream forms then make batches of at least 256 x dec_waves
+                                 blocks of such models instead of 256.  An opt-in until it becomes the default */
+  uint64_t reserved[1];       /* must be 0: the library uses the word for calls of its own */
 } zpaqhip_opts;
 
 /* Timing / accounting of the last decode call on a context (the reference's
@@ -151,7 +161,7 @@ typedef struct zpaqhip_stats {
   uint64_t out_bytes;         /* plaintext bytes produced */
   uint64_t model_bytes;       /* per-block model state (sum over decoded blocks) */
   uint32_t launches;          /* decode kernel launches */
-  uint32_t concurrent;        /* blocks in flight per launch */
+  uint32_t concurrent;        /* blocks in flight per launch (with opts.dec_waves >= 2: the waves with a block of the largest launch) */
   uint32_t kernel_kind;       /* most specialised kernel used: 1 generic, 2 single-CM lanes, 3 lane-per-component */
   uint32_t reserved;
 } zpaqhip_stats;
@@ -258,6 +268,12 @@ int zpaqhip_decode_blocks_device(zpaqhip_ctx *ctx, const void *d_in, const uint8
                                  void *d_out, const uint64_t *out_off, const uint64_t *out_cap,
                                  zpaqhip_seg_result *results,
                                  const zpaqhip_opts *opts, void *hip_stream, zpaqhip_err *err);
+
+/* zh_chain's LDS plan for the model of a block header (`hdr` as the stream carries it: hsize lo, hsize hi, hh hm ph pm n,
+ * components, 0, HCOMP, 0): *waves = the most decoder waves one compute unit holds for it, 1 to 4 (what opts.dec_waves uses
+ * at most), or 0 for a model that kernel does not take; *lds_bytes = the LDS of a workgroup of that many waves (the shared
+ * tables and, per wave, the model's ICM / ISSE tables and a fixed part), at most 163 840, or 0.  Host-side, no GPU needed. */
+int zpaqhip_dec_chain_plan(const uint8_t *hdr, size_t hdr_len, uint32_t *waves, uint32_t *lds_bytes, zpaqhip_err *err);
 
 /* Device-side copies of the model-independent tables, for parity tests
  * (Predictor.cs:48-79 squash/stretch/dt/dt2k, StateTable.cs:21-149).

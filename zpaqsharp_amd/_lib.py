@@ -42,7 +42,7 @@ class SegResult(C.Structure):
 class Opts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("verify_sha1", C.c_uint32), ("max_concurrent", C.c_uint32),
                 ("kernel", C.c_uint32), ("zpaql_budget", C.c_uint64), ("batch_blocks", C.c_uint64),
-                ("queue_blocks", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+                ("queue_blocks", C.c_uint64), ("dec_waves", C.c_uint64), ("reserved", C.c_uint64 * 1)]
 
 
 class Stats(C.Structure):
@@ -66,7 +66,8 @@ SYMBOLS = ("zpaqhip_version", "zpaqhip_strerror", "zpaqhip_device_count", "zpaqh
            "zpaqhip_decompress_segments", "zpaqhip_decompress_cb", "zpaqhip_decode_blocks_device", "zpaqhip_read_device_tables",
            "zpaqhip_block_pcomp", "zpaqhip_decompress_multi", "zpaqhip_decompress_multi_stats", "zpaqhip_block_costs", "zpaqhip_multi_trim",
            "zpaqhip_compress_blocks", "zpaqhip_preprocess_blocks", "zpaqhip_compress_method_blocks", "zpaqhip_bwt_blocks",
-           "zpaqhip_gap_hist_blocks", "zpaqhip_lzsa_blocks", "zpaqhip_lzht_blocks", "zpaqhip_enc_chain_plan")
+           "zpaqhip_gap_hist_blocks", "zpaqhip_lzsa_blocks", "zpaqhip_lzht_blocks", "zpaqhip_enc_chain_plan",
+           "zpaqhip_dec_chain_plan")
 
 _lib = None
 
@@ -121,5 +122,6 @@ def load():
                                                  C.POINTER(CompressOpts), errp]
     L.zpaqhip_gap_hist_blocks.argtypes = [vp, vp, vp, sz, vp, errp]
     L.zpaqhip_enc_chain_plan.argtypes = [vp, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), errp]
+    L.zpaqhip_dec_chain_plan.argtypes = [vp, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), errp]
     _lib = L
     return L

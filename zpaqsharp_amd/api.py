@@ -139,20 +139,30 @@ def decompress_multi(devices: Sequence[int], stream, out_cap: Optional[int] = No
     return out[:n.value]
 
 
-def enc_chain_plan(model):
-    """zpaqhip_enc_chain_plan: (waves, lds_bytes) of the lane-per-component encoder for a model (a models name, a zpaql.Model
-    or header bytes): the most encoder waves one compute unit holds for it (1 to 4; what enc_waves=0 uses at most) and the
-    LDS of such a workgroup, or (0, 0) for a model that encoder does not take.  Host-side."""
+def _chain_plan(fn, model):
     from . import models
-    L = _lib.load()
     if isinstance(model, str):
         model = models.get(model)
     hdr = _as_u8(model if isinstance(model, (bytes, bytearray, np.ndarray)) else model.header)
     waves, lds, err = C.c_uint32(0), C.c_uint32(0), Err()
-    rc = L.zpaqhip_enc_chain_plan(hdr.ctypes.data, hdr.size, C.byref(waves), C.byref(lds), C.byref(err))
+    rc = fn(hdr.ctypes.data, hdr.size, C.byref(waves), C.byref(lds), C.byref(err))
     if rc:
         _raise(err, rc)
     return waves.value, lds.value
+
+
+def enc_chain_plan(model):
+    """zpaqhip_enc_chain_plan: (waves, lds_bytes) of the lane-per-component encoder for a model (a models name, a zpaql.Model
+    or header bytes): the most encoder waves one compute unit holds for it (1 to 4; what enc_waves=0 uses at most) and the
+    LDS of such a workgroup, or (0, 0) for a model that encoder does not take.  Host-side."""
+    return _chain_plan(_lib.load().zpaqhip_enc_chain_plan, model)
+
+
+def dec_chain_plan(model):
+    """zpaqhip_dec_chain_plan: (waves, lds_bytes) of the lane-per-component decoder (zh_chain.hip) for a model (a models
+    name, a zpaql.Model or header bytes): the most decoder waves one compute unit holds for it (1 to 4; what dec_waves= uses
+    at most) and the LDS of such a workgroup, or (0, 0) for a model that kernel does not take.  Host-side."""
+    return _chain_plan(_lib.load().zpaqhip_dec_chain_plan, model)
 
 
 def multi_trim() -> None:
@@ -161,7 +171,11 @@ def multi_trim() -> None:
 
 
 def make_opts(verify_sha1: bool = False, max_concurrent: int = 0, kernel: int = 0, zpaql_budget: int = 0,
-              batch_blocks: int = 0, queue_blocks: int = 0) -> Opts:
+              batch_blocks: int = 0, queue_blocks: int = 0, dec_waves: int = 0) -> Opts:
+    """zpaqhip_opts from keywords (include/zpaqhip.h describes each): every decode entry point below takes them as **opt.
+    `dec_waves`: 2 to 4 puts up to that many decoder waves (blocks in flight) on a compute unit for blocks that zh_chain
+    decodes with its run-time level walk (kernel=0's other models, every chain model with kernel=4), as many as the models'
+    LDS plan (dec_chain_plan) allows; 0 or 1 one; more than 4 is 4.  The plaintext never depends on it."""
     o = Opts()
     o.struct_size = C.sizeof(Opts)
     o.verify_sha1 = int(verify_sha1)
@@ -170,6 +184,7 @@ def make_opts(verify_sha1: bool = False, max_concurrent: int = 0, kernel: int = 
     o.zpaql_budget = zpaql_budget
     o.batch_blocks = batch_blocks
     o.queue_blocks = queue_blocks
+    o.dec_waves = dec_waves
     return o
 
 

@@ -29,6 +29,7 @@ extern "C" hipError_t zh_launch_cm(const ZhLaunch *L, uint32_t grid, hipStream_t
 extern "C" hipError_t zh_launch_cm_x2(const ZhLaunch *L, uint32_t grid, hipStream_t stream);   // two blocks per workgroup
 extern "C" hipError_t zh_launch_sha1(const uint8_t *data, const uint64_t *seg, uint32_t n_seg, uint32_t *digest, hipStream_t stream);
 extern "C" hipError_t zh_launch_chain(const ZhLaunch *L, uint32_t grid, hipStream_t stream, uint32_t spec, int prof, int pcall);
+extern "C" hipError_t zh_launch_chain_mw(const ZhLaunch *L, const ZhChainWaves *V, uint32_t grid, hipStream_t stream, int pcall);
 extern "C" hipError_t zh_launch_cm_prof(const ZhLaunch *L, uint32_t grid, hipStream_t stream);
 extern "C" hipError_t zh_launch_chain2(const ZhLaunch *L, uint32_t grid, hipStream_t stream, uint32_t spec, int prof);
 extern "C" int zh_chain2_has(uint32_t spec);
@@ -59,6 +60,7 @@ struct DevBuf {
 
 struct zpaqhip_ctx {
   int device = 0;
+  int cus = 0;                            // compute units: a several-waves launch of zh_chain puts one workgroup on each
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   DevBuf tables, arena, models, code, bdesc, sdesc, results, queue, in, out;
@@ -91,6 +93,7 @@ zpaqhip_opts resolve_opts(const zpaqhip_opts *o) {
   memset(&r, 0, sizeof r);
   if (o) memcpy(&r, o, std::min<size_t>(sizeof r, o->struct_size ? o->struct_size : sizeof r));
   if (!r.zpaql_budget) r.zpaql_budget = 1ull << 32;
+  if (r.dec_waves > ZH_DEC_CHAIN_MAX_WAVES) r.dec_waves = ZH_DEC_CHAIN_MAX_WAVES;
   return r;
 }
 
@@ -151,8 +154,11 @@ int zpaqhip_ctx_create(int device, zpaqhip_ctx **out, zpaqhip_err *err) {
     return ZPAQHIP_E_NO_DEVICE;
   }
   HIPCHK(hipSetDevice(device));
+  int cus = 0;
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
   zpaqhip_ctx *c = new zpaqhip_ctx();
   c->device = device;
+  c->cus = std::max(1, cus);
   hipError_t e;
   if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess ||
       (e = hipEventCreate(&c->ev0)) != hipSuccess || (e = hipEventCreate(&c->ev1)) != hipSuccess ||
@@ -337,7 +343,7 @@ static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, 
     for (uint32_t i = 0; i < bd[k].n_seg; ++i) weight[k] += sd[bd[k].first_seg + i].in_len;
 
   // ---- blocks grouped by route (route_block): one group, one kernel
-  const bool pp_only = opts.reserved[0] == kPpOnlyMagic;
+  const bool pp_only = opts.reserved[0] == kPpOnlyMagic;        // the library's own use of the reserved word (zpaqhip_block_pcomp)
   const bool prof = getenv("ZPAQHIP_PROF") != nullptr;   // diagnostic build with in-kernel stamps
   std::vector<std::vector<uint32_t>> groups(ZH_NFAM_HOST);
   ZhRoute route_of[ZH_NFAM_HOST] = {};
@@ -382,6 +388,8 @@ static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, 
   // used by one family after the other
   uint32_t slots_of[ZH_NFAM_HOST] = {};
   bool cm_x2[ZH_NFAM_HOST] = {};
+  ZhChainWaves mw[ZH_NFAM_HOST] = {};     // waves > 1: the group runs on zh_decode_chain_mw, mw_grid workgroups of that many waves
+  uint32_t mw_grid[ZH_NFAM_HOST] = {};
   uint64_t stride_of[ZH_NFAM_HOST], arena_need = 0, arena_sum = 0, arena_off[ZH_NFAM_HOST] = {};
   uint32_t n_fam = 0;
   for (auto &x : stride_of) x = 256;
@@ -398,6 +406,30 @@ static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, 
     if (cm_x2[g]) want = opts.max_concurrent ? opts.max_concurrent : 512u;
     slots_of[g] = (uint32_t)std::min<uint64_t>({(uint64_t)want, max_slots, (uint64_t)groups[g].size()});
     if (cm_x2[g]) { slots_of[g] = (slots_of[g] + 1u) & ~1u; if (slots_of[g] > max_slots) { slots_of[g] = (uint32_t)(max_slots & ~1ull); cm_x2[g] = slots_of[g] >= 2; if (!cm_x2[g]) slots_of[g] = 1; } }
+    // opts.dec_waves >= 2, blocks on zh_chain's run-time level walk: several decoder waves per workgroup, an arena slot
+    // each.  The blocks spread over the compute units first; a second, third and fourth wave come with more blocks than
+    // workgroups, as many as the LDS plan of the group's models (the smallest: one launch, its pool sized for the largest
+    // chain), opts.dec_waves and the blocks per workgroup allow; where memory (or opts.max_concurrent) is short of a slot
+    // per wave the waves go before the workgroups.  One wave left: the launch is the one-wave kernel's, as without the option.
+    if (route_of[g].kernel == ZhKernel::Chain && route_of[g].spec == 0 && !prof && opts.dec_waves >= 2) {
+      uint32_t plan = ZH_DEC_CHAIN_MAX_WAVES, units = 0;
+      for (uint32_t k : groups[g]) {
+        const DecChainPlan p = plan_dec_chain(models[bd[k].model]);
+        plan = std::min(plan, p.waves);
+        units = std::max(units, p.units);
+      }
+      const uint32_t grid = std::min<uint32_t>(slots_of[g], (uint32_t)c->cus);
+      const uint64_t room = std::min<uint64_t>(max_slots, opts.max_concurrent ? opts.max_concurrent : UINT32_MAX);
+      uint32_t w = (uint32_t)std::min<uint64_t>({(uint64_t)plan, opts.dec_waves, (groups[g].size() + grid - 1) / grid});
+      while (w > 1 && (uint64_t)grid * w > room) --w;
+      if (w > 1) {
+        mw[g].waves = w;
+        mw[g].lds_pool = units * 1024u;
+        mw[g].lds_stride = zh_dec_chain_stride(units);
+        mw_grid[g] = grid;
+        slots_of[g] = grid * w;                          // one arena slot per resident wave
+      }
+    }
     arena_need = std::max<uint64_t>(arena_need, slots_of[g] * stride_of[g]);
     arena_off[g] = arena_sum;
     arena_sum += (slots_of[g] * stride_of[g] + 255) & ~255ull;
@@ -467,7 +499,8 @@ static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, 
       case ZhKernel::Chain: {
         int pcall = 0;                                   // any model with PCOMP memory: the variant with translated post-processors
         for (uint32_t k : groups[g]) pcall |= (models[bd[k].model].ph | models[bd[k].model].pm) != 0;
-        HIPCHK(zh_launch_chain(&L, slots_of[g], stream, r.spec, prof, pcall));
+        if (mw[g].waves > 1) HIPCHK(zh_launch_chain_mw(&L, &mw[g], mw_grid[g], stream, pcall));
+        else HIPCHK(zh_launch_chain(&L, slots_of[g], stream, r.spec, prof, pcall));
         break;
       }
       case ZhKernel::Chain2: HIPCHK(zh_launch_chain2(&L, slots_of[g], stream, r.spec, prof)); break;   // per-model bit loop
@@ -478,7 +511,8 @@ static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, 
       HIPCHK(hipStreamWaitEvent(launch_stream, c->fam_ev[g], 0));
     }
     ++launches;
-    slots = std::max(slots, slots_of[g]);
+    // (a several-waves launch: the blocks in flight are its waves with a block)
+    slots = std::max(slots, mw[g].waves > 1 ? (uint32_t)std::min<uint64_t>(slots_of[g], groups[g].size()) : slots_of[g]);
     kind_used = std::max(kind_used, r.kernel == ZhKernel::Generic || r.kernel == ZhKernel::Store ? 1u : r.kernel == ZhKernel::Cm ? 2u : 3u);
   }
   HIPCHK(hipEventRecord(c->ev1, stream));
@@ -693,9 +727,11 @@ void cut_at_bad_model(Batch &bt) {
 }
 
 // Next batch of whole blocks, or batch.so.blocks.empty() at the end of the stream.  Returns a call-level error only.
-int next_batch(Source &src, Batch &bt, size_t blk0, size_t seg0, size_t batch_blocks, zpaqhip_err *err) {
+int next_batch(Source &src, Batch &bt, size_t blk0, size_t seg0, size_t batch_blocks, size_t dec_waves, zpaqhip_err *err) {
   ScanLimit lim;
   lim.min_blocks = kBatchMinBlocks; lim.min_blocks_other = kBatchMinBlocksOther; lim.min_bytes = kBatchMinBytes; lim.max_blocks = kBatchMaxBlocks;
+  // opts.dec_waves >= 2: a batch of 256 blocks would leave zh_chain's second to fourth wave of a compute unit without a block
+  if (dec_waves > 1) lim.min_blocks_other = kBatchMinBlocksOther * dec_waves;
   if (batch_blocks) { lim.min_blocks = lim.max_blocks = batch_blocks; lim.min_blocks_other = 0; lim.min_bytes = 0; }   // zpaqhip_opts.batch_blocks
   bt = Batch();
   bt.blk0 = blk0; bt.seg0 = seg0;
@@ -1023,7 +1059,7 @@ int run_pipeline_impl(zpaqhip_ctx *c, Source &src, Sinkk &sink, const zpaqhip_op
     return ZPAQHIP_OK;
   };
 
-  int rc = next_batch(src, bt[cur], blk0, seg0, (size_t)opts.batch_blocks, err);
+  int rc = next_batch(src, bt[cur], blk0, seg0, (size_t)opts.batch_blocks, (size_t)opts.dec_waves, err);
   if (rc) return rc;
   bt[cur].slot = cur;
   rc = upload(bt[cur]);
@@ -1055,7 +1091,7 @@ int run_pipeline_impl(zpaqhip_ctx *c, Source &src, Sinkk &sink, const zpaqhip_op
     if (more) {
       { float ms = 0; if (hipEventElapsedTime(&ms, c->ev_h0, c->ev_h1) == hipSuccess) h2d_ms += ms; else (void)hipGetLastError(); }
       HIPCHK(hipStreamSynchronize(c->s_out));          // prev's device buffers are about to be reused
-      rc = next_batch(src, prev, blk0 + B.so.blocks.size(), seg0 + B.so.segs.size(), (size_t)opts.batch_blocks, err);
+      rc = next_batch(src, prev, blk0 + B.so.blocks.size(), seg0 + B.so.segs.size(), (size_t)opts.batch_blocks, (size_t)opts.dec_waves, err);
       if (rc) return rc;
       prev.slot = cur ^ 1;
       rc = upload(prev);
@@ -1480,6 +1516,20 @@ int zpaqhip_block_pcomp(zpaqhip_ctx *c, const uint8_t *in, size_t in_len, uint32
   out[0] = (uint8_t)(hsize & 255);
   out[1] = (uint8_t)(hsize >> 8);
   HIPCHK(hipMemcpy(out + 2, (const uint8_t *)c->arena.p + m.pz_off + ZH_CODE_PAD, hsize, hipMemcpyDeviceToHost));
+  return ZPAQHIP_OK;
+}
+
+// zh_chain.hip's several-waves plan for a block header: host only
+int zpaqhip_dec_chain_plan(const uint8_t *hdr, size_t hdr_len, uint32_t *waves, uint32_t *lds_bytes, zpaqhip_err *err) {
+  if (!hdr || !waves || !lds_bytes) { set_err(err, ZPAQHIP_E_ARG, -1, -1); return ZPAQHIP_E_ARG; }
+  *waves = *lds_bytes = 0;
+  ZhModel m;
+  std::vector<uint8_t> code;
+  const int rc = build_model(hdr, hdr_len, m, code, err);
+  if (rc) return rc;
+  const DecChainPlan p = plan_dec_chain(m);
+  *waves = p.waves;
+  *lds_bytes = p.lds_bytes;
   return ZPAQHIP_OK;
 }
 

@@ -21,10 +21,14 @@
 //  * MATCH verifies a candidate match with all 64 lanes comparing history bytes and
 //    one ballot (Predictor.cs:403-405 is a serial loop of up to 255 steps).
 //  * HCOMP / PCOMP run on the scalar core (zh_core.h) with H and M in LDS when small.
+//
+// The kernels at the end of the file put one such wavefront into a workgroup.  zh_chain_mw.hip compiles the same body into
+// workgroups of up to four of them, one per SIMD (opts.dec_waves; zh_dec_chain.h has the LDS layout).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "zh_core.h"
+#include "zh_dec_chain.h"
 #include "zh_dev.h"
 #include "zh_model.h"
 #include "zh_zpaql_native.h"
@@ -49,9 +53,7 @@ constexpr int kCodeBytes = 2048;          // HCOMP program window kept in LDS wh
 constexpr int kPHWords = 256;             // PCOMP H in LDS when 2^ph <= 256
 constexpr int kPMBytes = 1024;            // PCOMP M in LDS when 2^pm <= 1024
 
-struct alignas(16) ChainLds {
-  ZhTables t;
-  uint32_t small[kSmallWords];
+struct alignas(16) ChainWaveLds {          // what a decoder wave keeps per block, behind its ICM / ISSE pool
   uint8_t slot[64][64];                   // per-lane nibble cache (hash row or CM line)
   uint32_t sserow[64];                    // specialised kernels: the 32-entry table row of up to two SSE components for this bit
   uint32_t dummy[64];                     // per-lane sink for the stores of lanes a branch-free step does not concern
@@ -65,7 +67,31 @@ struct alignas(16) ChainLds {
   Sink sink;
   alignas(16) uint32_t pimm[64];          // operands of a structurally matched PCOMP (zh_zpaql_pcomp.h)
 };
+struct alignas(16) ChainLds {              // one wave per workgroup: the tables, a pool for the largest chain, the wave
+  ZhTables t;
+  uint32_t small[kSmallWords];
+  ChainWaveLds w;
+};
+struct alignas(16) ChainMwLds {            // up to four waves per workgroup (zh_dec_chain.h)
+  ZhTables t;                             // one copy for the workgroup, read-only after the fill
+  uint8_t waves[ZH_DEC_CHAIN_LDS - sizeof(ZhTables)];   // region w at w * ZhChainWaves::lds_stride: pool, then ChainWaveLds
+};
 static_assert(sizeof(ChainLds) <= 163840, "LDS budget");
+static_assert(sizeof(ChainWaveLds) == ZH_DEC_CHAIN_WAVE_FIXED, "zh_dec_chain.h plans with this size");
+static_assert(sizeof(ZhTables) == ZH_DEC_CHAIN_TABLES && sizeof(ZhTables) % 16 == 0, "zh_dec_chain.h plans with this size");
+static_assert(sizeof(ChainMwLds) == ZH_DEC_CHAIN_LDS && ZH_DEC_CHAIN_LDS <= 163840, "LDS budget");
+static_assert(ZH_DEC_CHAIN_TABLES + kSmallWords * 4 + ZH_DEC_CHAIN_WAVE_FIXED <= ZH_DEC_CHAIN_LDS, "the largest chain (64 units) fits one wave");
+
+// Orders what the lanes of ONE wave stored (LDS and the arena in global memory) before what they load next.  A workgroup of
+// one wave (MW false) keeps its __syncthreads(); in a workgroup of several decoder waves, each at a block of its own, it is
+// the waits of a workgroup fence and a scheduling fence and no s_barrier, as zh_enc_chain.hip's wave_sync().
+template <bool MW>
+__device__ __forceinline__ void lanes_sync() {
+  if constexpr (MW) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+  } else __syncthreads();
+}
 
 // Products of a 20-bit weight or error term and a 12-bit stretched prediction use the full-rate 24-bit multiplier
 // (__mul24 -> v_mul_i32_i24); both operands are bounded by clamp512k / clamp2k / squash, so the results are exact.
@@ -98,30 +124,34 @@ struct Lane {
   bool rowvalid;                          // slot holds a row/line that must be written back
 };
 
-template <bool PROF, class SP, bool PCALL>
-__device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S) {
+// T: the workgroup's tables; small: this wave's ICM / ISSE pool; S: this wave's state.  MW: the workgroup holds `waves` such
+// waves, this one is `wave` and owns arena slot blockIdx.x * waves + wave; they share T and meet at ONE workgroup barrier,
+// after the table fill; everything behind it orders one wave's lanes only (lanes_sync).
+template <bool PROF, class SP, bool PCALL, bool MW>
+__device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ZhTables &T, uint32_t *small, ChainWaveLds &S, uint32_t wave, uint32_t waves) {
+  static_assert(!MW || (SP::id == 0 && !PROF), "several waves: the run-time level walk only");
   constexpr bool kSpec = SP::id != 0;
   constexpr bool kDefer = SP::id == 1 || SP::id == 2;   // deferred mixer-weight store (measured: helps min / mid, not max)
 #define ZH_HAS(t) ((SP::types >> (t)) & 1u)
   uint64_t prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t tprev = 0;
-  const uint32_t lane = threadIdx.x;
+  const uint32_t lane = MW ? threadIdx.x & 63u : threadIdx.x;
 
   {  // model-independent tables -> LDS
     const uint4 *src = reinterpret_cast<const uint4 *>(L.tables);
-    uint4 *dst = reinterpret_cast<uint4 *>(&S.t);
-    for (uint32_t i = lane; i < sizeof(ZhTables) / 16; i += 64) dst[i] = src[i];
+    uint4 *dst = reinterpret_cast<uint4 *>(&T);
+    for (uint32_t i = MW ? threadIdx.x : lane; i < sizeof(ZhTables) / 16; i += MW ? 64u * waves : 64u) dst[i] = src[i];   // by every wave
   }
-  __syncthreads();
+  __syncthreads();                                       // MW: the kernel's only workgroup barrier; every wave reaches it
 
-  uint8_t *slot_mem = L.arena + (uint64_t)blockIdx.x * L.arena_stride;
+  uint8_t *slot_mem = L.arena + (uint64_t)(MW ? blockIdx.x * waves + wave : blockIdx.x) * L.arena_stride;
   uint8_t *myslot = &S.slot[lane][0];
 
   for (;;) {
     uint32_t bi = 0;
     if (lane == 0) bi = atomicAdd(L.queue, 1u);
     bi = uni((uint32_t)__shfl((int)bi, 0));
-    if (bi >= L.n_blocks) break;                       // every wave reaches this exit
+    if (bi >= L.n_blocks) break;                       // every wave reaches this exit, each at its own time
 
     const ZhBlockDesc *bdp = &L.blocks[bi];
     const uint32_t model_i = uni(bdp->model);
@@ -150,10 +180,10 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
         for (uint64_t k = lane; k < cmb / 16; k += 64) {
           const uint32_t j = (uint32_t)(k * 4) & 31;
           uint4 v;
-          v.x = (uint32_t)S.t.squash[(j + 0) * 64 - 992 + 2048] << 17 | start;
-          v.y = (uint32_t)S.t.squash[(j + 1) * 64 - 992 + 2048] << 17 | start;
-          v.z = (uint32_t)S.t.squash[(j + 2) * 64 - 992 + 2048] << 17 | start;
-          v.w = (uint32_t)S.t.squash[(j + 3) * 64 - 992 + 2048] << 17 | start;
+          v.x = (uint32_t)T.squash[(j + 0) * 64 - 992 + 2048] << 17 | start;
+          v.y = (uint32_t)T.squash[(j + 1) * 64 - 992 + 2048] << 17 | start;
+          v.z = (uint32_t)T.squash[(j + 2) * 64 - 992 + 2048] << 17 | start;
+          v.w = (uint32_t)T.squash[(j + 3) * 64 - 992 + 2048] << 17 | start;
           q[k] = v;
         }
       }
@@ -172,7 +202,7 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
       for (uint32_t i = lane; i < kPMBytes / 4; i += 64) reinterpret_cast<uint32_t *>(S.pmreg)[i] = 0;
     }
 
-    __syncthreads();
+    lanes_sync<MW>();
     // ---- this lane's component
     Lane me;
     {
@@ -193,16 +223,16 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
         case ZH_ICM:
           me.limit = 1023;
           for (uint32_t j = 0; j < 256; ++j) {
-            const uint32_t n0 = S.t.ns[j * 4 + 2], n1 = S.t.ns[j * 4 + 3];
-            S.small[me.sbase + j] = ((n1 * 2 + 1) << 22) / (n0 + n1 + 1);                 // StateTable.cminit
+            const uint32_t n0 = T.ns[j * 4 + 2], n1 = T.ns[j * 4 + 3];
+            small[me.sbase + j] = ((n1 * 2 + 1) << 22) / (n0 + n1 + 1);                 // StateTable.cminit
           }
           break;
         case ZH_ISSE:
           for (uint32_t j = 0; j < 256; ++j) {
-            const uint32_t n0 = S.t.ns[j * 4 + 2], n1 = S.t.ns[j * 4 + 3];
+            const uint32_t n0 = T.ns[j * 4 + 2], n1 = T.ns[j * 4 + 3];
             const uint32_t ci = ((n1 * 2 + 1) << 22) / (n0 + n1 + 1);
-            S.small[me.sbase + 2 * j] = 1u << 15;
-            S.small[me.sbase + 2 * j + 1] = (uint32_t)clamp512k(S.t.stretch[ci >> 8] * 1024);
+            small[me.sbase + 2 * j] = 1u << 15;
+            small[me.sbase + 2 * j + 1] = (uint32_t)clamp512k(T.stretch[ci >> 8] * 1024);
           }
           break;
         case ZH_MATCH: (slot_mem + me.hto)[0] = 1; break;
@@ -252,13 +282,13 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
       if (cnt > 1) dsc |= 7u << 12;
       if (lane == lv) lvl_desc = dsc;
     }
-    __syncthreads();
+    lanes_sync<MW>();
 
     // per-lane constants of the branch-free ICM / ISSE steps
     const bool is_icm = me.type == ZH_ICM, is_isse = me.type == ZH_ISSE, is_ii = is_icm || is_isse, is_match = me.type == ZH_MATCH;
-    const uint32_t ii_tab = lds_off(&S.small[0]) + me.sbase * 4;      // table of this lane (others: the pool's start, read only)
+    const uint32_t ii_tab = lds_off(&small[0]) + me.sbase * 4;      // table of this lane (others: the pool's start, read only)
     const uint32_t ii_sh = is_isse ? 3u : 2u;                         // 8-byte weight pairs / 4-byte probabilities
-    const uint32_t slot_off = lds_off(myslot), dummy_off = lds_off(&S.dummy[lane]), ns_off = lds_off(&S.t.ns[0]);
+    const uint32_t slot_off = lds_off(myslot), dummy_off = lds_off(&S.dummy[lane]), ns_off = lds_off(&T.ns[0]);
     int pm0 = 0, pm1 = 0;                                             // MATCH: stretch of +-dt2k[len] for this byte
 
     // HCOMP machine (ZPAQL.cs:1010-1026): H and M in LDS when they fit
@@ -308,7 +338,7 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
     out_room(ob);
     Sink &sink = S.sink;
     sink.out = ob.base; sink.cap = ob.cap; sink.len = 0;
-    __syncthreads();
+    lanes_sync<MW>();
     InBuf in;
     in.stream = L.in; in.total = L.in_total; in.cbase = 0; in.k = 0; in.avail = 0; in.cur = 0;
 
@@ -438,8 +468,8 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
             if (ZH_HAS(ZH_CM) && me.type == ZH_CM) {
               me.cxt = (me.h ^ hmap4) & 15;
               pv = reinterpret_cast<const uint32_t *>(myslot)[me.cxt];
-              me.p = S.t.stretch[pv >> 17];
-              pdt = S.t.dt[pv & 0x3ff];
+              me.p = T.stretch[pv >> 17];
+              pdt = T.dt[pv & 0x3ff];
             }
             uint32_t ii_a = 0;
             if (ZH_HAS(ZH_ICM) || ZH_HAS(ZH_ISSE)) {
@@ -450,7 +480,7 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
               ii_a = ii_tab + (st << ii_sh);
               const uint32_t w_x = *(lds_u32_p)ii_a, w_y = *(lds_u32_p)(ii_a + 4);
               const uint32_t nsv = *(lds_u16_p)(ns_off + st * 4);               // next(state, 0) | next(state, 1) << 8
-              const int stv = S.t.stretch[is_icm ? w_x >> 8 : 0];
+              const int stv = T.stretch[is_icm ? w_x >> 8 : 0];
               if (is_ii) { me.cxt = st; pns = nsv; pv = w_x; me.w0 = (int)w_x; me.w1 = (int)w_y; }
               if (is_icm) me.p = stv;
             }
@@ -464,9 +494,9 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
             }
             ZH_STAMP(0);
             // ================= predict, dependent levels =================
-            if constexpr (SP::id == 1) zh_spec_levels_min(me, lane, c8, S.t.stretch, slot_mem, S.sserow);
-            else if constexpr (SP::id == 2) zh_spec_levels_mid(me, lane, c8, S.t.stretch, slot_mem, S.sserow);
-            else if constexpr (SP::id == 3) zh_spec_levels_max(me, lane, c8, S.t.stretch, slot_mem, S.sserow);
+            if constexpr (SP::id == 1) zh_spec_levels_min(me, lane, c8, T.stretch, slot_mem, S.sserow);
+            else if constexpr (SP::id == 2) zh_spec_levels_mid(me, lane, c8, T.stretch, slot_mem, S.sserow);
+            else if constexpr (SP::id == 3) zh_spec_levels_max(me, lane, c8, T.stretch, slot_mem, S.sserow);
             else {
             for (uint32_t lv = 1; lv <= depth; ++lv) {
               const uint32_t desc = rdlane(lvl_desc, lv & 63);
@@ -496,7 +526,7 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
                   me.cxt += (uint32_t)pq;
                   const uint32_t *cm = reinterpret_cast<const uint32_t *>(slot_mem + me.cmo);
                   const uint32_t e0 = cm[me.cxt & me.cm_mask], e1 = cm[(me.cxt + 1) & me.cm_mask];
-                  me.p = S.t.stretch[((e0 >> 10) * (uint32_t)(64 - wt) + (e1 >> 10) * (uint32_t)wt) >> 13];
+                  me.p = T.stretch[((e0 >> 10) * (uint32_t)(64 - wt) + (e1 >> 10) * (uint32_t)wt) >> 13];
                   me.cxt += (uint32_t)(wt >> 5);
                   me.w0 = (int)((wt >> 5) ? e1 : e0);    // the entry train() will update
                 }
@@ -518,7 +548,7 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
                       me.cxt += (uint32_t)pq;
                       const uint32_t *cm = reinterpret_cast<const uint32_t *>(slot_mem + me.cmo);
                       const uint32_t e0 = cm[me.cxt & me.cm_mask], e1 = cm[(me.cxt + 1) & me.cm_mask];
-                      me.p = S.t.stretch[((e0 >> 10) * (uint32_t)(64 - wt) + (e1 >> 10) * (uint32_t)wt) >> 13];
+                      me.p = T.stretch[((e0 >> 10) * (uint32_t)(64 - wt) + (e1 >> 10) * (uint32_t)wt) >> 13];
                       me.cxt += (uint32_t)(wt >> 5);
                       me.w0 = (int)((wt >> 5) ? e1 : e0);
                       break;
@@ -542,7 +572,7 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
             }
             ZH_STAMP(1);
             // ================= decode the bit =================
-            const int sqp = (int)S.t.squash[me.p + 2048];          // squash(p[i]) of every lane, one LDS pass
+            const int sqp = (int)T.squash[me.p + 2048];          // squash(p[i]) of every lane, one LDS pass
             const uint32_t pr = rdlane((uint32_t)sqp, n - 1);
             const uint32_t ps = (pr * 2 + 1) << 16;
             ZH_DEC_STEP(d, ps, j, bad, rn);
@@ -569,7 +599,7 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
               const uint32_t v = (uint32_t)me.w0, cnt = v & 0x3ff;
               const int e = y * 32767 - (int)(v >> 17);
               reinterpret_cast<uint32_t *>(slot_mem + me.cmo)[me.cxt & me.cm_mask] =
-                  v + (((uint32_t)e * (uint32_t)S.t.dt[cnt]) & 0xFFFFFC00u) + (cnt < me.limit);
+                  v + (((uint32_t)e * (uint32_t)T.dt[cnt]) & 0xFFFFFC00u) + (cnt < me.limit);
             }
             if (ZH_HAS(ZH_ICM) || ZH_HAS(ZH_ISSE)) {            // all lanes, stores of unconcerned lanes go to their dummy cell
               *(lds_u8_p)(is_ii ? slot_off + hm15 : dummy_off) = (uint8_t)(pns >> (y * 8));   // StateTable.next
@@ -661,9 +691,9 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
             }
             if (ism) me.mbyte = (slot_mem + me.hto)[(me.limit - me.b) & me.ht_mask];
             if (ZH_HAS(ZH_MATCH)) {                        // the two predictions a match of this length can make (Predictor.cs:273-287)
-              const int dk = S.t.dt2k[is_match ? me.a : 0];
-              pm0 = S.t.stretch[dk & 32767];
-              pm1 = S.t.stretch[(-dk) & 32767];
+              const int dk = T.dt2k[is_match ? me.a : 0];
+              pm0 = T.stretch[dk & 32767];
+              pm1 = T.stretch[(-dk) & 32767];
             }
             nibble_finish();
           }
@@ -704,14 +734,14 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
           if (c < 0) { status = ZH_E_PP_EOS; break; }
           pzbuf[pp_len] = (uint8_t)c;
           if ((int)++pp_len == pp_hsize) {
-            __syncthreads();
+            lanes_sync<MW>();
             pz.prog = pzbuf; pz.len = pp_len;
             pz.a = pz.b = pz.c = pz.d = pz.f = 0;
             pnative = p_lds ? uni(zh_native_pcomp_lookup(pzbuf, pp_len)) : 0;
             if constexpr (PCALL) {
               pskel = pnative ? 0u : uni(zh_pcomp_lookup(pzbuf, pp_len));
               if (lane == 0) zh_pcomp_operands(pskel, pzbuf, S.pimm);
-              __syncthreads();
+              lanes_sync<MW>();
             }
             pp_state = 5;
           }
@@ -733,7 +763,7 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
     }
     if (PROF && lane == 0 && L.debug)
       for (int i = 0; i < 8; ++i) atomicAdd((unsigned long long *)&L.debug[i], (unsigned long long)prof[i]);
-    __syncthreads();
+    lanes_sync<MW>();
   }
 }
 
@@ -741,10 +771,11 @@ __device__ __forceinline__ void decode_chain_body(const ZhLaunch &L, ChainLds &S
 
 #undef ZH_HAS
 
+#ifndef ZH_CHAIN_MW_TU
 #define ZH_CHAIN_KERNEL(name, prof, spec, pcall)                                       \
   extern "C" __global__ __launch_bounds__(64) void name(ZhLaunch L) {                  \
     __shared__ ChainLds S;                                                             \
-    decode_chain_body<prof, spec, pcall>(L, S);                                        \
+    decode_chain_body<prof, spec, pcall, false>(L, S.t, S.small, S.w, 0u, 1u);           \
   }
 ZH_CHAIN_KERNEL(zh_decode_chain, false, ZhSpec_generic, false)
 // ... the same with the translated post-processors of zh_zpaql_pcomp.h behind a call: launched for models that give their
@@ -768,3 +799,32 @@ extern "C" hipError_t zh_launch_chain(const ZhLaunch *L, uint32_t grid, hipStrea
   hipLaunchKernelGGL(k, dim3(grid), dim3(64), 0, stream, *L);
   return hipGetLastError();
 }
+
+#else
+// ---- several decoder waves per workgroup, one per SIMD: the run-time level walk (ZhSpec_generic) only.  Each wave pulls its
+// own blocks from L.queue into its own arena slot and LDS region (zh_dec_chain.h); the waves share the tables and nothing
+// else, and run different numbers of blocks: the body's only workgroup barrier follows the table fill.  Compiled as a
+// translation unit of their own (zh_chain_mw.hip includes this file): a second caller of zh_zpaql_pcomp.h's functions in
+// one unit would change the code the compiler makes of them for zh_decode_chain_pc.
+#define ZH_CHAIN_MW_KERNEL(name, pcall)                                                                  \
+  extern "C" __global__ __launch_bounds__(256) void name(ZhLaunch L, ZhChainWaves V) {                   \
+    __shared__ ChainMwLds S;                                                                             \
+    const uint32_t wave = uni(threadIdx.x >> 6);                                                         \
+    uint8_t *const region = S.waves + wave * uni(V.lds_stride);                                          \
+    decode_chain_body<false, ZhSpec_generic, pcall, true>(                                               \
+        L, S.t, reinterpret_cast<uint32_t *>(region), *reinterpret_cast<ChainWaveLds *>(region + uni(V.lds_pool)), \
+        wave, uni(V.waves));                                                                             \
+  }
+ZH_CHAIN_MW_KERNEL(zh_decode_chain_mw, false)
+ZH_CHAIN_MW_KERNEL(zh_decode_chain_mw_pc, true)          // (as zh_decode_chain_pc: a model of the launch has PCOMP memory)
+
+extern "C" hipError_t zh_launch_chain_mw(const ZhLaunch *L, const ZhChainWaves *V, uint32_t grid, hipStream_t stream, int pcall) {
+  // the regions of the launch's waves lie inside the kernel's LDS block, and the pool in front of each is whole units
+  if (V->waves < 1 || V->waves > ZH_DEC_CHAIN_MAX_WAVES || V->lds_pool % 1024 || V->lds_stride % 16 ||
+      V->lds_stride < V->lds_pool + ZH_DEC_CHAIN_WAVE_FIXED ||
+      (uint64_t)V->waves * V->lds_stride > ZH_DEC_CHAIN_LDS - ZH_DEC_CHAIN_TABLES)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pcall ? zh_decode_chain_mw_pc : zh_decode_chain_mw, dim3(grid), dim3(64 * V->waves), 0, stream, *L, *V);
+  return hipGetLastError();
+}
+#endif

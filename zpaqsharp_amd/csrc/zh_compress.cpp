@@ -121,9 +121,6 @@ namespace {
 // ZH_FAM_CM1 models with opts.kernel 0 or 2, the lane-per-component encoder for the chain families with opts.kernel 2, the
 // generic encoder for everything else (and for a block too long for zh_enc_cm's 28-bit positions)
 enum class EncKernel { Generic, Cm, Chain };
-bool chain_family(uint32_t f) {
-  return (f >= ZH_FAM_CHAIN && f <= ZH_FAM_CHAIN + 3) || f == ZH_FAM_CHAIN_MID8 || f == ZH_FAM_CHAIN_MIN1;
-}
 EncKernel route_encode(const ZhModel &m, const zpaqhip_compress_opts &o, uint64_t coded) {
   if ((m.kind & 255u) == ZH_FAM_CM1 && (o.kernel == 0 || o.kernel == 2) && coded < ZH_ENC_CM_MAX_N) return EncKernel::Cm;
   if (o.kernel == 2 && chain_family(m.kind & 255u)) return EncKernel::Chain;
@@ -136,7 +133,7 @@ struct ChainPlan { uint32_t waves = 0, units = 0, lds_bytes = 0; };
 ChainPlan plan_chain(const ZhModel &m) {
   ChainPlan p;
   if (!chain_family(m.kind & 255u)) return p;
-  for (uint32_t i = 0; i < m.n; ++i) p.units += m.comp[i].type == ZH_ICM ? 1u : m.comp[i].type == ZH_ISSE ? 2u : 0u;
+  p.units = chain_units(m);
   p.waves = zh_enc_chain_fit(p.units);
   p.lds_bytes = p.waves ? ZH_ENC_CHAIN_TABLES + p.waves * zh_enc_chain_stride(p.units) : 0;
   return p;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/zpaqhip.h"
+#include "zh_dec_chain.h"
 #include "zh_model.h"
 
 // Kernel families known to the host only (the kernels never look at a family number): zh_model.h's, and
@@ -54,6 +55,28 @@ int scan_stream(const uint8_t *in, size_t n, ScanOut &out, zpaqhip_err *err, con
 // ZhModel + padded code window.  Mirrors ZPAQL.read (ZPAQL.cs:112-156) and the
 // limit checks of Predictor.init (Predictor.cs:94-167).
 int build_model(const uint8_t *hdr, size_t len, ZhModel &m, std::vector<uint8_t> &code, zpaqhip_err *err);
+
+// The lane-per-component kernels' family (zh_chain.hip, zh_enc_chain.hip) and a model's units of their ICM / ISSE pool in LDS
+// (ZhComp::small_unit counts them the same way: ICM 1, ISSE 2, at most 64)
+inline bool chain_family(uint32_t f) {
+  return (f >= ZH_FAM_CHAIN && f <= ZH_FAM_CHAIN + 3) || f == ZH_FAM_CHAIN_MID8 || f == ZH_FAM_CHAIN_MIN1;
+}
+inline uint32_t chain_units(const ZhModel &m) {
+  uint32_t u = 0;
+  for (uint32_t i = 0; i < m.n; ++i) u += m.comp[i].type == ZH_ICM ? 1u : m.comp[i].type == ZH_ISSE ? 2u : 0u;
+  return u;
+}
+// zh_chain.hip's several-waves kernel (zh_dec_chain.h): the most decoder waves of one workgroup (one per SIMD) whose regions fit
+// next to the shared tables, and the LDS of such a workgroup.  Models outside the family get no wave.
+struct DecChainPlan { uint32_t units = 0, waves = 0, lds_bytes = 0; };
+inline DecChainPlan plan_dec_chain(const ZhModel &m) {
+  DecChainPlan p;
+  if (!chain_family(m.kind & 255u)) return p;
+  p.units = chain_units(m);
+  p.waves = zh_dec_chain_fit(p.units);
+  p.lds_bytes = p.waves ? ZH_DEC_CHAIN_TABLES + p.waves * zh_dec_chain_stride(p.units) : 0;
+  return p;
+}
 
 const char *status_message(int code);
 void set_err(zpaqhip_err *err, int code, int block, int seg, const char *msg = nullptr);

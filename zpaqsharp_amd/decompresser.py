@@ -82,8 +82,9 @@ _BLOCK, _FILENAME, _COMMENT, _DATA, _SEGEND = range(5)     # Decompresser.cs:212
 
 
 class Decompresser:
-    def __init__(self, context: Optional[api.Context] = None, device: int = 0):
+    def __init__(self, context: Optional[api.Context] = None, device: int = 0, dec_waves: int = 0):
         self._ctx = context or api.Context(device)
+        self._dec_waves = dec_waves           # zpaqhip_opts.dec_waves of the one decode behind this object
         self._own = context is None
         self._in: Optional[Reader] = None
         self._out: Optional[Writer] = None
@@ -119,7 +120,7 @@ class Decompresser:
 
     def _decode_all(self):
         if self._res is None:
-            self._plain, self._res = self._ctx.decompress_segments(self._stream)
+            self._plain, self._res = self._ctx.decompress_segments(self._stream, dec_waves=self._dec_waves)
 
     # ---- Decompresser.cs:29-58
     def findBlock(self) -> bool:
@@ -221,9 +222,9 @@ class Decompresser:
             self._ctx.close()
 
 
-def decompress(reader: Reader, writer: Writer, context: Optional[api.Context] = None) -> None:
-    """LibZPAQ.decompress(Reader in, Writer out), LibZPAQ.cs:65-79."""
-    d = Decompresser(context)
+def decompress(reader: Reader, writer: Writer, context: Optional[api.Context] = None, dec_waves: int = 0) -> None:
+    """LibZPAQ.decompress(Reader in, Writer out), LibZPAQ.cs:65-79.  `dec_waves` is api.make_opts'."""
+    d = Decompresser(context, dec_waves=dec_waves)
     try:
         d.setInput(reader)
         d.setOutput(writer)

@@ -128,6 +128,10 @@ typedef struct zpaqhip_opts {
                                      specialisation (stored blocks included);
                                    5 min / mid / max on zh_chain's forms of the built-in models; the level 3 / 4 models on zh_chain;
                                    9 min / mid on zh_chain2 (bit at a time) instead of zh_nibble; the level 3 / 4 models on zh_chain;
+                                   10 as 0, and the E8E9 forms of `lazy2` / `lzpre` in unmodelled blocks (methods x..,5,.. and
+                                     x..,6,.. without a model: levels 1 and 2 on executables) stay on zh_store, which runs
+                                     their end-of-segment pass wave-wide, instead of being handed to zh_generic in a second
+                                     launch.  An opt-in until it becomes the default;
                                    7 / 8 and any other value: as 0 */
   uint64_t zpaql_budget;      /* runaway-program guard, per run() call: max ZPAQL instructions on the interpreter, max backward
                                  jumps in an ahead-of-time translated program (a translation checks where it can loop);

@@ -170,12 +170,21 @@ def multi_trim() -> None:
     _lib.load().zpaqhip_multi_trim()
 
 
+# opts.kernel value (include/zpaqhip.h has the table): as 0, and the E8E9 forms of lazy2 / lzpre in unmodelled blocks stay on
+# zh_store.hip instead of going to zh_generic.hip in a second launch
+KERNEL_STORE_E8 = 10
+
+
 def make_opts(verify_sha1: bool = False, max_concurrent: int = 0, kernel: int = 0, zpaql_budget: int = 0,
               batch_blocks: int = 0, queue_blocks: int = 0, dec_waves: int = 0) -> Opts:
     """zpaqhip_opts from keywords (include/zpaqhip.h describes each): every decode entry point below takes them as **opt.
     `dec_waves`: 2 to 4 puts up to that many decoder waves (blocks in flight) on a compute unit for blocks that zh_chain
     decodes with its run-time level walk (kernel=0's other models, every chain model with kernel=4), as many as the models'
-    LDS plan (dec_chain_plan) allows; 0 or 1 one; more than 4 is 4.  The plaintext never depends on it."""
+    LDS plan (dec_chain_plan) allows; 0 or 1 one; more than 4 is 4.  The plaintext never depends on it.
+    `kernel`: 0 auto; 1 everything on zh_generic; 2 / 6 single-CM blocks one / two per workgroup; 3 single-CM blocks on
+    zh_chain; 4 every specialised model and stored blocks on zh_chain; 5 / 9 the older forms of min / mid / max;
+    KERNEL_STORE_E8 (10) as 0, and unmodelled lazy2 / lzpre blocks with E8E9 stay on zh_store (one launch instead of two);
+    any other value as 0.  The plaintext never depends on it."""
     o = Opts()
     o.struct_size = C.sizeof(Opts)
     o.verify_sha1 = int(verify_sha1)

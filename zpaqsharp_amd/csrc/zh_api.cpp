@@ -117,7 +117,7 @@ ZhRoute route_block(const ZhModel &m, const zpaqhip_opts &o, bool pp_only) {
   switch (f) {
     case ZH_FAM_GENERIC: return {f, ZhKernel::Generic, 0};
     case ZH_FAM_CM1: return {f, ZhKernel::Cm, 0};
-    case ZH_FAM_STORE: return {f, ZhKernel::Store, 0};
+    case ZH_FAM_STORE: return {f, ZhKernel::Store, K == 10 ? 1u : 0u};   // 1: the E8E9 forms of lazy2 / lzpre stay on it
     case ZH_FAM_CHAIN_MID8: return {f, ZhKernel::Nibble, 5};           // mid's shape, eight mixer inputs
     case ZH_FAM_CHAIN_MIN1: return {f, ZhKernel::Nibble, 6};           // one ICM on min's loop
   }
@@ -485,6 +485,7 @@ static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, 
     L.flags = pp_only ? ZH_LAUNCH_PP_ONLY : 0u;
     if (prof) L.debug = (uint64_t *)((uint8_t *)c->queue.p + kQueueBytes);
     const ZhRoute &r = route_of[g];
+    if (r.kernel == ZhKernel::Store && r.spec) L.flags |= ZH_LAUNCH_STORE_E8;
     switch (r.kernel) {
       case ZhKernel::Generic: HIPCHK(zh_launch_generic(&L, slots_of[g], stream)); break;
       case ZhKernel::Store:

@@ -23,6 +23,11 @@
 // other programs, the E8E9 variants, the BWT, a stream that ends inside a chunk, a copy longer than 2^24 — makes the
 // block report ZH_E_RETRY: the host then runs it on zh_generic.hip, which is the complete implementation (it starts the
 // block from scratch).  PASS blocks (stored bytes, no program) are copied wave-wide by the parser wave.
+//
+// With ZH_LAUNCH_STORE_E8 (opts.kernel == 10) the E8E9 variants of lazy2 and lzpre are taken too.  They are the same
+// parsers without `out`: the flusher moves the ring to M only, and at the end of a segment, with everything flushed, the
+// parser wave runs the program's loop over M[0 .. d) as zh_e8e9_wave.h's schedule (e8_pass), which writes the Writer and
+// M.  A segment that writes more than |M| bytes is handed back: the program's loop then runs with wrapped indices.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -31,6 +36,8 @@
 #include "zh_model.h"
 #include "zh_zpaql_pcomp.h"
 #include "zh_ibwt.h"
+#define ZH_E8W_FN __device__ __forceinline__
+#include "zh_e8e9_wave.h"
 
 using namespace zhcore;
 using namespace zhdev;
@@ -60,6 +67,7 @@ struct alignas(16) StoreLds {
   uint32_t seg_base;                                    // ring position of the segment's first byte (the program's ptr = position - seg_base)
   uint32_t flush_to;                                    // the flusher also moves a last partial round up to here
   uint32_t skip_to;                                     // PASS: the parser wrote the Writer itself up to here
+  uint32_t m_only;                                      // an E8E9 form: the ring goes to M alone (the Writer gets the end-of-segment pass's bytes)
   Lz z;                                                 // the parser's state between two calls of lz_window
 };
 
@@ -126,6 +134,9 @@ __device__ const uint8_t kLazy302[43] = {255, 8, 0, 1, 3, 0, 3, 2, 7, 3, 5, 1, 2
 __device__ const uint8_t kLazy337[51] = {255, 8, 0, 1, 3, 0, 3, 2, 7, 3, 5, 1, 2, 3, 1, 2, 1, 1, 1, 1, 1, 1, 2, 3, 2, 5,
                                           5, 0, 0, 0, 0, 2, 2, 1, 0, 0, 0, 3, 1, 1, 1, 1, 1, 1, 1, 4, 4, 7, 8, 8, 0};
 
+// the end-of-segment loop of the E8E9 forms (LibZPAQ.cs:441-462, :581-601): a+= 4, a&= 254, a== 232, a&= 254, a== 0, a<<= 8 (2), a>>= 8 (2)
+__device__ const uint8_t kE8Tail[9] = {4, 254, 232, 254, 0, 8, 8, 8, 8};
+
 // bwtrle (LibZPAQ.cs:642-795), the two list traversals without E8E9: 16 MiB blocks at most / any size
 
 enum : uint32_t { kProgNone = 0, kProgLzpre = 1, kProgLazy2 = 2, kProgBwt = 3 };
@@ -157,6 +168,7 @@ __device__ void store_flusher(const ZhLaunch &L, StoreLds &S, uint32_t lane) {
       const uint32_t sk = st_ld(&S.skip_to);
       if ((int32_t)(sk - fl) > 0) { fl = sk; st_put0(&S.fpos, fl); }        // PASS: nothing of this comes from the ring
       const uint32_t w = st_ld(&S.wpos), ft = st_ld(&S.flush_to), sb = st_ld(&S.seg_base);
+      const uint64_t wcap = st_ld(&S.m_only) ? 0u : cap;
       // whole rounds of 64 up to the parser's position; everything up to flush_to
       uint32_t lim = fl + ((w - fl) & ~63u);
       if ((int32_t)(ft - lim) > 0 && (int32_t)(w - ft) >= 0) lim = ft;
@@ -171,7 +183,7 @@ __device__ void store_flusher(const ZhLaunch &L, StoreLds &S, uint32_t lane) {
           const uint32_t pos = fl + lane;
           const uint8_t v = *(lds_u8_p)(lds_off(S.ring) + (pos & kRM));
           Mp[(pos - sb) & mmask] = v;
-          if ((uint64_t)pos < cap) out[pos] = v;
+          if ((uint64_t)pos < wcap) out[pos] = v;
         }
         fl += n;
       }
@@ -643,6 +655,66 @@ __device__ __attribute__((noinline)) void lz_window(StoreLds &S, Lz &Z, uint32_t
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// END OF A SEGMENT of an E8E9 form: the program's loop over M[0 .. d), d <= |M|, on the parser wave with everything
+// flushed (zh_e8e9_wave.h: rounds of 64 slices, walked until no lane's incoming state changes).  The ring is scratch:
+// the round's original bytes and its final bytes, a slot per lane.  Final bytes go to M and, below `room`, to the Writer.
+// M is read past the vector cache (the flusher, another wave, wrote it) in aligned dwords: |M| is a multiple of 4 here.
+// ---------------------------------------------------------------------------------------------------------------
+typedef __attribute__((address_space(3))) uint32_t *lds_u32_p;
+__device__ __attribute__((noinline)) void e8_pass(StoreLds &S, uint8_t *Mp, uint8_t *outp, uint32_t room, uint32_t d, uint32_t lane) {
+  static_assert(2u * 8192u <= kRing && kZhE8wBuf <= 8192u && kZhE8wSlot % 4u == 0u && kZhE8wLanes == 64u, "two slot buffers in the ring, dword slots, a lane per slice");
+  const uint32_t in0 = lds_off(S.ring), out0 = in0 + 8192u;
+  const lds_u8_p my_in = (lds_u8_p)(in0 + lane * kZhE8wSlot), my_out = (lds_u8_p)(out0 + lane * kZhE8wSlot);
+  uint32_t carry = kZhE8wNone;
+  for (uint32_t base = 0; base < d; base += kZhE8wRound) {
+    const uint32_t nr = d - base < kZhE8wRound ? d - base : kZhE8wRound;
+    // the round's original bytes and the four after them, zeros from d on
+    for (uint32_t q = 4u * lane; q < nr + 4u; q += 256u) {
+      const uint32_t p = base + q;
+      uint32_t v = 0;
+      if (p < d) {
+        v = __hip_atomic_load(reinterpret_cast<const uint32_t *>(Mp + p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (d - p < 4u) v &= (1u << (8u * (d - p))) - 1u;
+      }
+      const uint32_t l = q / kZhE8wSlice, i = q % kZhE8wSlice;
+      if (l < kZhE8wLanes) *(lds_u32_p)(in0 + l * kZhE8wSlot + i) = v;
+      if (i == 0u && l > 0u) *(lds_u32_p)(in0 + (l - 1u) * kZhE8wSlot + kZhE8wSlice) = v;     // the look-ahead of the slice before
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const uint32_t p0 = base + lane * kZhE8wSlice, n = zh_e8w_count(base, lane, d);
+    uint32_t steps = 0;
+    uint32_t ist = lane == 0u && carry != kZhE8wNone ? carry : zh_e8w_clean(my_in);
+    uint32_t ost = zh_e8w_walk(my_in, my_out, p0, n, d, ist, kZhE8wNone, &steps);
+    for (;;) {
+      const uint32_t prev = (uint32_t)__shfl_up((int)ost, 1);
+      const uint32_t nin = lane == 0u ? ist : prev;
+      const bool changed = nin != ist;
+      if (__ballot(changed) == 0ull) break;
+      if (changed) {
+        const uint32_t o = zh_e8w_walk(my_in, my_out, p0, n, d, nin, ist, &steps);
+        if (o != kZhE8wNone) ost = o;
+        ist = nin;
+      }
+    }
+    carry = (uint32_t)__builtin_amdgcn_readlane((int)ost, 63);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    // the final bytes: M in dwords, the Writer a byte per lane (it begins anywhere)
+    for (uint32_t q = 4u * lane; q < nr; q += 256u) {
+      const uint32_t p = base + q;
+      const uint32_t v = *(lds_u32_p)(out0 + (q / kZhE8wSlice) * kZhE8wSlot + q % kZhE8wSlice);
+      if (d - p >= 4u) *reinterpret_cast<uint32_t *>(Mp + p) = v;
+      else for (uint32_t k = 0; k < d - p; ++k) Mp[p + k] = (uint8_t)(v >> (8u * k));
+    }
+    for (uint32_t j = lane; j < nr; j += 64u) {
+      const uint32_t p = base + j;
+      if (p < room) outp[p] = *(lds_u8_p)(out0 + zh_e8w_slot(j));
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  }
+  __builtin_amdgcn_s_waitcnt(0);                          // M is complete (L2) before the next segment's matches read it
+}
+
 typedef BwtLdsT<4096u> BwtLds;
 static_assert(sizeof(BwtLds) <= kRing, "the inverse BWT's tables live in the ring");
 }  // namespace
@@ -652,7 +724,7 @@ extern "C" __global__ __launch_bounds__(128) void zh_decode_store(ZhLaunch L) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = uni(threadIdx.x >> 6);
   uint8_t *slot = L.arena + (uint64_t)blockIdx.x * L.arena_stride;
-  if (threadIdx.x == 0) { S.cmd = 0; S.ack = 0; S.wpos = 0; S.fpos = 0; S.flush_to = 0; S.seg_base = 0; S.skip_to = 0; }
+  if (threadIdx.x == 0) { S.cmd = 0; S.ack = 0; S.wpos = 0; S.fpos = 0; S.flush_to = 0; S.seg_base = 0; S.skip_to = 0; S.m_only = 0; }
   __syncthreads();
   if (wave == 1) { store_flusher(L, S, lane); return; }
 
@@ -679,6 +751,7 @@ extern "C" __global__ __launch_bounds__(128) void zh_decode_store(ZhLaunch L) {
     uint32_t pp_len = 0, prog = kProgNone;
     uint32_t minlen = 0, rb = 0, bw_n = 0;               // (bwtrle: bytes of the segment collected in M)
     bool retry = false, failed = false, lost = false;
+    bool e8 = false;                                    // an E8E9 form: the Writer gets its bytes at the end of a segment (e8_pass)
     uint32_t fpos_seen = 0;                             // last value read from the flusher
 
     // the parser waits until the flusher has passed `need`
@@ -702,7 +775,7 @@ extern "C" __global__ __launch_bounds__(128) void zh_decode_store(ZhLaunch L) {
       const uint64_t mo = Mo->pm_off;
       S.words[4] = (uint32_t)mo; S.words[5] = (uint32_t)(mo >> 32);
       S.words[6] = mmask;
-      S.wpos = 0; S.fpos = 0; S.flush_to = 0; S.seg_base = 0; S.skip_to = 0;
+      S.wpos = 0; S.fpos = 0; S.flush_to = 0; S.seg_base = 0; S.skip_to = 0; S.m_only = 0;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     ++cmd_seq;
@@ -862,6 +935,32 @@ extern "C" __global__ __launch_bounds__(128) void zh_decode_store(ZhLaunch L) {
               }
               prog = kProgLazy2;
             }
+            else if ((L.flags & ZH_LAUNCH_STORE_E8) && (id == ZH_PCOMP_LZPRE_165 || id == ZH_PCOMP_LAZY2_360 || id == ZH_PCOMP_LAZY2_395)) {
+              // the E8E9 forms: words[0] = 255, the nine operands of the end-of-segment loop, then the plain form's from [1] on
+              ok = S.words[0] == 255u;
+              for (int k = 0; k < 9; ++k) ok = ok && S.words[1 + k] == kE8Tail[k];
+              if (id == ZH_PCOMP_LZPRE_165) {
+                for (int k = 1; k < 12; ++k) ok = ok && (k == 5 || S.words[9 + k] == kLzpre108[k]);
+                minlen = uni(S.words[9 + 5]); prog = kProgLzpre;
+              } else if (id == ZH_PCOMP_LAZY2_360) {
+                for (int k = 1; k < 43; ++k) ok = ok && S.words[9 + k] == kLazy302[k];
+                rb = 0; prog = kProgLazy2;
+              } else {
+                rb = uni(S.words[9 + 27]) + 1u;
+                ok = ok && rb >= 1u && rb <= 8u;
+                const uint32_t mk = (1u << (rb & 31u)) - 1u;
+                for (int k = 1; k < 51 && ok; ++k) {
+                  uint32_t want = kLazy337[k];
+                  if (k == 27) want = rb - 1u;
+                  else if (k == 28 || k == 35) want = mk;
+                  else if (k == 29 || k == 30 || k == 34) want = rb;
+                  ok = S.words[9 + k] == want;
+                }
+                prog = kProgLazy2;
+              }
+              ok = ok && pmb >= 2u;                      // (e8_pass reads M in dwords)
+              e8 = true;
+            }
             else if (id == ZH_PCOMP_BWTRLE_123 || id == ZH_PCOMP_BWTRLE_106) {
               ok = true;
               const int nk = id == ZH_PCOMP_BWTRLE_123 ? 11 : 9;
@@ -883,6 +982,7 @@ extern "C" __global__ __launch_bounds__(128) void zh_decode_store(ZhLaunch L) {
             if (lane == 0) {
               S.z.bits = S.z.nb = S.z.st = S.z.len = S.z.mbits = S.z.r5 = S.z.off = 0;
               S.z.rb = rb; S.z.minlen = minlen; S.z.mmask = mmask; S.z.prog = prog;
+              S.m_only = e8 ? 1u : 0u;
             }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
             pp_state = 5;
@@ -894,6 +994,11 @@ extern "C" __global__ __launch_bounds__(128) void zh_decode_store(ZhLaunch L) {
       if (flusher_on && !lost) {
         if (pp_state == 1 || prog == kProgBwt) { st_put0(&S.skip_to, wp); wait_flushed(wp); }     // (PASS and the inverse BWT wrote the Writer themselves)
         else flush_all();
+      }
+      if (e8 && !retry && !lost && pp_state == 5) {      // the program's loop over what the segment wrote
+        const uint32_t d = wp - seg_base;
+        if (d > mmask + 1u) retry = true;                // (it would run with wrapped indices)
+        else if (d) e8_pass(S, slot + uni64(Mo->pm_off), outp + seg_base, b_out_cap > seg_base ? (uint32_t)(b_out_cap - seg_base < 0xFFFFFFFFull ? b_out_cap - seg_base : 0xFFFFFFFFull) : 0u, d, lane);
       }
       if (retry || lost) break;
       const uint64_t produced = wp;

@@ -132,6 +132,11 @@ typedef struct zpaqhip_opts {
                                      x..,6,.. without a model: levels 1 and 2 on executables) stay on zh_store, which runs
                                      their end-of-segment pass wave-wide, instead of being handed to zh_generic in a second
                                      launch.  An opt-in until it becomes the default;
+                                   11 as 10, and zh_nibble runs the post-processors `lzpre` and `bwtrle` with E8E9 behind a model
+                                     (methods x..,6,..c0,0,511.. and x..,7ci1: levels 3 and 4 on executables, blocks up to
+                                     16 MiB) wave-wide — match copies, the inverse BWT and the end-of-segment E8E9 loop —
+                                     instead of as translated code on one lane (zpaqhip_stats.e8_wave_segs counts the
+                                     segments).  An opt-in;
                                    7 / 8 and any other value: as 0 */
   uint64_t zpaql_budget;      /* runaway-program guard, per run() call: max ZPAQL instructions on the interpreter, max backward
                                  jumps in an ahead-of-time translated program (a translation checks where it can loop);
@@ -167,7 +172,9 @@ typedef struct zpaqhip_stats {
   uint32_t launches;          /* decode kernel launches */
   uint32_t concurrent;        /* blocks in flight per launch (with opts.dec_waves >= 2: the waves with a block of the largest launch) */
   uint32_t kernel_kind;       /* most specialised kernel used: 1 generic, 2 single-CM lanes, 3 lane-per-component */
-  uint32_t reserved;
+  uint32_t e8_wave_segs;      /* opts.kernel == 11: segments of modelled blocks whose end-of-segment E8E9 loop ran wave-wide in
+                                 the call (a block decoded twice because its plaintext outgrew its staging slot counts
+                                 twice); 0 with any other kernel.  Was `reserved` */
 } zpaqhip_stats;
 
 typedef struct zpaqhip_ctx zpaqhip_ctx;

@@ -49,7 +49,7 @@ class Stats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("init_ms", C.c_double), ("h2d_ms", C.c_double), ("d2h_ms", C.c_double),
                 ("blocks", C.c_uint64), ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64),
                 ("model_bytes", C.c_uint64), ("launches", C.c_uint32), ("concurrent", C.c_uint32),
-                ("kernel_kind", C.c_uint32), ("reserved", C.c_uint32)]
+                ("kernel_kind", C.c_uint32), ("e8_wave_segs", C.c_uint32)]
 
 
 class CompressOpts(C.Structure):

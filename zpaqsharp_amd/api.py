@@ -173,6 +173,9 @@ def multi_trim() -> None:
 # opts.kernel value (include/zpaqhip.h has the table): as 0, and the E8E9 forms of lazy2 / lzpre in unmodelled blocks stay on
 # zh_store.hip instead of going to zh_generic.hip in a second launch
 KERNEL_STORE_E8 = 10
+# ... as 10, and zh_nibble.hip runs lzpre / bwtrle with E8E9 behind a model (levels 3 and 4 on executables) wave-wide, the
+# end-of-segment E8E9 loop included; Context.stats().e8_wave_segs counts the segments
+KERNEL_MODEL_E8 = 11
 
 
 def make_opts(verify_sha1: bool = False, max_concurrent: int = 0, kernel: int = 0, zpaql_budget: int = 0,
@@ -184,7 +187,9 @@ def make_opts(verify_sha1: bool = False, max_concurrent: int = 0, kernel: int = 
     `kernel`: 0 auto; 1 everything on zh_generic; 2 / 6 single-CM blocks one / two per workgroup; 3 single-CM blocks on
     zh_chain; 4 every specialised model and stored blocks on zh_chain; 5 / 9 the older forms of min / mid / max;
     KERNEL_STORE_E8 (10) as 0, and unmodelled lazy2 / lzpre blocks with E8E9 stay on zh_store (one launch instead of two);
-    any other value as 0.  The plaintext never depends on it."""
+    KERNEL_MODEL_E8 (11) as 10, and the modelled lzpre / bwtrle blocks with E8E9 (methods x..,6,..c0,0,511.., x..,7ci1) have
+    their post-processor run wave-wide on zh_nibble (stats().e8_wave_segs counts the segments); any other value as 0.  The
+    plaintext never depends on it."""
     o = Opts()
     o.struct_size = C.sizeof(Opts)
     o.verify_sha1 = int(verify_sha1)

@@ -101,7 +101,7 @@ zpaqhip_opts resolve_opts(const zpaqhip_opts *o) {
 // one / two blocks per workgroup, decided in decode_launch where the group's size is known.  `group` is the block's family
 // after opts.kernel's overrides (its work-queue head, arena region, stream and launch order); `spec` the kernel's specialisation
 enum class ZhKernel { Generic, Store, Cm, Chain, Chain2, Nibble };
-struct ZhRoute { uint32_t group; ZhKernel kernel; uint32_t spec; };
+struct ZhRoute { uint32_t group; ZhKernel kernel; uint32_t spec; uint32_t flags = 0; };   // flags: ZH_LAUNCH_* of the launch
 
 ZhRoute route_block(const ZhModel &m, const zpaqhip_opts &o, bool pp_only) {
   const uint32_t K = o.kernel, hk = (m.kind >> 8) & 255u;
@@ -114,15 +114,16 @@ ZhRoute route_block(const ZhModel &m, const zpaqhip_opts &o, bool pp_only) {
   if (K == 4 && f > ZH_FAM_CHAIN) f = ZH_FAM_CHAIN;                  // stored blocks included
   if ((K == 5 || K == 9) && ((f > ZH_FAM_CHAIN && f < ZH_FAM_STORE && method) || f == ZH_FAM_CHAIN_MID8 || f == ZH_FAM_CHAIN_MIN1))
     f = ZH_FAM_CHAIN;
+  const uint32_t nb_flags = K == 11 ? ZH_LAUNCH_MODEL_E8 : 0u;         // zh_nibble.hip: lzpre / bwtrle with E8E9 wave-wide
   switch (f) {
     case ZH_FAM_GENERIC: return {f, ZhKernel::Generic, 0};
     case ZH_FAM_CM1: return {f, ZhKernel::Cm, 0};
-    case ZH_FAM_STORE: return {f, ZhKernel::Store, K == 10 ? 1u : 0u};   // 1: the E8E9 forms of lazy2 / lzpre stay on it
-    case ZH_FAM_CHAIN_MID8: return {f, ZhKernel::Nibble, 5};           // mid's shape, eight mixer inputs
-    case ZH_FAM_CHAIN_MIN1: return {f, ZhKernel::Nibble, 6};           // one ICM on min's loop
+    case ZH_FAM_STORE: return {f, ZhKernel::Store, 0, K == 10 || K == 11 ? ZH_LAUNCH_STORE_E8 : 0u};   // the E8E9 forms of lazy2 / lzpre stay on it
+    case ZH_FAM_CHAIN_MID8: return {f, ZhKernel::Nibble, 5, nb_flags};  // mid's shape, eight mixer inputs
+    case ZH_FAM_CHAIN_MIN1: return {f, ZhKernel::Nibble, 6, nb_flags};  // one ICM on min's loop
   }
   const uint32_t spec = f - ZH_FAM_CHAIN;                              // 0: level walk at run time; 1 / 2 / 3: min / mid / max
-  if (spec && zh_nibble_has(spec) && K != 5 && K != 9) return {f, ZhKernel::Nibble, spec};   // 9: the bit-at-a-time form
+  if (spec && zh_nibble_has(spec) && K != 5 && K != 9) return {f, ZhKernel::Nibble, spec, nb_flags};   // 9: the bit-at-a-time form
   if (spec && zh_chain2_has(spec) && K != 5) return {f, ZhKernel::Chain2, spec};
   return {f, ZhKernel::Chain, spec};
 }
@@ -273,6 +274,7 @@ struct zh_pending {
   ZhLaunch store_launch{};
   size_t store_base = 0, store_count = 0;
   uint32_t store_slots = 0;
+  bool e8_wave = false;                                 // a launch had ZH_LAUNCH_MODEL_E8: word 1 of its work-queue head counts segments
 };
 
 static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, size_t in_len,
@@ -485,7 +487,8 @@ static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, 
     L.flags = pp_only ? ZH_LAUNCH_PP_ONLY : 0u;
     if (prof) L.debug = (uint64_t *)((uint8_t *)c->queue.p + kQueueBytes);
     const ZhRoute &r = route_of[g];
-    if (r.kernel == ZhKernel::Store && r.spec) L.flags |= ZH_LAUNCH_STORE_E8;
+    L.flags |= r.flags;
+    P.e8_wave |= (r.flags & ZH_LAUNCH_MODEL_E8) != 0;
     switch (r.kernel) {
       case ZhKernel::Generic: HIPCHK(zh_launch_generic(&L, slots_of[g], stream)); break;
       case ZhKernel::Store:
@@ -607,6 +610,12 @@ static int decode_finish(zpaqhip_ctx *c, zh_pending &P, zpaqhip_seg_result *resu
   c->stats.launches = launches + extra_launches;
   c->stats.concurrent = slots;
   c->stats.kernel_kind = kind_used;
+  if (P.e8_wave) {                                      // (the heads of launches of other kernels keep their word 1 at zero)
+    uint32_t heads[kQueueBytes / 4];
+    HIPCHK(hipMemcpyAsync(heads, c->queue.p, kQueueBytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    for (size_t g = 0; g < kQueueBytes / 32; ++g) c->stats.e8_wave_segs += heads[8 * g + 1];
+  }
   return first_bad;
 }
 
@@ -892,7 +901,7 @@ int settle_batch(zpaqhip_ctx *c, Batch &bt, const zpaqhip_opts &opts, bool toler
   int rc = decode_launch(c, c->in2[bt.slot].p, bt.h, bt.len, bt.so.blocks.data(), nb, bt.so.segs.data(), bt.so.segs.size(),
                          redo.data(), redo.size(), c->out_fix[bt.slot].p, off2.data(), cap2.data(), opts, c->stream, P, err);
   if (!rc) rc = decode_finish(c, P, bt.res.data(), err);
-  acc.kernel_ms += c->stats.kernel_ms; acc.launches += c->stats.launches;
+  acc.kernel_ms += c->stats.kernel_ms; acc.launches += c->stats.launches; acc.e8_wave_segs += c->stats.e8_wave_segs;
   if (rc && !(tolerate && data_error(rc)) && !data_error(rc)) return rc;
   for (size_t k = 0; k < redo.size(); ++k) {            // mark: lives in out_fix (offset | top bit)
     bt.off[redo[k]] = off2[k] | (1ull << 63);
@@ -1104,7 +1113,7 @@ int run_pipeline_impl(zpaqhip_ctx *c, Source &src, Sinkk &sink, const zpaqhip_op
     }
     // ---- finish this batch
     rc = decode_finish(c, P, B.res.data(), err);
-    acc.kernel_ms += c->stats.kernel_ms; acc.launches += c->stats.launches;
+    acc.kernel_ms += c->stats.kernel_ms; acc.launches += c->stats.launches; acc.e8_wave_segs += c->stats.e8_wave_segs;
     acc.blocks += c->stats.blocks; acc.in_bytes += c->stats.in_bytes; acc.model_bytes += c->stats.model_bytes;
     acc.concurrent = std::max(acc.concurrent, c->stats.concurrent); acc.kernel_kind = std::max(acc.kernel_kind, c->stats.kernel_kind);
     if (rc && !data_error(rc)) { rebase_err(err, B); return rc; }
@@ -1391,7 +1400,7 @@ int zpaqhip_decompress_multi_stats(const int *devices, size_t n_dev, const uint8
       const int rc = run_pipeline(c, src, sink, opts, false, nullptr, &e2, &stream_error);
       J.st.kernel_ms += c->stats.kernel_ms; J.st.h2d_ms += c->stats.h2d_ms; J.st.d2h_ms += c->stats.d2h_ms;
       J.st.blocks += c->stats.blocks; J.st.in_bytes += c->stats.in_bytes; J.st.out_bytes += c->stats.out_bytes;
-      J.st.model_bytes += c->stats.model_bytes; J.st.launches += 1;
+      J.st.model_bytes += c->stats.model_bytes; J.st.launches += 1; J.st.e8_wave_segs += c->stats.e8_wave_segs;
       J.st.concurrent = std::max(J.st.concurrent, c->stats.concurrent); J.st.kernel_kind = std::max(J.st.kernel_kind, c->stats.kernel_kind);
       size_t good = ids.size();
       if (rc) {

@@ -46,7 +46,8 @@ enum ZhCompType : uint8_t {  // LibZPAQ.cs:51-63
 #define ZH_E_STOPPED (-101)       // decode ended on request (ZH_LAUNCH_PP_ONLY); never leaves the library
 #define ZH_E_RETRY (-102)         // zh_store.hip hands the block to zh_generic.hip; never leaves the library
 #define ZH_LAUNCH_PP_ONLY 1u
-#define ZH_LAUNCH_STORE_E8 2u        // zh_store.hip takes the E8E9 forms of lazy2 / lzpre (opts.kernel == 10)
+#define ZH_LAUNCH_STORE_E8 2u        // zh_store.hip takes the E8E9 forms of lazy2 / lzpre (opts.kernel == 10 or 11)
+#define ZH_LAUNCH_MODEL_E8 4u        // zh_nibble.hip runs lzpre / bwtrle with E8E9 wave-wide (opts.kernel == 11)
 
 struct ZhComp {            // one component of a model (Component.cs:18-57 + header args)
   uint8_t type;            // ZhCompType
@@ -120,10 +121,10 @@ struct ZhLaunch {          // kernel arguments (one struct, passed by value)
   uint8_t *arena;
   uint64_t arena_stride;
   const ZhTables *tables;
-  uint32_t *queue;         // work-queue head (device-scope atomic)
+  uint32_t *queue;         // work-queue head (device-scope atomic); [1]: segments whose E8E9 loop ran wave-wide (ZH_LAUNCH_MODEL_E8)
   uint32_t n_blocks;
   uint32_t flags;          // ZH_LAUNCH_PP_ONLY: stop a block once its post-processor header is complete (generic kernel);
-                           // ZH_LAUNCH_STORE_E8 (store kernel)
+                           // ZH_LAUNCH_STORE_E8 (store kernel); ZH_LAUNCH_MODEL_E8 (nibble kernels)
   uint64_t budget;         // ZPAQL instructions per run()
   uint64_t in_total;       // length of the whole stream at `in`
   uint64_t *debug;         // diagnostic builds only (cycle sums); NULL otherwise

@@ -31,6 +31,7 @@
 #include "zh_zpaql_pcomp.h"
 #include "zh_ibwt.h"
 #include "zh_e8e9.h"
+#include "zh_e8e9_round.h"
 #include "zh_lzcopy.h"
 
 using namespace zhcore;
@@ -867,7 +868,10 @@ __device__ __attribute__((noinline)) int nb_pcomp_drain(const ZhLaunch *Lp_, LDS
     // segment — find it as they expect); loads of M go to L2 (glc): the bytes may have been written by other lanes a moment ago.
     // The distance is taken modulo |M| first, as the program's addresses are; a distance of 0 (offset bytes FF FF FF FF, or
     // |M| - 1 modulo |M|) writes out the cells M already holds.
-    const uint32_t lane = threadIdx.x & 63u, minlen = uni(S.fxs[kFxPlz]) - 1u, mm = uni(pz.mmask);
+    // The form with E8E9 (kFxPlz bit 16; ZH_PCOMP_LZPRE_165) is the same machine with nothing written out during the segment:
+    // its loop at the end of the segment writes M[0 .. b) out (nb_e8_pass).
+    const uint32_t lane = threadIdx.x & 63u, minlen = (uni(S.fxs[kFxPlz]) & 0xFFFFu) - 1u, mm = uni(pz.mmask);
+    const bool e8 = (uni(S.fxs[kFxPlz]) >> 16) != 0u;
     uint8_t *Mw = reinterpret_cast<uint8_t *>(uni64((uint64_t)(uintptr_t)pz.m));
     uint32_t r1 = uni(S.pr[1]), r2 = uni(S.pr[2]);
     OutBuf o;
@@ -884,7 +888,7 @@ __device__ __attribute__((noinline)) int nb_pcomp_drain(const ZhLaunch *Lp_, LDS
       } else if (pd == 1u) {
         if (lane == 0) Mw[pb & mm] = (uint8_t)x;
         ++pb;
-        out_put(o, x, lane);
+        if (!e8) out_put(o, x, lane);
         if (--r1 == 0u) pd = 0;
       } else if (pd > 2u) {
         r2 = r2 << 8 | x;
@@ -892,7 +896,7 @@ __device__ __attribute__((noinline)) int nb_pcomp_drain(const ZhLaunch *Lp_, LDS
       } else {
         r2 = r2 << 8 | x;
         const uint32_t n = r1, dist = r2 + 1u;
-        out_flush(o, lane);                              // the literals parked so far
+        if (!e8) out_flush(o, lane);                     // the literals parked so far
         __builtin_amdgcn_s_waitcnt(0);                   // (their stores to M, too)
         // (zh_lzcopy.h: the distance modulo |M| decides — 0 is a copy of every cell onto itself, nothing to store)
         const uint32_t d = zh_lz_reduce(dist, mm);
@@ -902,19 +906,18 @@ __device__ __attribute__((noinline)) int nb_pcomp_drain(const ZhLaunch *Lp_, LDS
           if (lane < m) {
             const uint8_t v = __hip_atomic_load(&Mw[(pb + done + lane - deff) & mm], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (d) Mw[(pb + done + lane) & mm] = v;
-            if (o.len + done + lane < o.cap) o.base[o.len + done + lane] = v;
+            if (!e8 && o.len + done + lane < o.cap) o.base[o.len + done + lane] = v;
           }
           done += m;
           __builtin_amdgcn_s_waitcnt(0);
           if (d) deff = zh_lz_grow(d, deff, done, mm);
         }
         pb += n;
-        o.len += n; o.stored = o.len; o.word = 0;
-        out_room(o);
+        if (!e8) { o.len += n; o.stored = o.len; o.word = 0; out_room(o); }
         pd = 0;
       }
     }
-    out_flush(o, lane);
+    if (!e8) out_flush(o, lane);
     if (lane == 0) { sink.len = o.len; S.pr[1] = r1; S.pr[2] = r2; }
   } else if (pnative == ZH_NATIVE_PCOMP_E8E9 && uni(pz.mmask) == 0u) {
     // E8E9 as the scalar operations it amounts to (zh_e8e9.h); its output parked and written like the decoder's own
@@ -1184,6 +1187,78 @@ __device__ __attribute__((noinline)) bool nb_ibwt(const ZhLaunch &L, LDS &S, uin
   return ok;
 }
 
+// The end-of-segment E8E9 loop of the reference's lzpre / bwtrle with E8E9 (LibZPAQ.cs:581-601, :716-735) over the d bytes at
+// `src`, wave-wide: rounds of zh_e8e9_wave.h's schedule (64 passes per round at most, whatever the data; no wait on another
+// wave).  The final bytes go back to `dst` (the program's M; null when the bytes are not M's) and, below `room`, to `outp`;
+// src == outp runs the pass in place (a round's bytes are loaded before they are stored, what a trigger writes beyond its
+// round travels in the state).  The two slot buffers overlay the start of S.stretch: the decoder wave is between two bytes
+// and reads no table, the helper wave is past its last commit of the segment and polls its mailbox, which lies behind the
+// tables (nb_ibwt's ordering); the tables are loaded again before the next segment's first byte.  Loads go to L2: other
+// lanes, or the inverse BWT, wrote the bytes a moment ago.
+template <class LDS>
+__device__ __attribute__((noinline)) void nb_e8_pass(const ZhLaunch &L, LDS &S, uint32_t lane, const uint8_t *src_, uint8_t *dst_, uint8_t *outp_, uint64_t room_,
+                                                     uint32_t d_) {
+  static_assert(2u * kZhE8wBuf <= sizeof(S.stretch) && offsetof(LDS, stretch) == 0 && kZhE8wBuf % 16u == 0u && kZhE8wLanes == 64u,
+                "two slot buffers over the model-independent tables, a lane per slice");
+  const uint8_t *src = reinterpret_cast<const uint8_t *>(uni64((uint64_t)(uintptr_t)src_));
+  uint8_t *dst = reinterpret_cast<uint8_t *>(uni64((uint64_t)(uintptr_t)dst_)), *outp = reinterpret_cast<uint8_t *>(uni64((uint64_t)(uintptr_t)outp_));
+  const uint64_t room = uni64(room_);
+  const uint32_t d = uni(d_);
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+  __builtin_amdgcn_s_waitcnt(0);
+  const uint32_t in0 = lds_off(S.stretch), out0 = in0 + kZhE8wBuf;
+  const lds_u8_p my_in = (lds_u8_p)(in0 + lane * kZhE8wSlot), my_out = (lds_u8_p)(out0 + lane * kZhE8wSlot);
+  const bool src_dw = ((uintptr_t)src & 3u) == 0u, dst_dw = ((uintptr_t)dst & 3u) == 0u;
+  const auto rd = [&](uint32_t p, uint32_t k) -> uint32_t {
+    if (src_dw && k == 4u) return __hip_atomic_load(reinterpret_cast<const uint32_t *>(src + p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uint32_t v = 0;
+    for (uint32_t t = 0; t < k; ++t) v |= (uint32_t)__hip_atomic_load(src + p + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) << (8u * t);
+    return v;
+  };
+  const auto wr = [&](uint32_t p, uint32_t k, uint32_t v) {
+    if (dst_dw && k == 4u) *reinterpret_cast<uint32_t *>(dst + p) = v;
+    else for (uint32_t t = 0; t < k; ++t) dst[p + t] = (uint8_t)(v >> (8u * t));
+  };
+  uint32_t carry = kZhE8wNone;
+  for (uint32_t base = 0; base < d; base += kZhE8wRound) {
+    const uint32_t nr = zh_e8w_round_len(base, d);
+    zh_e8w_load(rd, (lds_u32_p)in0, base, d, lane);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const uint32_t p0 = base + lane * kZhE8wSlice, n = zh_e8w_count(base, lane, d);
+    uint32_t steps = 0;
+    uint32_t ist = lane == 0u && carry != kZhE8wNone ? carry : zh_e8w_clean(my_in);
+    uint32_t ost = zh_e8w_walk(my_in, my_out, p0, n, d, ist, kZhE8wNone, &steps);
+    for (uint32_t pass = 0; pass <= kZhE8wLanes; ++pass) {  // (the ballot is empty after 64 walks at most: zh_e8e9_wave.h)
+      const uint32_t prev = (uint32_t)__shfl_up((int)ost, 1);
+      const uint32_t nin = lane == 0u ? ist : prev;
+      const bool changed = nin != ist;
+      if (__ballot(changed) == 0ull) break;
+      if (changed) {
+        const uint32_t o = zh_e8w_walk(my_in, my_out, p0, n, d, nin, ist, &steps);
+        if (o != kZhE8wNone) ost = o;
+        ist = nin;
+      }
+    }
+    carry = (uint32_t)__builtin_amdgcn_readlane((int)ost, 63);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    if (dst) zh_e8w_store(wr, (lds_u32_p)out0, base, d, lane);
+    for (uint32_t j = lane; j < nr; j += 64u) {
+      const uint32_t p = base + j;
+      if ((uint64_t)p < room) outp[p] = *(lds_u8_p)(out0 + zh_e8w_slot(j));
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  }
+  __builtin_amdgcn_s_waitcnt(0);                          // M is complete (L2) before the next segment's matches read it
+  if (lane == 0) atomicAdd(&L.queue[1], 1u);
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  nb_load_tables(L, S, lane);                             // (pm01, squash and ns lie behind the buffers: untouched)
+  nb_wave_sync();
+}
+
+// operands of the reference's lzpre / bwtrle with E8E9: the plain form's (zh_ibwt.h) and the nine of the loop
+__device__ const uint8_t kLzpre165[21] = {255, 4, 254, 232, 254, 0, 8, 8, 8, 8, 0, 6, 1, 63, 0 /* minimum match */, 1, 0, 2, 8, 8, 0};
+__device__ const uint8_t kBwt182[20] = {255, 8, 8, 8, 0, 255, 1, 255, 8, 0, 8, 4, 254, 232, 254, 0, 8, 8, 8, 8};
+
 template <class SP, bool PROF, class LDS>
 __device__ __forceinline__ void decode_nibble_body(const ZhLaunch &L, LDS &S) {
   constexpr uint64_t kII = NbK<SP>::kII;
@@ -1289,6 +1364,7 @@ __device__ __forceinline__ void decode_nibble_body(const ZhLaunch &L, LDS &S) {
     uint32_t pnative = 0, pskel = 0;                    // the loaded program is the translated E8E9 / has the structure of one of zh_zpaql_pcomp.h's
     uint32_t pbwt = 0;                                  // ... is the reference's bwtrle, operand for operand, in a block of one segment: M collects, nb_ibwt inverts
     uint32_t plz = 0;                                   // ... is the reference's lzpre, operand for operand (1 + its minimum match length): nb_pcomp_drain's state machine
+                                                        // (ZH_LAUNCH_MODEL_E8: 2 / bit 16 for the forms with E8E9, whose end-of-segment loop is nb_e8_pass)
     uint32_t pa = 0, pb = 0, pc_ = 0, pd = 0, pf = 0;
     uint8_t *pzbuf = slot_mem + uni64(M->pz_off) + ZH_CODE_PAD;
     OutBuf sb;                                          // state 5: the cursor nb_fast parks decoded bytes under on their way to the program
@@ -1433,10 +1509,30 @@ __device__ __forceinline__ void decode_nibble_body(const ZhLaunch &L, LDS &S) {
         } else if (pp_state == 5) {
           int rc;
           bool done = false;
-          if (pbwt && c < 0) {                          // end of the block's only segment: the inverse BWT, wave-wide
+          if (plz >> 16 && c < 0 && (uint64_t)pb <= (uint64_t)pz.mmask + 1u && (uint64_t)pb <= L.budget) {
+            // lzpre with E8E9, end of a segment that wrote M[0 .. pb) without a wrap: the program's loop, wave-wide, and its reset line
+            const uint64_t have = uni64(sink.len), cap = uni64(sink.cap);
+            nb_e8_pass(L, S, lane, pz.m, pz.m, sink.out + have, cap > have ? cap - have : 0u, pb);
+            uint32_t r1_, r2_;
+            const uint32_t wrote = pb;
+            zh_e8w_regs_after(pa, pb, pc_, pd, pf, r1_, r2_);
+            if (lane == 0) { sink.len = have + wrote; S.pr[1] = r1_; S.pr[2] = r2_; }
+            nb_wave_sync();
+            done = true;
+          }
+          // (bwtrle with E8E9 writes the inverse into M and its loop writes that out: here the inverse goes to the Writer's region
+          // and the loop runs there in place, so the region must hold all of it — the inverse has pb - 5 bytes at most: the walk ends at the
+          // list's head after visiting distinct positions other than idx, of the pb - 4 there are — and the
+          // program's own run must be sure of its budget, or the program runs as before)
+          uint64_t wroom = 0;
+          if (pbwt == 2u && c < 0) wroom = uni64(sink.cap) > uni64(sink.len) ? uni64(sink.cap) - uni64(sink.len) : 0u;
+          if (pbwt && c < 0 && (pbwt == 1u || (pb >= 6u && (uint64_t)(pb - 5u) <= wroom && L.budget >= 8ull * pb + 1024u))) {   // end of the block's only segment: the inverse BWT, wave-wide
             uint32_t produced_b = 0;
             bool touched = false;
-            if (nb_ibwt(L, S, lane, pb, &produced_b, &touched)) {
+            bool inv = nb_ibwt(L, S, lane, pb, &produced_b, &touched);
+            if (inv && pbwt == 2u && (uint64_t)uni(produced_b) > wroom) inv = false;     // (cannot be: the pass must not leave the region)
+            if (inv) {
+              if (pbwt == 2u) { uint8_t *at = sink.out + uni64(sink.len); nb_e8_pass(L, S, lane, at, (uint8_t *)nullptr, at, wroom, uni(produced_b)); }
               if (lane == 0) sink.len += uni(produced_b);
               nb_wave_sync();
               done = true;
@@ -1488,6 +1584,17 @@ __device__ __forceinline__ void decode_nibble_body(const ZhLaunch &L, LDS &S) {
               bool same = true;
               for (int k = 0; k < nk; ++k) same = same && uni(S.pimm[k]) == (pskel == ZH_PCOMP_BWTRLE_123 ? kBwt123[k] : kBwt106[k]);
               pbwt = same ? 1u : 0u;
+            }
+            if ((L.flags & ZH_LAUNCH_MODEL_E8) && pskel == ZH_PCOMP_BWTRLE_182 && n_seg == 1u && !p_lds) {
+              bool same = true;
+              for (int k = 0; k < 20; ++k) same = same && uni(S.pimm[k]) == kBwt182[k];
+              pbwt = same ? 2u : 0u;                       // 2: the inverse is not the output yet (nb_e8_pass)
+            }
+            if ((L.flags & ZH_LAUNCH_MODEL_E8) && pskel == ZH_PCOMP_LZPRE_165 && !p_lds && pz.m != S.pmreg && L.budget >= 1024u) {
+              bool same = true;
+              for (int k = 0; k < 21; ++k) same = same && (k == 14 || uni(S.pimm[k]) == kLzpre165[k]);
+              const uint32_t minlen = uni(S.pimm[14]);
+              plz = (same && minlen >= 1u) ? (minlen + 1u) | 0x10000u : 0u;    // bit 16: nothing goes out before the end of the segment
             }
             if (pskel == ZH_PCOMP_LZPRE_108 && !p_lds && pz.m != S.pmreg) {
               bool same = true;

@@ -1,98 +1,33 @@
 """zh_e8e9_wave.h — the end-of-segment E8E9 pass of `lazy2` / `lzpre` with E8E9 as a schedule for a wave — played on the
 host as 64 lanes against the oracle's interpreter running the reference's program."""
-import ctypes
 import os
 import shutil
 import subprocess
 
-import numpy as np
 import pytest
 
 import oracle
 from tests import store_e8_cases as cases
+from tests.e8w_harness import e8w  # noqa: F401  (the fixture)
 from tools import methods
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# The wave, lane by lane: what zh_store.hip's e8_pass does with shuffles and a ballot is done here with arrays.  Every lane
-# takes the outgoing state of the lane before it from the SAME pass (the snapshot `prev`), as lanes in lockstep do.
-HARNESS = r"""
-#include <stdint.h>
-#include <string.h>
-#define ZH_E8W_FN static inline
-#include "%s/zpaqsharp_amd/csrc/zh_e8e9_wave.h"
-extern "C" void e8w_sizes(uint32_t *s) { s[0] = kZhE8wSlice; s[1] = kZhE8wLanes; s[2] = kZhE8wRound; }
-// M[0 .. d) in place, the bytes written out to `out`; stat[0] = rounds, [1] = walk passes over all rounds, [2] = most in a round,
-// [3] = positions walked
-extern "C" void e8w_pass(uint8_t *M, uint32_t d, uint8_t *out, uint64_t *stat) {
-  static uint8_t in[kZhE8wBuf], fin[kZhE8wBuf];
-  uint32_t carry = kZhE8wNone;
-  stat[0] = stat[1] = stat[2] = stat[3] = 0;
-  for (uint32_t base = 0; base < d; base += kZhE8wRound) {
-    const uint32_t nr = d - base < kZhE8wRound ? d - base : kZhE8wRound;
-    memset(in, 0xAA, sizeof in);                        // (what a lane without positions finds in its slot does not matter)
-    for (uint32_t r = 0; r < nr + 4u; ++r) {
-      const uint8_t v = base + r < d ? M[base + r] : 0;
-      const uint32_t l = r / kZhE8wSlice, i = r %% kZhE8wSlice;
-      if (l < kZhE8wLanes) in[l * kZhE8wSlot + i] = v;
-      if (i < 4u && l > 0u) in[(l - 1u) * kZhE8wSlot + kZhE8wSlice + i] = v;
-    }
-    uint32_t ist[kZhE8wLanes], ost[kZhE8wLanes], prev[kZhE8wLanes], steps = 0;
-    uint64_t passes = 1;
-    for (uint32_t l = 0; l < kZhE8wLanes; ++l) {
-      ist[l] = l == 0u && carry != kZhE8wNone ? carry : zh_e8w_clean(in + l * kZhE8wSlot);
-      ost[l] = zh_e8w_walk(in + l * kZhE8wSlot, fin + l * kZhE8wSlot, base + l * kZhE8wSlice, zh_e8w_count(base, l, d), d, ist[l], kZhE8wNone, &steps);
-    }
-    for (;;) {
-      memcpy(prev, ost, sizeof prev);
-      bool any = false;
-      for (uint32_t l = 1; l < kZhE8wLanes; ++l) {
-        const uint32_t nin = prev[l - 1u];
-        if (nin == ist[l]) continue;
-        any = true;
-        const uint32_t o = zh_e8w_walk(in + l * kZhE8wSlot, fin + l * kZhE8wSlot, base + l * kZhE8wSlice, zh_e8w_count(base, l, d), d, nin, ist[l], &steps);
-        if (o != kZhE8wNone) ost[l] = o;
-        ist[l] = nin;
-      }
-      if (!any) break;
-      ++passes;
-    }
-    carry = ost[kZhE8wLanes - 1u];
-    for (uint32_t r = 0; r < nr; ++r) out[base + r] = M[base + r] = fin[zh_e8w_slot(r)];
-    stat[0] += 1; stat[1] += passes; stat[3] += steps;
-    if (passes > stat[2]) stat[2] = passes;
-  }
-}
-"""
 
 METHOD = "x0,6,1,0,7,16"                                  # lzpre + E8E9, matches from one byte: |M| = 2^20
 
 
 @pytest.fixture(scope="module")
-def wave(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("needs g++")
-    d = tmp_path_factory.mktemp("e8w")
-    src = d / "e8w.cpp"
-    src.write_text(HARNESS % ROOT)
-    so = d / "e8w.so"
-    subprocess.run(["g++", "-O1", "-Wall", "-Werror", "-shared", "-fPIC", "-o", str(so), str(src)], check=True)
-    lib = ctypes.CDLL(str(so))
-    sizes = (ctypes.c_uint32 * 3)()
-    lib.e8w_sizes(sizes)
-
+def wave(e8w):
+    """zh_store.hip's call: M[0 .. d) in place and aligned, the bytes written out to a buffer of their own.
+    -> (bytes written out, M afterwards, stat)"""
     def run(data: bytes):
-        m = (ctypes.c_uint8 * max(1, len(data))).from_buffer_copy(data if data else b"\0")
-        out = (ctypes.c_uint8 * max(1, len(data)))()
-        stat = (ctypes.c_uint64 * 4)()
-        lib.e8w_pass(m, len(data), out, stat)
-        return bytes(out[:len(data)]), bytes(m[:len(data)]), tuple(stat)
-    run.slice, run.lanes, run.round = tuple(sizes)
+        return e8w(data, m_in_place=True)
+    run.slice, run.lanes, run.round = e8w.slice, e8w.lanes, e8w.round
     return run
 
 
 def test_header_needs_only_stdint(tmp_path):
-    """The header compiles for the host with nothing but <stdint.h> before it (the harness above adds <string.h> for itself)."""
+    """The header compiles for the host with nothing but <stdint.h> before it (the harness of tests/e8w_harness.py adds <string.h> for itself)."""
     if not shutil.which("g++"):
         pytest.skip("needs g++")
     src = tmp_path / "only.cpp"

@@ -9,13 +9,12 @@ at type "binary".  Streams: the CPU stream writer (synth.method_stream, 16 host 
 and kernel = 10 are ALTERNATED, --rounds times each; one JSON line per run: kernel_ms (zpaqhip_last_stats), plaintext MB/s
 from it, launches, and the bytes that equal the plaintext generator's (bytes_checked; SHA-1 of every segment is verified
 too).  Summary lines give the ratios of the best kernel_ms.  Last, the schedule of zh_e8e9_wave.h is played on the host (the
-harness of tests/test_store_e8.py, needs g++) over what the LZ77 codes of the first --walk-blocks blocks write, and its
+harness of tests/e8w_harness.py, needs g++) over what the LZ77 codes of the first --walk-blocks blocks write, and its
 rounds, walk passes per round and positions walked per byte are printed."""
 import argparse
 import ctypes
 import json
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -29,19 +28,16 @@ from zpaqsharp_amd import method, synth  # noqa: E402
 
 
 def walk_stats(kind, blocks, block_size):
-    from tests.test_store_e8 import HARNESS
+    from tests import e8w_harness
     with tempfile.TemporaryDirectory() as d:
-        src, so = os.path.join(d, "e8w.cpp"), os.path.join(d, "e8w.so")
-        with open(src, "w") as f:
-            f.write(HARNESS % ROOT)
-        subprocess.run(["g++", "-O2", "-shared", "-fPIC", "-o", so, src], check=True)
-        lib = ctypes.CDLL(so)
+        lib, _ = e8w_harness.compile_lib(d, "-O2")
         tot = np.zeros(4, np.uint64)
         for b in range(blocks):
             m = synth.e8e9(synth.plain(kind, b, block_size)).copy()        # what the segment's codes write into M
             out = np.empty(max(1, m.size), np.uint8)
             stat = (ctypes.c_uint64 * 4)()
-            lib.e8w_pass(m.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint32(m.size), out.ctypes.data_as(ctypes.c_void_p), stat)
+            rc = lib.e8w_pass(m.ctypes.data, m.ctypes.data, out.ctypes.data, m.size, m.size, stat)     # (zh_store.hip's call: M in place)
+            assert rc == 0
             assert np.array_equal(out, synth.plain(kind, b, block_size))
             tot[0] += stat[0]; tot[1] += stat[1]; tot[3] += stat[3]
             tot[2] = max(int(tot[2]), int(stat[2]))

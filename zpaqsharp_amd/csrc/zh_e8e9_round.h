@@ -1,8 +1,8 @@
 // zh_e8e9_round.h — a round of zh_e8e9_wave.h's schedule in and out of its slot buffers, for a caller whose bytes lie in a
-// flat buffer that begins anywhere (zh_nibble.hip: M, or the Writer's region after the inverse BWT).  Plain integer code
+// flat buffer that begins anywhere (zh_nibble.hip: M, or the Writer's region after the inverse BWT; zh_store.hip: M).  Plain integer code
 // like the schedule itself: the caller says how a dword of the flat buffer is read and written, the slot buffers are
 // addressed in dwords (kZhE8wSlot and kZhE8wSlice are multiples of 4, and so is every round's base).
-// tests/test_model_e8.py compiles it for the host and plays the 64 lanes one after the other.
+// The kernels' driver (zh_e8e9_pass.h) and the tests' harness (tests/e8w_harness.py) both load and store their rounds with it.
 #pragma once
 #include <stdint.h>
 

@@ -1,7 +1,9 @@
 // zh_e8e9_wave.h — the inverse E8E9 pass at the end of a segment of the reference's LZ77 post-processors with E8E9 (lazy2:
 // LibZPAQ.cs:441-462, lzpre: :581-601) as a schedule that a wave executes.  Plain integer code over two byte buffers that
-// the caller owns: zh_store.hip runs it with both in LDS, tests/test_store_e8.py compiles it for the host and plays the 64
-// lanes one after the other against the oracle's run of the program.
+// the caller owns: the kernels' one driver (zh_e8e9_pass.h) runs it with both in LDS, the tests' one harness
+// (tests/e8w_harness.py) compiles it for the host and plays the 64 lanes one after the other against the oracle's run of the
+// program.  What a lane does in steps 1 to 3 below is here (zh_e8w_first, zh_e8w_retake); a caller's own is the exchange
+// between the lanes.
 //
 // The program, with d = the bytes the segment wrote into M (d <= |M|: no index wraps):
 //   for b = 0 .. d-1:
@@ -86,4 +88,28 @@ ZH_E8W_FN uint32_t zh_e8w_walk(PI in, PO out, uint32_t p0, uint32_t n, uint32_t 
     o3 = o4;
   }
   return st;
+}
+
+// What a lane keeps through a round: the incoming state its slice was last walked from and the outgoing state it has now
+struct ZhE8wLane { uint32_t ist, ost; };
+
+// Step 1 for lane `lane` of the round at `base` (`in` / `out`: the slot buffers): the walk from the clean state, lane 0's
+// from `carry`, the outgoing state of lane 63 in the round before (kZhE8wNone in the first round)
+template <class PI, class PO>
+ZH_E8W_FN void zh_e8w_first(ZhE8wLane &s, PI in, PO out, uint32_t base, uint32_t lane, uint32_t d, uint32_t carry, uint32_t *steps) {
+  in += lane * kZhE8wSlot;
+  s.ist = lane == 0u && carry != kZhE8wNone ? carry : zh_e8w_clean(in);
+  s.ost = zh_e8w_walk(in, out + lane * kZhE8wSlot, base + lane * kZhE8wSlice, zh_e8w_count(base, lane, d), d, s.ist, kZhE8wNone, steps);
+}
+
+// Steps 2 and 3 for lane `lane`: `nin` is the outgoing state the lane before it had when this time through step 2 began
+// (lane 0 has no lane before it: whatever it is given, its incoming state stands).  Returns whether the incoming state
+// changed, and has walked the slice again if so; the round is settled when no lane's did.
+template <class PI, class PO>
+ZH_E8W_FN bool zh_e8w_retake(ZhE8wLane &s, PI in, PO out, uint32_t base, uint32_t lane, uint32_t d, uint32_t nin, uint32_t *steps) {
+  if (lane == 0u || nin == s.ist) return false;
+  const uint32_t o = zh_e8w_walk(in + lane * kZhE8wSlot, out + lane * kZhE8wSlot, base + lane * kZhE8wSlice, zh_e8w_count(base, lane, d), d, nin, s.ist, steps);
+  if (o != kZhE8wNone) s.ost = o;                         // (the walk met the old one: its outgoing state stands)
+  s.ist = nin;
+  return true;
 }

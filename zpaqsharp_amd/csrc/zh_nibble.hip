@@ -31,7 +31,7 @@
 #include "zh_zpaql_pcomp.h"
 #include "zh_ibwt.h"
 #include "zh_e8e9.h"
-#include "zh_e8e9_round.h"
+#include "zh_e8e9_pass.h"
 #include "zh_lzcopy.h"
 
 using namespace zhcore;
@@ -1188,8 +1188,8 @@ __device__ __attribute__((noinline)) bool nb_ibwt(const ZhLaunch &L, LDS &S, uin
 }
 
 // The end-of-segment E8E9 loop of the reference's lzpre / bwtrle with E8E9 (LibZPAQ.cs:581-601, :716-735) over the d bytes at
-// `src`, wave-wide: rounds of zh_e8e9_wave.h's schedule (64 passes per round at most, whatever the data; no wait on another
-// wave).  The final bytes go back to `dst` (the program's M; null when the bytes are not M's) and, below `room`, to `outp`;
+// `src`, wave-wide: zh_e8e9_pass.h drives the rounds of zh_e8e9_wave.h's schedule (64 passes per round at most, whatever the
+// data; no wait on another wave).  The final bytes go back to `dst` (the program's M; null when the bytes are not M's) and, below `room`, to `outp`;
 // src == outp runs the pass in place (a round's bytes are loaded before they are stored, what a trigger writes beyond its
 // round travels in the state).  The two slot buffers overlay the start of S.stretch: the decoder wave is between two bytes
 // and reads no table, the helper wave is past its last commit of the segment and polls its mailbox, which lies behind the
@@ -1207,7 +1207,6 @@ __device__ __attribute__((noinline)) void nb_e8_pass(const ZhLaunch &L, LDS &S, 
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
   __builtin_amdgcn_s_waitcnt(0);
   const uint32_t in0 = lds_off(S.stretch), out0 = in0 + kZhE8wBuf;
-  const lds_u8_p my_in = (lds_u8_p)(in0 + lane * kZhE8wSlot), my_out = (lds_u8_p)(out0 + lane * kZhE8wSlot);
   const bool src_dw = ((uintptr_t)src & 3u) == 0u, dst_dw = ((uintptr_t)dst & 3u) == 0u;
   const auto rd = [&](uint32_t p, uint32_t k) -> uint32_t {
     if (src_dw && k == 4u) return __hip_atomic_load(reinterpret_cast<const uint32_t *>(src + p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1219,36 +1218,7 @@ __device__ __attribute__((noinline)) void nb_e8_pass(const ZhLaunch &L, LDS &S, 
     if (dst_dw && k == 4u) *reinterpret_cast<uint32_t *>(dst + p) = v;
     else for (uint32_t t = 0; t < k; ++t) dst[p + t] = (uint8_t)(v >> (8u * t));
   };
-  uint32_t carry = kZhE8wNone;
-  for (uint32_t base = 0; base < d; base += kZhE8wRound) {
-    const uint32_t nr = zh_e8w_round_len(base, d);
-    zh_e8w_load(rd, (lds_u32_p)in0, base, d, lane);
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    const uint32_t p0 = base + lane * kZhE8wSlice, n = zh_e8w_count(base, lane, d);
-    uint32_t steps = 0;
-    uint32_t ist = lane == 0u && carry != kZhE8wNone ? carry : zh_e8w_clean(my_in);
-    uint32_t ost = zh_e8w_walk(my_in, my_out, p0, n, d, ist, kZhE8wNone, &steps);
-    for (uint32_t pass = 0; pass <= kZhE8wLanes; ++pass) {  // (the ballot is empty after 64 walks at most: zh_e8e9_wave.h)
-      const uint32_t prev = (uint32_t)__shfl_up((int)ost, 1);
-      const uint32_t nin = lane == 0u ? ist : prev;
-      const bool changed = nin != ist;
-      if (__ballot(changed) == 0ull) break;
-      if (changed) {
-        const uint32_t o = zh_e8w_walk(my_in, my_out, p0, n, d, nin, ist, &steps);
-        if (o != kZhE8wNone) ost = o;
-        ist = nin;
-      }
-    }
-    carry = (uint32_t)__builtin_amdgcn_readlane((int)ost, 63);
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    if (dst) zh_e8w_store(wr, (lds_u32_p)out0, base, d, lane);
-    for (uint32_t j = lane; j < nr; j += 64u) {
-      const uint32_t p = base + j;
-      if ((uint64_t)p < room) outp[p] = *(lds_u8_p)(out0 + zh_e8w_slot(j));
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  }
-  __builtin_amdgcn_s_waitcnt(0);                          // M is complete (L2) before the next segment's matches read it
+  zh_e8w_pass(rd, wr, dst != nullptr, in0, out0, outp, room, d, lane);       // (M is complete before the next segment's matches read it)
   if (lane == 0) atomicAdd(&L.queue[1], 1u);
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   nb_load_tables(L, S, lane);                             // (pm01, squash and ns lie behind the buffers: untouched)

@@ -37,7 +37,7 @@
 #include "zh_zpaql_pcomp.h"
 #include "zh_ibwt.h"
 #define ZH_E8W_FN __device__ __forceinline__
-#include "zh_e8e9_wave.h"
+#include "zh_e8e9_pass.h"
 
 using namespace zhcore;
 using namespace zhdev;
@@ -657,62 +657,28 @@ __device__ __attribute__((noinline)) void lz_window(StoreLds &S, Lz &Z, uint32_t
 
 // ---------------------------------------------------------------------------------------------------------------
 // END OF A SEGMENT of an E8E9 form: the program's loop over M[0 .. d), d <= |M|, on the parser wave with everything
-// flushed (zh_e8e9_wave.h: rounds of 64 slices, walked until no lane's incoming state changes).  The ring is scratch:
+// flushed (zh_e8e9_pass.h: rounds of 64 slices, walked until no lane's incoming state changes).  The ring is scratch:
 // the round's original bytes and its final bytes, a slot per lane.  Final bytes go to M and, below `room`, to the Writer.
 // M is read past the vector cache (the flusher, another wave, wrote it) in aligned dwords: |M| is a multiple of 4 here.
 // ---------------------------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) uint32_t *lds_u32_p;
 __device__ __attribute__((noinline)) void e8_pass(StoreLds &S, uint8_t *Mp, uint8_t *outp, uint32_t room, uint32_t d, uint32_t lane) {
-  static_assert(2u * 8192u <= kRing && kZhE8wBuf <= 8192u && kZhE8wSlot % 4u == 0u && kZhE8wLanes == 64u, "two slot buffers in the ring, dword slots, a lane per slice");
-  const uint32_t in0 = lds_off(S.ring), out0 = in0 + 8192u;
-  const lds_u8_p my_in = (lds_u8_p)(in0 + lane * kZhE8wSlot), my_out = (lds_u8_p)(out0 + lane * kZhE8wSlot);
-  uint32_t carry = kZhE8wNone;
-  for (uint32_t base = 0; base < d; base += kZhE8wRound) {
-    const uint32_t nr = d - base < kZhE8wRound ? d - base : kZhE8wRound;
-    // the round's original bytes and the four after them, zeros from d on
-    for (uint32_t q = 4u * lane; q < nr + 4u; q += 256u) {
-      const uint32_t p = base + q;
-      uint32_t v = 0;
-      if (p < d) {
-        v = __hip_atomic_load(reinterpret_cast<const uint32_t *>(Mp + p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (d - p < 4u) v &= (1u << (8u * (d - p))) - 1u;
-      }
-      const uint32_t l = q / kZhE8wSlice, i = q % kZhE8wSlice;
-      if (l < kZhE8wLanes) *(lds_u32_p)(in0 + l * kZhE8wSlot + i) = v;
-      if (i == 0u && l > 0u) *(lds_u32_p)(in0 + (l - 1u) * kZhE8wSlot + kZhE8wSlice) = v;     // the look-ahead of the slice before
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    const uint32_t p0 = base + lane * kZhE8wSlice, n = zh_e8w_count(base, lane, d);
-    uint32_t steps = 0;
-    uint32_t ist = lane == 0u && carry != kZhE8wNone ? carry : zh_e8w_clean(my_in);
-    uint32_t ost = zh_e8w_walk(my_in, my_out, p0, n, d, ist, kZhE8wNone, &steps);
-    for (;;) {
-      const uint32_t prev = (uint32_t)__shfl_up((int)ost, 1);
-      const uint32_t nin = lane == 0u ? ist : prev;
-      const bool changed = nin != ist;
-      if (__ballot(changed) == 0ull) break;
-      if (changed) {
-        const uint32_t o = zh_e8w_walk(my_in, my_out, p0, n, d, nin, ist, &steps);
-        if (o != kZhE8wNone) ost = o;
-        ist = nin;
-      }
-    }
-    carry = (uint32_t)__builtin_amdgcn_readlane((int)ost, 63);
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    // the final bytes: M in dwords, the Writer a byte per lane (it begins anywhere)
-    for (uint32_t q = 4u * lane; q < nr; q += 256u) {
-      const uint32_t p = base + q;
-      const uint32_t v = *(lds_u32_p)(out0 + (q / kZhE8wSlice) * kZhE8wSlot + q % kZhE8wSlice);
-      if (d - p >= 4u) *reinterpret_cast<uint32_t *>(Mp + p) = v;
-      else for (uint32_t k = 0; k < d - p; ++k) Mp[p + k] = (uint8_t)(v >> (8u * k));
-    }
-    for (uint32_t j = lane; j < nr; j += 64u) {
-      const uint32_t p = base + j;
-      if (p < room) outp[p] = *(lds_u8_p)(out0 + zh_e8w_slot(j));
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  }
-  __builtin_amdgcn_s_waitcnt(0);                          // M is complete (L2) before the next segment's matches read it
+  static_assert(2u * 8192u <= kRing && kZhE8wBuf <= 8192u, "two slot buffers in the ring");
+  const auto rd = [&](uint32_t p, uint32_t k) -> uint32_t {
+    if (k == 4u) return __hip_atomic_load(reinterpret_cast<const uint32_t *>(Mp + p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uint32_t v = 0;
+    for (uint32_t t = 0; t < k; ++t) v |= (uint32_t)__hip_atomic_load(Mp + p + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) << (8u * t);
+    return v;
+  };
+  const auto wr = [&](uint32_t p, uint32_t k, uint32_t v) {
+    if (k == 4u) *reinterpret_cast<uint32_t *>(Mp + p) = v;
+    else for (uint32_t t = 0; t < k; ++t) Mp[p + t] = (uint8_t)(v >> (8u * t));
+  };
+  // More registers are declared written than the pass needs.  The compiler tells the caller which registers a noinline
+  // callee leaves alone, and zh_decode_store is allocated around that: with the pass's own smaller footprint the kernel's
+  // plain LZ77 path, which never comes here, measured 0.35 % slower (SGPR spills 143 -> 138 and another allocation throughout;
+  // profiles/e8_pass/rates.txt).  With these the kernel is instruction for instruction the one that path was measured with.
+  asm volatile("" ::: "s28", "s29", "s40", "s41", "s42", "s43", "v7", "v39", "v48", "v49", "v50", "v51", "v52");
+  zh_e8w_pass(rd, wr, true, lds_off(S.ring), lds_off(S.ring) + 8192u, outp, room, d, lane);   // (M is complete before the next segment's matches read it)
 }
 
 typedef BwtLdsT<4096u> BwtLds;

@@ -423,6 +423,35 @@ int zpaqhip_compress_method_blocks(zpaqhip_ctx *ctx, const int32_t args[9], cons
                                    size_t n_blocks, const char *const *filenames, uint8_t *out, size_t out_cap, size_t *out_len,
                                    uint64_t *block_off, const zpaqhip_compress_opts *opts, zpaqhip_err *err);
 
+/* ---- compression of device-resident blocks: the two calls above with the plaintext and the stream in device memory --------
+ * zpaqhip_compress_blocks_device is zpaqhip_compress_blocks, zpaqhip_compress_method_blocks_device is
+ * zpaqhip_compress_method_blocks (same flags, bits 0 to 4 of opts.flags), with `d_in`, `d_orig` (optional) and `d_out` device
+ * pointers on the context's device; in_off, orig_off, filenames, block_off, out_len, hdr and pcomp stay host memory.
+ * `hip_stream` is a hipStream_t (NULL = the context's own stream) on which every read of d_in / d_orig and every write of
+ * d_out is ordered; the call returns after the stream's work has completed.  The contract is the host forms': d_out[0,
+ * *out_len) holds exactly the bytes the host form writes for the same arguments, block_off and zpaqhip_last_stats are the
+ * same (launches also counts the packing kernel, zh_frame.hip: its launch that frames a batch, whose time is part of
+ * kernel_ms, and, without pre-processing, the one that stages a batch in place of the host form's upload, which like that
+ * upload is not timed), and with out_cap too small the call
+ * returns ZPAQHIP_E_OUTPUT_FULL with *out_len = the bytes needed, every block that fits in whole written and nothing written
+ * at or past d_out + out_cap.  No plaintext and no coded byte crosses the bus: per batch the results of the encoders, the
+ * digests (20 bytes per block) and the frame table (where each block's head, body and tail go) do.
+ * Alignment: none is asked of d_out, d_in or d_orig.  Heads and tails are built on the host; the packing kernel gathers
+ * head || body || tail of every block into d_out.  The encoders and the pre-processing work on an aligned device copy of a
+ * batch's input (device to device), as they do on the staged copy of the host forms; SHA-1 reads d_orig, when given, where
+ * it is.  Device memory is read in aligned 16-byte groups that hold at least one byte of a block, as any allocation of
+ * hipMalloc allows. */
+int zpaqhip_compress_blocks_device(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
+                                   const void *d_in, const uint64_t *in_off, size_t n_blocks,
+                                   const void *d_orig, const uint64_t *orig_off, const char *const *filenames,
+                                   void *d_out, size_t out_cap, size_t *out_len, uint64_t *block_off,
+                                   const zpaqhip_compress_opts *opts, void *hip_stream, zpaqhip_err *err);
+int zpaqhip_compress_method_blocks_device(zpaqhip_ctx *ctx, const int32_t args[9], const uint8_t *hdr, size_t hdr_len,
+                                          const uint8_t *pcomp, size_t pcomp_len, const void *d_in, const uint64_t *in_off,
+                                          size_t n_blocks, const char *const *filenames, void *d_out, size_t out_cap,
+                                          size_t *out_len, uint64_t *block_off, const zpaqhip_compress_opts *opts,
+                                          void *hip_stream, zpaqhip_err *err);
+
 /* ---- the data analysis of LibZPAQ.compressBlock's numeric levels 5..9 (LibZPAQ.cs:242-255) -------------------------------
  * The histogram of repetition gaps of each block p = in[in_off[i], in_off[i+1]): with pt[256] and r[4096] all zero,
  *     for j in 0..n-1:  k = j - pt[p[j]];  if 0 < k < 4096: ++r[k];  pt[p[j]] = j

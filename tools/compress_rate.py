@@ -2,6 +2,7 @@
 
     python3 tools/compress_rate.py [--blocks 256] [--block-size 4194304] [--kinds T,R] [--model l1] [--method M] [--bwt] [--sa | --ht]
                                    [--level L [--analysis-only]] [--kernel 0] [--enc-waves 0] [--rounds 1] [--decode-kernel K] [--no-cpu]
+                                   [--device]
 
 Per kind: plaintext MB/s from wall time, the time of each pass (zpaqhip_last_stats: init_ms = model pass, kernel_ms -
 init_ms = coder pass), and the CPU writer
@@ -31,6 +32,16 @@ waves per compute unit (zpaqhip_compress_opts.enc_waves; 0 automatic, 1 one wave
 values alternated in the same way, inside each --kernel value; "in_flight" is stats().concurrent.  --decode-kernel K adds the kernel time of Context.decompress of the stream
 with that decoder kernel (4 = zh_chain.hip, level walk at run time).  --no-cpu skips the CPU writer and with it every
 comparison with it (cpu16_MBps, identical, cpu16_ratio); the round trip and same_as_first remain.
+
+--device (with --model or --method): the host form (Context.compress_blocks / compress_method) and the device form
+(compress_blocks_device / compress_method_device) on the same blocks, ALTERNATED in one process, --rounds times each
+(default 2 here), one JSON line per call: wall time of the call, kernel_ms, launches.  The device form's input tensor is
+filled before the clock starts and its output is compared with the host form's stream on the device ("identical").  A last
+line gives the packing kernel's own rate for a method without a model (the store layout): there kernel_ms is the
+pre-processing and the packing kernel and init_ms the pre-processing alone, so pack_ms = kernel_ms - init_ms of the device
+form (best of the rounds), pack_GBps = stream bytes / pack_ms, and next to it d2d_GBps, a device-to-device copy of the same
+number of bytes timed with events in the same process.  Behind a model the packing kernel's time is part of a kernel_ms
+thousands of times as long and cannot be read off it: pack_ms is null.
 """
 import argparse
 import json
@@ -93,6 +104,66 @@ def run_method(ctx, a, kernels):
                 print(json.dumps(row), flush=True)
 
 
+def run_device(ctx, a, kernels):
+    import numpy as np
+    import torch
+    for kind in a.kinds.split(","):
+        blocks = [synth.plain(kind, i, a.block_size) for i in range(a.blocks)]
+        mb = a.blocks * a.block_size / 1e6
+        in_off = np.arange(a.blocks + 1, dtype=np.uint64) * a.block_size
+        d_in = torch.empty(a.blocks * a.block_size, dtype=torch.uint8, device="cuda")
+        for i, b in enumerate(blocks):          # the generator is a host one: block by block, before any clock starts
+            d_in[i * a.block_size:(i + 1) * a.block_size].copy_(torch.from_numpy(b))
+        what = {"method": a.method} if a.method else {"model": a.model}
+        for k in kernels:
+            def host(bl, k=k):
+                if a.method:
+                    return ctx.compress_method(a.method, bl, bwt=a.bwt, kernel=k, sa=a.sa, ht=a.ht)
+                return ctx.compress_blocks(a.model, bl, kernel=k)
+
+            def device(n, d_out, k=k):
+                if a.method:
+                    return ctx.compress_method_device(a.method, d_in.data_ptr(), in_off[:n + 1], d_out.data_ptr(), d_out.numel(),
+                                                      bwt=a.bwt, kernel=k, sa=a.sa, ht=a.ht)
+                return ctx.compress_blocks_device(a.model, d_in.data_ptr(), in_off[:n + 1], d_out.data_ptr(), d_out.numel(), kernel=k)
+
+            want = host(blocks)                                              # warm-up of both forms, and the size
+            d_want = torch.from_numpy(np.frombuffer(want, np.uint8).copy()).cuda()
+            d_out = torch.empty(len(want) + 4096, dtype=torch.uint8, device="cuda")
+            device(a.blocks, d_out)                                          # (the full shape: the first call of a size pays its allocations)
+            store = bool(a.method) and method.model_of(a.method)[0].header[6] == 0
+            pack_ms = None
+            for rnd in range(a.rounds):
+                for form in ("host", "device"):
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    if form == "host":
+                        got = host(blocks)
+                        same = got == want
+                    else:
+                        rc, n, _ = device(a.blocks, d_out)
+                    wall = time.perf_counter() - t
+                    st = ctx.stats()
+                    if form == "device":
+                        same = bool(rc == 0 and n == len(want) and torch.equal(d_out[:n], d_want))
+                    if form == "device" and store:
+                        pack_ms = min(pack_ms or 1e30, st.kernel_ms - st.init_ms)
+                    print(json.dumps({**what, "kind": kind, "blocks": a.blocks, "block_size": a.block_size, "kernel": k, "form": form,
+                                      "round": rnd, "wall_s": wall, "MBps": mb / wall, "kernel_ms": st.kernel_ms, "pre_ms": st.init_ms,
+                                      "launches": st.launches, "out_bytes": st.out_bytes, "identical": same}), flush=True)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            d2d = 1e30
+            for _ in range(3):
+                e0.record()
+                d_out[:len(want)].copy_(d_want)
+                e1.record()
+                torch.cuda.synchronize()
+                d2d = min(d2d, e0.elapsed_time(e1))
+            print(json.dumps({**what, "kind": kind, "kernel": k, "stream_bytes": len(want), "pack_ms": pack_ms,
+                              "pack_GBps": len(want) / 1e6 / pack_ms if pack_ms else None, "d2d_ms": d2d,
+                              "d2d_GBps": len(want) / 1e6 / d2d}), flush=True)
+
+
 def run_level(ctx, a, kernels):
     for kind in a.kinds.split(","):
         blocks = [synth.plain(kind, i, a.block_size) for i in range(a.blocks)]
@@ -149,13 +220,17 @@ def main():
     ap.add_argument("--analysis-only", action="store_true", help="with --level: only the gap histogram, GPU against the host loop")
     ap.add_argument("--kernel", default=None, help="encoder choice(s), comma separated; several are alternated (default 0; 2 with --level)")
     ap.add_argument("--enc-waves", default="0", help="chain encoder waves per compute unit, comma separated; several are alternated")
-    ap.add_argument("--rounds", type=int, default=1, help="runs of each --kernel value")
+    ap.add_argument("--rounds", type=int, default=None, help="runs of each --kernel value (default 1; 2 with --device)")
+    ap.add_argument("--device", action="store_true", help="host form against device form (compress_*_device), alternated")
     ap.add_argument("--decode-kernel", type=int, default=None, help="also time the decoder with this opts.kernel")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU writer")
     a = ap.parse_args()
     kernels = [int(k) for k in (a.kernel or ("2" if a.level else "0")).split(",")]
     a.waves = [int(w) for w in a.enc_waves.split(",")]
+    a.rounds = a.rounds if a.rounds is not None else 2 if a.device else 1
     with z.Context(0) as ctx:
+        if a.device:
+            return run_device(ctx, a, kernels)
         if a.level:
             return run_level(ctx, a, kernels)
         if a.method:

@@ -466,6 +466,73 @@ class Context:
             return out[:got.value].tobytes(), boffs, first
         _raise(err, rc)
 
+    def compress_blocks_device(self, model, d_in: int, in_off: Sequence[int], d_out: int, out_cap: int, *, d_orig: int = 0,
+                               orig_off: Optional[Sequence[int]] = None, filenames=None, sha1: bool = True, tag: bool = True,
+                               kernel: int = 0, batch_blocks: int = 0, slot_bytes: int = 0, enc_waves: int = 0,
+                               hip_stream: int = 0, raise_on_error: bool = True):
+        """zpaqhip_compress_blocks_device: compress_blocks on device buffers (pointers as ints; the caller holds the memory,
+        e.g. torch tensors' .data_ptr()).  Block i codes the bytes d_in + in_off[i] .. d_in + in_off[i + 1] as they are (no
+        E8E9 here: a `+e8e9` or `+lz77` model takes its pre-processed bytes in d_in and, for the size comment and SHA-1, the
+        plaintext in d_orig / orig_off); the stream goes to d_out, at most out_cap bytes.  `model`, the options and the
+        bytes are compress_blocks'.  Returns (rc, out_len, block_off): rc 0, or -20 (ZPAQHIP_E_OUTPUT_FULL) with out_len the
+        bytes needed and the blocks that fit in whole written; any other status raises unless raise_on_error is False."""
+        from . import models
+        m = models.get(model) if isinstance(model, str) else model
+        flags = (1 if sha1 else 0) | (2 if tag else 0)
+        return self._compress_device(m.header, m.pcomp or b"", None, d_in, in_off, d_orig, orig_off, filenames, flags, kernel,
+                                     batch_blocks, slot_bytes, enc_waves, d_out, out_cap, hip_stream, raise_on_error)
+
+    def compress_method_device(self, method: str, d_in: int, in_off: Sequence[int], d_out: int, out_cap: int, *, filenames=None,
+                               sha1: bool = True, tag: bool = True, kernel: int = 0, batch_blocks: int = 0, slot_bytes: int = 0,
+                               bwt: bool = False, sa: bool = False, ht: bool = False, enc_waves: int = 0, hip_stream: int = 0,
+                               raise_on_error: bool = True):
+        """zpaqhip_compress_method_blocks_device: compress_method on device buffers, in the style of compress_blocks_device:
+        the plaintext of block i at d_in + in_off[i], the stream to d_out, (rc, out_len, block_off) back.  The method's
+        refusals (ValueError before the device is touched) and the options are compress_method's."""
+        from . import method as mth
+        args = mth.parse_args(method)[1]
+        off = [int(x) for x in in_off]
+        mth.check_blocks(args, [b - a for a, b in zip(off, off[1:])], bwt=bwt, sa=sa, ht=ht)
+        model, _ = mth.model_of(method)
+        flags = (1 if sha1 else 0) | (2 if tag else 0) | (4 if bwt else 0) | (8 if sa else 0) | (16 if ht else 0)
+        return self._compress_device(model.header, model.pcomp or b"", args, d_in, off, 0, None, filenames, flags, kernel,
+                                     batch_blocks, slot_bytes, enc_waves, d_out, out_cap, hip_stream, raise_on_error)
+
+    def _compress_device(self, header: bytes, pcomp: bytes, args, d_in: int, in_off, d_orig: int, orig_off, filenames, flags: int,
+                         kernel: int, batch_blocks: int, slot_bytes: int, enc_waves: int, d_out: int, out_cap: int,
+                         hip_stream: int, raise_on_error: bool):
+        """The two device forms (`args`: the method form): (status, bytes needed, block offsets)."""
+        coffs = np.ascontiguousarray(in_off, dtype=np.uint64)
+        n = max(0, coffs.size - 1)
+        ooffs = np.ascontiguousarray(orig_off, dtype=np.uint64) if orig_off is not None else None
+        if ooffs is not None and ooffs.size != coffs.size:
+            raise ValueError("orig_off needs one entry per entry of in_off")
+        names = None
+        if filenames is not None:
+            if len(filenames) != n:
+                raise ValueError("filenames needs one entry per block")
+            names = (C.c_char_p * max(1, n))(*[(f.encode() if isinstance(f, str) else f) for f in filenames])
+        o = CompressOpts()
+        o.struct_size = C.sizeof(CompressOpts)
+        o.flags, o.kernel, o.batch_blocks, o.slot_bytes, o.enc_waves = flags, kernel, batch_blocks, slot_bytes, enc_waves
+        hdr = _as_u8(header)
+        pc = _as_u8(pcomp) if pcomp else None
+        boffs = np.zeros(n + 1, np.uint64)
+        err, got = Err(), C.c_size_t(0)
+        pcp, pcn = (pc.ctypes.data, pc.size) if pc is not None else (None, 0)
+        if args is not None:
+            rc = self._L.zpaqhip_compress_method_blocks_device(
+                self._h, (C.c_int32 * 9)(*args), hdr.ctypes.data, hdr.size, pcp, pcn, d_in or None, coffs.ctypes.data, n, names,
+                d_out or None, out_cap, C.byref(got), boffs.ctypes.data, C.byref(o), hip_stream or None, C.byref(err))
+        else:
+            rc = self._L.zpaqhip_compress_blocks_device(
+                self._h, hdr.ctypes.data, hdr.size, pcp, pcn, d_in or None, coffs.ctypes.data, n, d_orig or None,
+                ooffs.ctypes.data if ooffs is not None else None, names, d_out or None, out_cap, C.byref(got), boffs.ctypes.data,
+                C.byref(o), hip_stream or None, C.byref(err))
+        if rc and rc != -20 and raise_on_error:
+            _raise(err, rc)
+        return rc, got.value, boffs
+
     def decompress(self, stream, out_cap: Optional[int] = None, **opt) -> np.ndarray:
         """LibZPAQ.decompress(Reader, Writer) (LibZPAQ.cs:65-79) on host buffers."""
         a = _as_u8(stream)

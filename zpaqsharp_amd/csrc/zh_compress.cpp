@@ -25,6 +25,7 @@ extern "C" hipError_t zh_launch_enc_chain(const ZhEncLaunch *L, uint32_t grid, h
 extern "C" hipError_t zh_launch_enc_cm_model(const ZhEncLaunch *L, uint32_t n_blocks, hipStream_t stream);
 extern "C" hipError_t zh_launch_enc_cm_code(const ZhEncLaunch *L, uint32_t n_blocks, hipStream_t stream);
 extern "C" hipError_t zh_launch_sha1(const uint8_t *data, const uint64_t *seg, uint32_t n_seg, uint32_t *digest, hipStream_t stream);
+extern "C" hipError_t zh_launch_frame_pack(const ZhFrameLaunch *L, hipStream_t stream, uint32_t *launches);
 
 using namespace zh;
 
@@ -44,48 +45,6 @@ zpaqhip_compress_opts zh::resolve_compress_opts(const zpaqhip_compress_opts *opt
   if (opts) memcpy(&o, opts, std::min<size_t>(sizeof o, opts->struct_size ? opts->struct_size : sizeof o));
   else o.flags = 3;
   return o;
-}
-
-std::vector<uint8_t> zh::selector_prefix(const uint8_t *pcomp, size_t pcomp_len) {
-  if (!pcomp_len) return {0};
-  std::vector<uint8_t> sel{1, (uint8_t)(pcomp_len & 255), (uint8_t)(pcomp_len >> 8)};
-  sel.insert(sel.end(), pcomp, pcomp + pcomp_len);
-  return sel;
-}
-
-zh::BlockFrame::BlockFrame(bool tag, uint8_t level, const uint8_t *hdr, size_t hdr_len, const char *filename, uint64_t plain_len,
-                           const uint32_t *digest) : tail(4, '\0') {
-  static constexpr uint8_t kTag[13] = {0x37, 0x6b, 0x53, 0x74, 0xa0, 0x31, 0x83, 0xd3, 0x8c, 0xb2, 0x28, 0xb0, 0xd3};   // Compressor.cs:27-43
-  if (tag) head.append((const char *)kTag, 13);
-  head.append("zPQ", 3);
-  head.push_back((char)level);
-  head.push_back(1);
-  head.append((const char *)hdr, hdr_len);
-  head.push_back(1);
-  if (filename) head.append(filename);
-  head.push_back(0);
-  head.append(std::to_string(plain_len));
-  head.push_back(0);
-  head.push_back(0);
-  if (digest) {
-    tail.push_back((char)253);
-    for (int w = 0; w < 5; ++w)
-      for (int s = 24; s >= 0; s -= 8) tail.push_back((char)(digest[w] >> s));
-  } else tail.push_back((char)254);
-  tail.push_back((char)255);
-}
-
-uint64_t zh::store_body_len(uint64_t decoded) { return decoded + 4 * ((decoded + 65535) / 65536); }
-
-void zh::write_store_body(uint8_t *w, const std::vector<uint8_t> &sel, const uint8_t *pre, uint64_t pre_len) {
-  const uint64_t ns = sel.size(), dec = ns + pre_len;
-  for (uint64_t c = 0; c < dec; c += 65536) {
-    const uint64_t e = std::min<uint64_t>(c + 65536, dec), cl = e - c, p = std::max(c, ns);
-    *w++ = (uint8_t)(cl >> 24); *w++ = (uint8_t)(cl >> 16); *w++ = (uint8_t)(cl >> 8); *w++ = (uint8_t)cl;
-    if (c < ns) memcpy(w, sel.data() + c, std::min(ns, e) - c);
-    if (p < e) memcpy(w + (p - c), pre + (p - ns), e - p);
-    w += cl;
-  }
 }
 
 int zh::sha1_segments(const CtxView &v, const uint8_t *d_base, const std::vector<uint64_t> &seg, std::vector<uint32_t> &digest,
@@ -180,12 +139,17 @@ struct Call {
   DevPre *pre;
   zpaqhip_err *err;
   zpaqhip_compress_opts o;
+  bool dev_in = false, dev_out = false;   // the device form: `in` and `orig`, `out` are device memory; stage and frame differ
+  hipStream_t user_stream = nullptr;
+  uint32_t pack_launches = 0;             // zh_frame.hip's launches, of staging and of framing
   ZhModel M;
   std::vector<uint8_t> code, sel, dev_prefix;   // the selector prefix; what of it goes in front of the bytes on the device
   bool store = false;                     // n = 0: no encoder, the store layout of the pre-processed bytes (a level 2 block)
   CtxView v{};
   Event ev_model;                         // end of the model pass: init_ms times zh_enc_cm_model on its own
   DevMem d_model, d_code;
+  DevMem d_tab;                           // the packing kernel's table and blob, kept across batches and grown when needed
+  size_t tab_cap = 0;
   uint32_t wmask = 0;
   uint64_t budget = 0, arena_stride = 0;
   zpaqhip_stats st{};
@@ -214,12 +178,14 @@ struct Call {
   int encode(const Batch &B, EncRun &r);
   int encode_batch(Batch &B);
   int retry(Batch &B);
+  int pack(const FrameTable &T, const Batch &B, uint8_t *d_dst, float *ms);
   int frame(Batch &B);
 };
 
 // the device, the model for the generic encoder and what the CM encoder needs of it, the budget
 int Call::open(zpaqhip_ctx *ctx) {
   v = ctx_view(ctx);
+  if (user_stream) v.stream = user_stream;
   HIPCHK(hipSetDevice(v.device));
   st.blocks = n_blocks;
   if (!store) {
@@ -267,6 +233,23 @@ int Call::stage(Batch &B) {
     st.kernel_ms += B.pre.ms;
     return ZPAQHIP_OK;
   }
+  if (dev_in) {                           // device to device: prefix || block at its aligned place, by the packing kernel
+    FrameTable T;
+    T.blob = dev_prefix;
+    for (size_t j = 0; j < B.nb(); ++j) {
+      ZhFrameEntry e;
+      memset(&e, 0, sizeof e);
+      e.dst_off = B.boff[j];
+      e.head_len = (uint32_t)np;
+      e.src = ZH_FRAME_SRC_INPUT;
+      e.src_off = in_off[B.b0 + j];
+      e.body_len = B.blen[j] - np;
+      T.entry.push_back(e);
+      T.pieces = (uint32_t)std::max<uint64_t>(T.pieces, (e.body_len + ZH_FRAME_PIECE - 1) / ZH_FRAME_PIECE);
+    }
+    float ms = 0;
+    return pack(T, B, B.d_in.as<uint8_t>(), &ms);
+  }
   std::vector<uint8_t> h_in(B.in_total);
   for (size_t j = 0; j < B.nb(); ++j) {
     memcpy(h_in.data() + B.boff[j], dev_prefix.data(), np);
@@ -290,6 +273,10 @@ int Call::digests(Batch &B) const {
   if (!orig) {
     for (size_t j = 0; j < nb; ++j) seg[2 * j] = B.boff[j] + np;
     return sha1_segments(v, B.d_in.as<uint8_t>(), seg, B.digest, err);
+  }
+  if (dev_in) {                           // where the caller has it
+    for (size_t j = 0; j < nb; ++j) seg[2 * j] = orig_off[B.b0 + j];
+    return sha1_segments(v, orig, seg, B.digest, err);
   }
   uint64_t total = 0;
   for (size_t j = 0; j < nb; ++j) { seg[2 * j] = total; total += align_up(seg[2 * j + 1], 16); }
@@ -454,33 +441,81 @@ int Call::retry(Batch &B) {
   return ZPAQHIP_OK;
 }
 
-// framing around each block's coded bytes, in block order
+// zh_frame.hip over a table: uploads it with its blob and packs into d_dst from the batch's buffers and the caller's input
+int Call::pack(const FrameTable &T, const Batch &B, uint8_t *d_dst, float *ms) {
+  if (T.entry.empty()) return ZPAQHIP_OK;
+  const size_t tb = T.entry.size() * sizeof(ZhFrameEntry);
+  std::vector<uint8_t> up(tb + T.blob.size());
+  memcpy(up.data(), T.entry.data(), tb);
+  if (!T.blob.empty()) memcpy(up.data() + tb, T.blob.data(), T.blob.size());
+  if (up.size() + 16 > tab_cap) {         // (+ 16: the kernel reads the blob in aligned 16-byte groups)
+    HIPCHK(d_tab.alloc(2 * up.size() + 16));
+    tab_cap = 2 * up.size() + 16;
+  }
+  HIPCHK(hipMemcpy(d_tab.p, up.data(), up.size(), hipMemcpyHostToDevice));
+  ZhFrameLaunch L;
+  memset(&L, 0, sizeof L);
+  L.table = d_tab.as<ZhFrameEntry>();
+  L.blob = d_tab.as<uint8_t>() + tb;
+  L.src[ZH_FRAME_SRC_FIRST] = B.first.slots.as<uint8_t>();
+  L.src[ZH_FRAME_SRC_REDO] = B.redo.slots.as<uint8_t>();
+  L.src[ZH_FRAME_SRC_PRE] = B.d_in.as<uint8_t>();
+  L.src[ZH_FRAME_SRC_INPUT] = in;
+  L.out = d_dst;
+  L.sel_len = T.sel_len;
+  L.n = (uint32_t)T.entry.size();
+  L.pieces = T.pieces;
+  HIPCHK(hipEventRecord(v.ev0, v.stream));
+  HIPCHK(zh_launch_frame_pack(&L, v.stream, &pack_launches));
+  HIPCHK(hipEventRecord(v.ev1, v.stream));
+  HIPCHK(hipStreamSynchronize(v.stream));
+  HIPCHK(hipEventElapsedTime(ms, v.ev0, v.ev1));
+  return ZPAQHIP_OK;
+}
+
+// framing around each block's coded bytes, in block order: the frame table says what goes where; the host form copies by
+// it, the device form hands it to the packing kernel
 int Call::frame(Batch &B) {
+  std::vector<FrameItem> items;
+  items.reserve(B.nb());
+  for (size_t j = 0; j < B.nb(); ++j) {
+    const size_t i = B.b0 + j, k = store ? 0 : B.slot_of[j];
+    const int64_t redo = store ? -1 : B.redo_of[k];
+    BlockFrame f((o.flags & 2) != 0, store ? 2 : 1, hdr, hdr_len, filenames ? filenames[i] : nullptr, plain_len(i),
+                 want_sha() ? &B.digest[5 * j] : nullptr);
+    if (store) items.push_back({std::move(f), ZH_FRAME_SRC_PRE, B.boff[j], B.blen[j]});
+    else if (redo >= 0) items.push_back({std::move(f), ZH_FRAME_SRC_REDO, B.redo.desc[redo].slot_off, B.redo.res[redo].len});
+    else items.push_back({std::move(f), ZH_FRAME_SRC_FIRST, B.first.desc[k].slot_off, B.first.res[k].len});
+    st.in_bytes += plain_len(i);
+  }
+  const uint64_t pos0 = pos;
+  FrameTable T;
+  pos = build_frame_table(items, store ? &sel : nullptr, pos0, out_cap, T, block_off ? block_off + B.b0 : nullptr);
+  if (dev_out) {
+    float ms = 0;
+    const int rc = pack(T, B, out, &ms);
+    st.kernel_ms += ms;
+    return rc;
+  }
   // the batch's slots (store layout: its pre-processed bytes) in one copy, unless nothing more fits in `out` (the call
   // then only counts the bytes it needs)
   const DevMem &d_src = store ? B.d_in : B.first.slots;
   std::vector<uint8_t> h_src;
-  if (pos < out_cap) {
+  if (pos0 < out_cap) {
     h_src.resize(store ? B.in_total : B.first.slot_total);
     HIPCHK(hipMemcpy(h_src.data(), d_src.p, h_src.size(), hipMemcpyDeviceToHost));
   }
-  for (size_t j = 0; j < B.nb(); ++j) {
-    const size_t i = B.b0 + j, k = store ? 0 : B.slot_of[j];
-    const int64_t redo = store ? -1 : B.redo_of[k];
-    const BlockFrame f((o.flags & 2) != 0, store ? 2 : 1, hdr, hdr_len, filenames ? filenames[i] : nullptr, plain_len(i),
-                       want_sha() ? &B.digest[5 * j] : nullptr);
-    const uint64_t body = store ? store_body_len(sel.size() + B.blen[j]) : redo >= 0 ? B.redo.res[redo].len : B.first.res[k].len;
-    const uint64_t need = f.head.size() + body + f.tail.size();
-    if (block_off) block_off[i] = pos;
-    if (pos + need <= out_cap) {
-      uint8_t *w = put(out + pos, f.head);
-      if (store) write_store_body(w, sel, h_src.data() + B.boff[j], B.blen[j]);
-      else if (redo >= 0) HIPCHK(hipMemcpy(w, B.redo.slots.as<uint8_t>() + B.redo.desc[redo].slot_off, body, hipMemcpyDeviceToHost));
-      else if (body) memcpy(w, h_src.data() + B.first.desc[k].slot_off, body);
-      put(w + body, f.tail);
-    }
-    pos += need;
-    st.in_bytes += plain_len(i);
+  for (size_t n = 0; n < T.entry.size(); ++n) {
+    const ZhFrameEntry &e = T.entry[n];
+    const BlockFrame &f = items[T.item[n]].f;
+    uint8_t *w = put(out + e.dst_off, f.head);
+    uint64_t body = e.body_len;
+    if (store) {
+      write_store_body(w, sel, h_src.data() + e.src_off, e.body_len);
+      body = store_body_len(sel.size() + e.body_len);
+    } else if (e.src == ZH_FRAME_SRC_REDO) HIPCHK(hipMemcpy(w, B.redo.slots.as<uint8_t>() + e.src_off, body, hipMemcpyDeviceToHost));
+    else if (body) memcpy(w, h_src.data() + e.src_off, body);
+    put(w + body, f.tail);
   }
   return ZPAQHIP_OK;
 }
@@ -511,11 +546,21 @@ extern "C" int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, siz
                        block_off, opts, nullptr, err);
 }
 
+extern "C" int zpaqhip_compress_blocks_device(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp,
+                                              size_t pcomp_len, const void *d_in, const uint64_t *in_off, size_t n_blocks,
+                                              const void *d_orig, const uint64_t *orig_off, const char *const *filenames,
+                                              void *d_out, size_t out_cap, size_t *out_len, uint64_t *block_off,
+                                              const zpaqhip_compress_opts *opts, void *hip_stream, zpaqhip_err *err) {
+  const DeviceEnds dev{(hipStream_t)hip_stream};
+  return compress_impl(ctx, hdr, hdr_len, pcomp, pcomp_len, (const uint8_t *)d_in, in_off, n_blocks, (const uint8_t *)d_orig, orig_off,
+                       filenames, (uint8_t *)d_out, out_cap, out_len, block_off, opts, nullptr, err, &dev);
+}
+
 int zh::compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
                       const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
                       const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
                       uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
-                      const zpaqhip_compress_opts *opts, DevPre *pre, zpaqhip_err *err) {
+                      const zpaqhip_compress_opts *opts, DevPre *pre, zpaqhip_err *err, const DeviceEnds *dev) {
   if (!ctx || !hdr || !out_len || (!out && out_cap) || (n_blocks && !in_off) || (orig && !orig_off) || (pcomp_len && !pcomp) ||
       pcomp_len > 65535) {
     set_err(err, ZPAQHIP_E_ARG, -1, -1);
@@ -532,6 +577,10 @@ int zh::compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, cons
       return ZPAQHIP_E_ARG;
     }
   Call c{hdr, hdr_len, in, in_off, n_blocks, orig, orig_off, filenames, out, out_cap, block_off, pre, err, resolve_compress_opts(opts)};
+  if (dev) {
+    c.dev_in = c.dev_out = true;
+    c.user_stream = dev->stream;
+  }
   int rc = build_model(hdr, hdr_len, c.M, c.code, err);
   if (rc) return rc;
   c.store = c.M.n == 0;
@@ -554,6 +603,7 @@ int zh::compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, cons
   // A known wart, kept for zpaqhip_last_stats' sake: the store layout counts the pre-processing launches, the encoders' path
   // counts its own only.
   if (c.store) c.st.launches = pre->launches;
+  c.st.launches += c.pack_launches;
   c.st.kernel_kind = c.store ? 0 : c.any_chain ? 3 : c.any_cm ? 2 : 1;
   return finish_call(c.v, c.st, c.pos, n_blocks, block_off, out_cap, out_len, err);
 }

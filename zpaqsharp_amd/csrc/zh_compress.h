@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "zh_ctx_view.h"
+#include "zh_frame.h"
 
 namespace zh {
 
@@ -36,9 +37,6 @@ hipError_t device_budget(uint32_t mem_share, uint64_t reusable, uint64_t *budget
 // opts as the call uses them (struct_size-aware copy); NULL means SHA-1 and tag (flags = 3)
 zpaqhip_compress_opts resolve_compress_opts(const zpaqhip_compress_opts *opts);
 
-// What the coded sequence starts with (Compressor.postProcess, Compressor.cs:156-190): 0, or 1, len lo, len hi, pcomp
-std::vector<uint8_t> selector_prefix(const uint8_t *pcomp, size_t pcomp_len);
-
 // End of the batch that starts at block b0: opts.batch_blocks blocks when set, else blocks while their cost fits half the
 // budget (at least one block, at most 4096).
 template <class Cost>
@@ -49,18 +47,6 @@ size_t batch_end(size_t b0, size_t n_blocks, uint64_t batch_blocks, uint64_t bud
   while (b1 < n_blocks && b1 - b0 < 4096 && cost + cost_of(b1) <= budget / 2) cost += cost_of(b1++);
   return b1;
 }
-
-// The bytes around one block's coded data (LibZPAQ.cs:296-323; BlockWriter::write_block): tag, block and segment header
-// with the size comment in `head`, end of segment (with the SHA-1 when `digest` gives its five words) and of block in `tail`.
-struct BlockFrame {
-  std::string head, tail;
-  BlockFrame(bool tag, uint8_t level, const uint8_t *hdr, size_t hdr_len, const char *filename, uint64_t plain_len,
-             const uint32_t *digest);
-};
-// Encoder.compress without a model (Encoder.cs:39-73): the decoded stream, `sel` then `pre`, in chunks of at most 65 536
-// bytes behind their 4-byte big-endian lengths.
-uint64_t store_body_len(uint64_t decoded);
-void write_store_body(uint8_t *w, const std::vector<uint8_t> &sel, const uint8_t *pre, uint64_t pre_len);
 
 // SHA-1 (zh_sha1_dev.hip) of the segments d_base + seg[2k] of seg[2k + 1] bytes: five words per segment in `digest`.
 int sha1_segments(const CtxView &v, const uint8_t *d_base, const std::vector<uint64_t> &seg, std::vector<uint32_t> &digest,
@@ -103,7 +89,10 @@ struct PreBatch {                         // what DevPre::run leaves of a batch 
 // Device pre-processing of a batch of blocks (zh_pre.cpp), in place of the host copy of their coded bytes.
 class DevPre {
  public:
-  DevPre(const Method &M, const uint8_t *in, const uint64_t *in_off) : M_(M), in_(in), in_off_(in_off) {}
+  // `in_dev`: `in` is device memory; run then copies the batch device to device (the kernels read past a block's end in
+  // aligned groups, so they always work on the stage's own aligned copy)
+  DevPre(const Method &M, const uint8_t *in, const uint64_t *in_off, bool in_dev = false)
+      : M_(M), in_(in), in_off_(in_off), in_dev_(in_dev) {}
   uint64_t n_of(size_t i) const { return in_off_[i + 1] - in_off_[i]; }
   uint64_t bound(size_t i) const;         // pre-processed bytes of block i at most
   uint64_t scratch(size_t i) const;       // device bytes the stage needs for block i
@@ -116,6 +105,7 @@ class DevPre {
   Method M_;
   const uint8_t *in_;
   const uint64_t *in_off_;
+  bool in_dev_;
   DevMem plain_, e8_, len_, desc_, pref_;
   DevMem tab_, chain_, prev_;             // Greedy: ZhPreLaunch's table, chain and prev
   DevMem starts_, arena_;                 // slot routes: the slot starts of every launch; zh_pre.cpp's SortArena
@@ -123,11 +113,13 @@ class DevPre {
 
 // The batch loop.  Without `pre`, block i's coded bytes are in[in_off[i], in_off[i+1]) and `orig`, when given, is what the
 // size comment and SHA-1 describe.  With `pre` (the method path) `in` is the plaintext and `orig` NULL; a header with n = 0
-// then gets the store layout instead of an encoder.
+// then gets the store layout instead of an encoder.  `dev`, when given, is the device form: `in`, `orig` and `out` are then
+// device pointers on the context's device, `pre` was made with in_dev, and the work runs on dev->stream when that is set.
+struct DeviceEnds { hipStream_t stream = nullptr; };
 int compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
                   const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
                   const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
                   uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
-                  const zpaqhip_compress_opts *opts, DevPre *pre, zpaqhip_err *err);
+                  const zpaqhip_compress_opts *opts, DevPre *pre, zpaqhip_err *err, const DeviceEnds *dev = nullptr);
 
 }  // namespace zh

@@ -1,0 +1,80 @@
+// zh_frame.h — block framing: the bytes around a block's coded data (BlockFrame), the store layout, and the frame table
+// of a batch, which says where every block's head, body and tail go in the stream.  The host forms of the compressing entry
+// points copy by it on the host; the device forms upload it and zh_frame.hip packs the stream on the GPU.  Nothing here
+// needs HIP: zh_frame_table.cpp builds alone (tests/native/frame_table_main.cpp links it under the sanitizers).
+#pragma once
+#include <stdint.h>
+
+// One block of the stream, for zh_frame.hip: head || body || tail at out + dst_off.  head and tail lie in the batch's blob;
+// the body is body_len bytes at src_off of the buffer `src` selects, written as they are or, with `store`, behind the
+// selector in the store layout (write_store_body).
+struct ZhFrameEntry {
+  uint64_t dst_off;
+  uint64_t src_off, body_len;
+  uint64_t head_off, tail_off;
+  uint32_t head_len, tail_len;
+  uint32_t src;                           // ZH_FRAME_SRC_*
+  uint32_t store;
+};
+
+enum {
+  ZH_FRAME_SRC_FIRST = 0,                 // the slots of the batch's first encoder run
+  ZH_FRAME_SRC_REDO = 1,                  // the worst-case slots of the overflow retry
+  ZH_FRAME_SRC_PRE = 2,                   // the batch's coded sequences (store layout: the pre-processed bytes)
+  ZH_FRAME_SRC_INPUT = 3,                 // the caller's device input (staging)
+  ZH_FRAME_N_SRC = 4
+};
+
+struct ZhFrameLaunch {
+  const ZhFrameEntry *table;
+  const uint8_t *blob;
+  const uint8_t *src[ZH_FRAME_N_SRC];
+  uint8_t *out;
+  uint64_t sel_off, sel_len;              // store layout: the selector prefix in the blob
+  uint32_t n;                             // entries
+  uint32_t pieces;                        // 64 KiB pieces of the longest body: sizes the grid
+};
+
+#define ZH_FRAME_PIECE 65536u             // body bytes per workgroup step; the store layout's chunk
+
+#include <string>
+#include <vector>
+
+namespace zh {
+
+// What the coded sequence starts with (Compressor.postProcess, Compressor.cs:156-190): 0, or 1, len lo, len hi, pcomp
+std::vector<uint8_t> selector_prefix(const uint8_t *pcomp, size_t pcomp_len);
+
+// The bytes around one block's coded data (LibZPAQ.cs:296-323; BlockWriter::write_block): tag, block and segment header
+// with the size comment in `head`, end of segment (with the SHA-1 when `digest` gives its five words) and of block in `tail`.
+struct BlockFrame {
+  std::string head, tail;
+  BlockFrame(bool tag, uint8_t level, const uint8_t *hdr, size_t hdr_len, const char *filename, uint64_t plain_len,
+             const uint32_t *digest);
+};
+// Encoder.compress without a model (Encoder.cs:39-73): the decoded stream, `sel` then `pre`, in chunks of at most 65 536
+// bytes behind their 4-byte big-endian lengths.
+uint64_t store_body_len(uint64_t decoded);
+void write_store_body(uint8_t *w, const std::vector<uint8_t> &sel, const uint8_t *pre, uint64_t pre_len);
+
+struct FrameItem {                        // one block of a batch as the framing sees it
+  BlockFrame f;
+  uint32_t src;                           // where its body lies, and how many bytes (store layout: the pre-processed bytes)
+  uint64_t src_off, src_len;
+};
+
+struct FrameTable {
+  std::vector<ZhFrameEntry> entry;        // the blocks that fit under out_cap, in block order
+  std::vector<size_t> item;               // entry[e] frames item[e] of the batch
+  std::vector<uint8_t> blob;              // the selector (store layout), then head and tail of every entry
+  uint64_t sel_len = 0;
+  uint32_t pieces = 1;
+};
+
+// The frame table of a batch whose first block starts at stream offset `pos`: block_pos[j] (optional) is where item j
+// starts, dst_off the same for the blocks that fit in whole under out_cap; one that does not fit is left out, later ones
+// that fit are in.  `sel` non-NULL selects the store layout.  Returns the stream offset behind the batch.
+uint64_t build_frame_table(const std::vector<FrameItem> &items, const std::vector<uint8_t> *sel, uint64_t pos, uint64_t out_cap,
+                           FrameTable &T, uint64_t *block_pos);
+
+}  // namespace zh

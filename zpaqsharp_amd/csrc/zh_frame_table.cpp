@@ -1,0 +1,84 @@
+// zh_frame_table.cpp — zh_frame.h's host side: BlockFrame, the store layout and the frame table of a batch.  Plain C++,
+// no HIP: it links into libzpaqhip.so and, on its own, into the stand-alone test of the table.
+#include <string.h>
+
+#include <algorithm>
+
+#include "zh_frame.h"
+
+std::vector<uint8_t> zh::selector_prefix(const uint8_t *pcomp, size_t pcomp_len) {
+  if (!pcomp_len) return {0};
+  std::vector<uint8_t> sel{1, (uint8_t)(pcomp_len & 255), (uint8_t)(pcomp_len >> 8)};
+  sel.insert(sel.end(), pcomp, pcomp + pcomp_len);
+  return sel;
+}
+
+zh::BlockFrame::BlockFrame(bool tag, uint8_t level, const uint8_t *hdr, size_t hdr_len, const char *filename, uint64_t plain_len,
+                           const uint32_t *digest) : tail(4, '\0') {
+  static constexpr uint8_t kTag[13] = {0x37, 0x6b, 0x53, 0x74, 0xa0, 0x31, 0x83, 0xd3, 0x8c, 0xb2, 0x28, 0xb0, 0xd3};   // Compressor.cs:27-43
+  if (tag) head.append((const char *)kTag, 13);
+  head.append("zPQ", 3);
+  head.push_back((char)level);
+  head.push_back(1);
+  head.append((const char *)hdr, hdr_len);
+  head.push_back(1);
+  if (filename) head.append(filename);
+  head.push_back(0);
+  head.append(std::to_string(plain_len));
+  head.push_back(0);
+  head.push_back(0);
+  if (digest) {
+    tail.push_back((char)253);
+    for (int w = 0; w < 5; ++w)
+      for (int s = 24; s >= 0; s -= 8) tail.push_back((char)(digest[w] >> s));
+  } else tail.push_back((char)254);
+  tail.push_back((char)255);
+}
+
+uint64_t zh::store_body_len(uint64_t decoded) { return decoded + 4 * ((decoded + 65535) / 65536); }
+
+void zh::write_store_body(uint8_t *w, const std::vector<uint8_t> &sel, const uint8_t *pre, uint64_t pre_len) {
+  const uint64_t ns = sel.size(), dec = ns + pre_len;
+  for (uint64_t c = 0; c < dec; c += 65536) {
+    const uint64_t e = std::min<uint64_t>(c + 65536, dec), cl = e - c, p = std::max(c, ns);
+    *w++ = (uint8_t)(cl >> 24); *w++ = (uint8_t)(cl >> 16); *w++ = (uint8_t)(cl >> 8); *w++ = (uint8_t)cl;
+    if (c < ns) memcpy(w, sel.data() + c, std::min(ns, e) - c);
+    if (p < e) memcpy(w + (p - c), pre + (p - ns), e - p);
+    w += cl;
+  }
+}
+
+uint64_t zh::build_frame_table(const std::vector<FrameItem> &items, const std::vector<uint8_t> *sel, uint64_t pos, uint64_t out_cap,
+                               FrameTable &T, uint64_t *block_pos) {
+  T = FrameTable();
+  if (sel) {
+    T.blob = *sel;
+    T.sel_len = sel->size();
+  }
+  for (size_t j = 0; j < items.size(); ++j) {
+    const FrameItem &it = items[j];
+    const uint64_t decoded = T.sel_len + it.src_len, body = sel ? store_body_len(decoded) : it.src_len;
+    const uint64_t need = it.f.head.size() + body + it.f.tail.size();
+    if (block_pos) block_pos[j] = pos;
+    if (need <= out_cap && pos <= out_cap - need) {
+      ZhFrameEntry e;
+      memset(&e, 0, sizeof e);
+      e.dst_off = pos;
+      e.src = it.src;
+      e.src_off = it.src_off;
+      e.body_len = it.src_len;
+      e.store = sel ? 1 : 0;
+      e.head_off = T.blob.size();
+      e.head_len = (uint32_t)it.f.head.size();
+      T.blob.insert(T.blob.end(), it.f.head.begin(), it.f.head.end());
+      e.tail_off = T.blob.size();
+      e.tail_len = (uint32_t)it.f.tail.size();
+      T.blob.insert(T.blob.end(), it.f.tail.begin(), it.f.tail.end());
+      T.entry.push_back(e);
+      T.item.push_back(j);
+      T.pieces = (uint32_t)std::max<uint64_t>(T.pieces, (decoded + ZH_FRAME_PIECE - 1) / ZH_FRAME_PIECE);
+    }
+    pos += need;
+  }
+  return pos;
+}

@@ -292,7 +292,8 @@ int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, cons
   HIPCHK(plain_.alloc(plain));
   HIPCHK(desc_.alloc(nb * sizeof(ZhPreBlock)));
   HIPCHK(len_.alloc(nb * 8));
-  if (plain) HIPCHK(hipMemcpy(plain_.p, in_ + base, plain, hipMemcpyHostToDevice));
+  if (plain && in_dev_) HIPCHK(hipMemcpyAsync(plain_.p, in_ + base, plain, hipMemcpyDeviceToDevice, v.stream));
+  else if (plain) HIPCHK(hipMemcpy(plain_.p, in_ + base, plain, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(desc_.p, desc.data(), nb * sizeof(ZhPreBlock), hipMemcpyHostToDevice));
   if (np) {
     HIPCHK(pref_.alloc(np));
@@ -528,11 +529,12 @@ extern "C" int zpaqhip_bwt_blocks(zpaqhip_ctx *ctx, int doe8, const uint8_t *in,
   return preprocess_entry(ctx, args, kFlagBwt, Route::Bwt, nullptr, in, in_off, n_blocks, out, out_cap, out_len, out_off, err);
 }
 
-extern "C" int zpaqhip_compress_method_blocks(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *hdr, size_t hdr_len,
-                                              const uint8_t *pcomp, size_t pcomp_len, const uint8_t *in, const uint64_t *in_off,
-                                              size_t n_blocks, const char *const *filenames, uint8_t *out, size_t out_cap,
-                                              size_t *out_len, uint64_t *block_off, const zpaqhip_compress_opts *opts,
-                                              zpaqhip_err *err) {
+namespace {
+
+int compress_method_impl(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp,
+                         size_t pcomp_len, const uint8_t *in, const uint64_t *in_off, size_t n_blocks, const char *const *filenames,
+                         uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off, const zpaqhip_compress_opts *opts,
+                         zpaqhip_err *err, const DeviceEnds *dev) {
   if (!ctx || !hdr || !out_len || (!out && out_cap) || (n_blocks && !in_off) || (pcomp_len && !pcomp) || pcomp_len > 65535)
     return refuse(err);
   *out_len = 0;
@@ -540,7 +542,28 @@ extern "C" int zpaqhip_compress_method_blocks(zpaqhip_ctx *ctx, const int32_t *a
   int rc = parse_method(args, resolve_compress_opts(opts).flags, M, err);
   if (rc) return rc;
   if ((rc = check_blocks(M, in, in_off, n_blocks, err))) return rc;
-  DevPre P(M, in, in_off);
+  DevPre P(M, in, in_off, dev != nullptr);
   return compress_impl(ctx, hdr, hdr_len, pcomp, pcomp_len, in, in_off, n_blocks, nullptr, nullptr, filenames, out, out_cap, out_len,
-                       block_off, opts, &P, err);
+                       block_off, opts, &P, err, dev);
+}
+
+}  // namespace
+
+extern "C" int zpaqhip_compress_method_blocks(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *hdr, size_t hdr_len,
+                                              const uint8_t *pcomp, size_t pcomp_len, const uint8_t *in, const uint64_t *in_off,
+                                              size_t n_blocks, const char *const *filenames, uint8_t *out, size_t out_cap,
+                                              size_t *out_len, uint64_t *block_off, const zpaqhip_compress_opts *opts,
+                                              zpaqhip_err *err) {
+  return compress_method_impl(ctx, args, hdr, hdr_len, pcomp, pcomp_len, in, in_off, n_blocks, filenames, out, out_cap, out_len,
+                              block_off, opts, err, nullptr);
+}
+
+extern "C" int zpaqhip_compress_method_blocks_device(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *hdr, size_t hdr_len,
+                                                     const uint8_t *pcomp, size_t pcomp_len, const void *d_in, const uint64_t *in_off,
+                                                     size_t n_blocks, const char *const *filenames, void *d_out, size_t out_cap,
+                                                     size_t *out_len, uint64_t *block_off, const zpaqhip_compress_opts *opts,
+                                                     void *hip_stream, zpaqhip_err *err) {
+  const DeviceEnds dev{(hipStream_t)hip_stream};
+  return compress_method_impl(ctx, args, hdr, hdr_len, pcomp, pcomp_len, (const uint8_t *)d_in, in_off, n_blocks, filenames,
+                              (uint8_t *)d_out, out_cap, out_len, block_off, opts, err, &dev);
 }

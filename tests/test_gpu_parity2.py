@@ -102,6 +102,13 @@ def _raw_block(model: str, decoded: bytes) -> bytes:
     return s
 
 
+def _store_block(decoded: bytes) -> bytes:
+    """An unmodelled (n = 0) block whose stored bytes are exactly `decoded` (as test_eof_inside_the_priming_bytes_of_a_store_block)."""
+    hdr = zpaql.assemble("comp 0 0 0 0 0 hcomp halt end").header
+    body = (len(decoded).to_bytes(4, "big") + decoded if decoded else b"") + b"\0\0\0\0"
+    return TAG + b"zPQ" + bytes([2, 1]) + hdr + b"\x01name\0comment\0\0" + body + bytes([254, 255])
+
+
 @pytest.mark.parametrize("decoded,msg", [
     (b"", "Unexpected EOS"),                         # state 0: EOS where the PASS/PROG selector should be   (PostProcessor.cs:43)
     (b"\x02abc", "unknown post processing type"),    # selector > 1                                          (:45)
@@ -112,11 +119,16 @@ def _raw_block(model: str, decoded: bytes) -> bytes:
     (b"\x01\x05\x00\x38\x38", "Unexpected EOS"),     # state 4: EOS inside the program bytes                 (:68)
 ])
 def test_postprocessor_header_errors(ctx, decoded, msg):
-    for model in ("l1", "mid"):
-        s = _raw_block(model, decoded)
+    # every kernel's copy of the header states (zh_generic.hip's and zh_store.hip's is zh_core.h's pp_head_step): zh_cm / zh_chain / zh_nibble /
+    # zh_generic as routed for l1 and mid, zh_chain2's three instances (max at its default, mid and min at kernel=9), min at its
+    # default, and zh_store for an unmodelled block (default and kernel=10)
+    routes = [(model, _raw_block(model, decoded), kernels) for model, kernels in
+              (("l1", (0, 1, 3)), ("mid", (0, 1, 4, 9)), ("max", (0,)), ("min", (0, 9)))]
+    routes.append(("store", _store_block(decoded), (0, 10)))
+    for model, s, kernels in routes:
         with pytest.raises(oracle.OracleError, match=msg):
             oracle.decompress(s)
-        for kernel in (0, 1) + ((3,) if model == "l1" else (4,)):
+        for kernel in kernels:
             with pytest.raises(z.ZpaqError) as e:
                 ctx.decompress(s, kernel=kernel)
             assert msg in str(e.value), (model, kernel, str(e.value))

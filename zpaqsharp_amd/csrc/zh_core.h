@@ -186,6 +186,38 @@ ZH_HD inline int vm_run(Vm &z, uint32_t input, Sink *out, uint64_t budget) {
   return rc;
 }
 
+// ---- PostProcessor.write, the header states 0, 2, 3 and 4 (PostProcessor.cs:37-79) ----
+// State 1 (PASS) and state 5 (the program runs) belong to the decoder that owns the output.
+struct PpHead {
+  int state, hsize;    // PostProcessor.cs:12-16; hsize stays the PCOMP length (ZhSegResult.pp_state carries it in bits 8-23)
+  uint32_t len;        // PCOMP bytes loaded so far
+};
+enum { ZH_PP_MORE = 0, ZH_PP_LOADED = 1 };
+// c is 0..255 or -1; pp.state is 0, 2, 3 or 4.  Returns ZH_PP_MORE, a ZH_E_PP_* status, or ZH_PP_LOADED when c was the
+// program's last byte (the state is 5 then).  store(i, byte) puts byte i of the program where the caller keeps it:
+// which lanes store is the kernel's business.  (An if-chain in the order the kernels had it, inlined: their code stays.)
+template <class Store>
+ZH_HD inline __attribute__((always_inline)) int pp_head_step(PpHead &pp, int c, Store store) {
+  if (pp.state == 0) {
+    if (c < 0) return ZH_E_PP_EOS;
+    pp.state = c + 1;                                  // 1 = PASS, 2 = PROG
+    if (pp.state > 2) return ZH_E_PP_TYPE;
+  } else if (pp.state == 2) {
+    if (c < 0) return ZH_E_PP_EOS;
+    pp.hsize = c; pp.state = 3;
+  } else if (pp.state == 3) {
+    if (c < 0) return ZH_E_PP_EOS;
+    pp.hsize += c * 256;
+    if (pp.hsize < 1) return ZH_E_PP_EMPTY;
+    pp.len = 0; pp.state = 4;
+  } else {                                             // state 4: PCOMP bytes
+    if (c < 0) return ZH_E_PP_EOS;
+    store(pp.len, (uint8_t)c);
+    if ((int)++pp.len == pp.hsize) { pp.state = 5; return ZH_PP_LOADED; }
+  }
+  return ZH_PP_MORE;
+}
+
 // ---- model-independent arithmetic (Predictor.cs:496-543, intended bounds) ----
 ZH_HD inline int clamp2k(int x) { return x < -2048 ? -2048 : x > 2047 ? 2047 : x; }
 ZH_HD inline int clamp512k(int x) {

@@ -1,10 +1,12 @@
 // zh_dev.h — device-side helpers shared by the lane-parallel kernels (zh_cm.hip,
 // zh_chain.hip): wave-uniform value pinning, the register-buffered stream reader, the
-// register-parked plaintext writer and the hand-scheduled scalar arithmetic-decoder step.
+// register-parked plaintext writer, the hand-scheduled scalar arithmetic-decoder step, and the two per-segment result
+// records (zh_store.hip, zh_generic.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "zh_core.h"
 #include "zh_model.h"
 
 namespace zhdev {
@@ -237,6 +239,31 @@ __device__ __forceinline__ int wave_sum(int v) {
   v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1,3
   v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2,3
   return (int)rdlane((uint32_t)v, 63);
+}
+
+// ---- per-segment results ----
+// A segment behind one that failed (Decompresser.cs:121-153 never reaches it).
+__device__ __forceinline__ void seg_skipped(ZhSegResult *results, uint32_t si, int pp_state, uint64_t out_off, uint32_t lane) {
+  if (lane == 0) {
+    ZhSegResult res;
+    res.status = ZH_E_SKIPPED; res.pp_state = (uint32_t)pp_state; res.out_off = out_off; res.out_len = 0; res.in_used = 0;
+    results[si] = res;
+  }
+}
+// A segment that ran: produced0 / produced = bytes of the block written before / after it (they count past out_cap).
+// Output beyond the capacity is a status of its own and does not stop the block; any other status does: returns `failed`.
+__device__ __forceinline__ int seg_done(ZhSegResult *results, uint32_t si, int status, const zhcore::PpHead &pp, uint64_t out_off, uint64_t out_cap,
+                                        uint64_t produced0, uint64_t produced, uint64_t in_used, uint32_t lane, int failed) {
+  if (!status && produced > out_cap) status = ZH_E_OUTPUT_FULL;
+  if (status && status != ZH_E_OUTPUT_FULL) failed = 1;
+  if (lane == 0) {
+    ZhSegResult res;
+    res.status = status; res.pp_state = (uint32_t)pp.state | (uint32_t)pp.hsize << 8;   // PCOMP length rides in bits 8-23
+    res.out_off = out_off + produced0; res.out_len = produced - produced0;
+    res.in_used = in_used;
+    results[si] = res;
+  }
+  return failed;
 }
 
 // In-kernel stamps (diagnostic build only: *_prof kernels): cycles spent per

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "zh_core.h"
+#include "zh_dev.h"
 #include "zh_model.h"
 #include "zh_zpaql_pcomp.h"
 
@@ -43,61 +44,37 @@ __device__ __forceinline__ int decode_bit(Coder &d, Src &in, uint32_t p) {
   return y;
 }
 
-struct PostProc {      // PostProcessor.cs:12-16
-  int state, hsize;
-  uint32_t plen;       // PCOMP bytes loaded so far
+struct PostProc {
+  PpHead hd;           // PostProcessor.cs:12-16 and the header states (zh_core.h)
   uint32_t native;     // zh_zpaql_pcomp.h: ahead-of-time translation of the loaded program, 0 = interpret
   Vm z;
 };
 
 // PostProcessor.cs:37-86.  c is 0..255 or -1.  Returns 0 or a status.
 __device__ int pp_write(PostProc &pp, int c, Sink &out, const ZhModel *M, uint8_t *slot, uint64_t budget, uint32_t *pimm) {
-  switch (pp.state) {
-    case 0:
-      if (c < 0) return ZH_E_PP_EOS;
-      pp.state = c + 1;
-      if (pp.state > 2) return ZH_E_PP_TYPE;
-      break;
-    case 1:
-      if (c >= 0) sink_put(out, (uint32_t)c);
-      break;
-    case 2:
-      if (c < 0) return ZH_E_PP_EOS;
-      pp.hsize = c;
-      pp.state = 3;
-      break;
-    case 3:
-      if (c < 0) return ZH_E_PP_EOS;
-      pp.hsize += c * 256;
-      if (pp.hsize < 1) return ZH_E_PP_EMPTY;
-      pp.plen = 0;
-      pp.state = 4;
-      break;
-    case 4: {
-      if (c < 0) return ZH_E_PP_EOS;
-      uint8_t *buf = slot + M->pz_off + ZH_CODE_PAD;
-      buf[pp.plen++] = (uint8_t)c;
-      if ((int)pp.plen == pp.hsize) {
-        // z.initp(): H/M were zeroed with the slot; registers start at 0 (ZPAQL.cs:1010-1026)
-        pp.z.prog = buf;
-        pp.z.len = pp.plen;
-        pp.z.a = pp.z.b = pp.z.c = pp.z.d = pp.z.f = 0;
-        pp.native = zh_pcomp_lookup(buf, pp.plen);
-        zh_pcomp_operands(pp.native, buf, pimm);
-        pp.state = 5;
-      }
-      break;
-    }
-    default:
-      if (pp.native) {
-        ZhPcRegs r{pp.z.a, pp.z.b, pp.z.c, pp.z.d, pp.z.f, 0};
-        r = zh_pcomp_call(pp.native, r, (uint32_t)c, pp.z.m, pp.z.mmask, pp.z.h, pp.z.hmask, pp.z.r, &out, budget, pimm);
-        pp.z.a = r.a; pp.z.b = r.b; pp.z.c = r.c; pp.z.d = r.d; pp.z.f = r.f;
-        return r.rc;
-      }
-      return vm_run(pp.z, (uint32_t)c, &out, budget);
+  if (pp.hd.state == 1) {
+    if (c >= 0) sink_put(out, (uint32_t)c);
+    return 0;
   }
-  return 0;
+  if (pp.hd.state != 5) {
+    uint8_t *buf = slot + M->pz_off + ZH_CODE_PAD;
+    const int rc = pp_head_step(pp.hd, c, [&](uint32_t i, uint8_t v) { buf[i] = v; });
+    if (rc != ZH_PP_LOADED) return rc;
+    // z.initp(): H/M were zeroed with the slot; registers start at 0 (ZPAQL.cs:1010-1026)
+    pp.z.prog = buf;
+    pp.z.len = pp.hd.len;
+    pp.z.a = pp.z.b = pp.z.c = pp.z.d = pp.z.f = 0;
+    pp.native = zh_pcomp_lookup(buf, pp.hd.len);
+    zh_pcomp_operands(pp.native, buf, pimm);
+    return 0;
+  }
+  if (pp.native) {
+    ZhPcRegs r{pp.z.a, pp.z.b, pp.z.c, pp.z.d, pp.z.f, 0};
+    r = zh_pcomp_call(pp.native, r, (uint32_t)c, pp.z.m, pp.z.mmask, pp.z.h, pp.z.hmask, pp.z.r, &out, budget, pimm);
+    pp.z.a = r.a; pp.z.b = r.b; pp.z.c = r.c; pp.z.d = r.d; pp.z.f = r.f;
+    return r.rc;
+  }
+  return vm_run(pp.z, (uint32_t)c, &out, budget);
 }
 
 __device__ void fill16(uint8_t *dst, uint64_t bytes, uint4 pat, uint32_t lane) {
@@ -259,7 +236,7 @@ extern "C" __global__ __launch_bounds__(64) void zh_decode_generic(ZhLaunch L) {
       if (n) { d.low = 1; d.high = 0xFFFFFFFFu; d.curr = 0; }
       else d.low = d.high = d.curr = 0;
       PostProc pp;
-      pp.state = 0; pp.hsize = 0; pp.plen = 0; pp.native = 0;
+      pp.hd = PpHead{0, 0, 0}; pp.native = 0;
       pp.z.a = pp.z.b = pp.z.c = pp.z.d = pp.z.f = 0;
       pp.z.prog = nullptr; pp.z.len = 0;
       pp.z.m = slot + M->pm_off; pp.z.mmask = (uint32_t)((1ull << M->pm) - 1);
@@ -272,13 +249,7 @@ extern "C" __global__ __launch_bounds__(64) void zh_decode_generic(ZhLaunch L) {
       int failed = 0;
       for (uint32_t s = 0; s < bd.n_seg; ++s) {
         const uint32_t si = bd.first_seg + s;
-        ZhSegResult res;
-        res.out_off = bd.out_off + out.len;
-        if (failed) {
-          res.status = ZH_E_SKIPPED; res.pp_state = (uint32_t)pp.state; res.out_len = 0; res.in_used = 0;
-          L.results[si] = res;
-          continue;
-        }
+        if (failed) { zhdev::seg_skipped(L.results, si, pp.hd.state, bd.out_off + out.len, 0u); continue; }
         const ZhSegDesc sd = L.segs[si];
         Src in;
         // Decoder.get() reads the caller's Reader, which does not stop at the segment end
@@ -292,13 +263,9 @@ extern "C" __global__ __launch_bounds__(64) void zh_decode_generic(ZhLaunch L) {
           int rc = pp_write(pp, c, out, M, slot, L.budget, S.pimm);
           if (rc) { status = rc; break; }
           if (c == -1) break;
-          if ((L.flags & ZH_LAUNCH_PP_ONLY) && (pp.state == 1 || pp.state == 5)) { status = ZH_E_STOPPED; break; }   // pcomp() read-back
+          if ((L.flags & ZH_LAUNCH_PP_ONLY) && (pp.hd.state == 1 || pp.hd.state == 5)) { status = ZH_E_STOPPED; break; }   // pcomp() read-back
         }
-        if (!status && out.len > out.cap) status = ZH_E_OUTPUT_FULL;
-        if (status && status != ZH_E_OUTPUT_FULL) failed = 1;
-        res.status = status; res.pp_state = (uint32_t)pp.state | (uint32_t)pp.hsize << 8; res.out_len = out.len - start;
-        res.in_used = (uint64_t)(in.p - (L.in + sd.in_off));
-        L.results[si] = res;
+        failed = zhdev::seg_done(L.results, si, status, pp.hd, bd.out_off, out.cap, start, out.len, (uint64_t)(in.p - (L.in + sd.in_off)), 0u, failed);
       }
     }
     __syncthreads();

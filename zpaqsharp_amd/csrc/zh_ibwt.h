@@ -1,20 +1,81 @@
 // zh_ibwt.h — the inverse BWT of the reference's `bwtrle` post-processor (LibZPAQ.cs:642-795) as a wave-wide device function,
-// shared by zh_store.hip (unmodelled BWT blocks) and zh_nibble.hip (the modelled BWT method `ci1`).
+// shared by zh_store.hip (unmodelled BWT blocks) and zh_nibble.hip (the modelled BWT method `ci1`), and the operand tables of
+// the reference's post-processors with the test made before one is taken for the reference's own: zh_ref_program.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "zh_dev.h"
+#include "zh_zpaql_pcomp.h"
 
 namespace {
 using zhdev::uni;
 
-// operands of the reference's two bwtrle programs (zh_zpaql_pcomp.h lists the disassembly; zh_store.hip says why every operand
-// is compared): blocks up to 16 MiB / any size
-// ... and of its lzpre program (LibZPAQ.cs:575-639)
+// ---- "is this PCOMP one of the reference's own programs, operand for operand?" ----
+// zh_pcomp_lookup matches a program's STRUCTURE (zh_zpaql_pcomp.h lists the disassembly) and zh_pcomp_operands extracts
+// its operands; a program that differs in ANY operand that is not a parameter of the method is not the reference's, and
+// the wave-wide shortcuts of zh_store.hip and zh_nibble.hip must not take it.  Of this header's two includers only
+// zh_store.hip calls zh_ref_program and reads kLazy302 / kLazy337 / kE8Tail; zh_nibble.hip reads kLzpre108, kBwt123 and kBwt106
+// and compares them itself (the note at its kLzpre165 says why).
+// lzpre (LibZPAQ.cs:575-639): [5] is the minimum match length
 __device__ const uint8_t kLzpre108[12] = {255, 0, 6, 1, 63, 0 /* minimum match */, 1, 0, 2, 8, 8, 0};
+// lazy2 with rb = 0 / rb > 0 (blocks over 16 MiB): [26..35] = 5, rb-1, (1<<rb)-1, rb, rb, 2, 2, 1, rb, (1<<rb)-1
+__device__ const uint8_t kLazy302[43] = {255, 8, 0, 1, 3, 0, 3, 2, 7, 3, 5, 1, 2, 3, 1, 2, 1, 1, 1, 1, 1, 1, 2, 3, 2, 2,
+                                          2, 1, 0, 3, 1, 1, 1, 1, 1, 1, 1, 4, 4, 7, 8, 8, 0};
+__device__ const uint8_t kLazy337[51] = {255, 8, 0, 1, 3, 0, 3, 2, 7, 3, 5, 1, 2, 3, 1, 2, 1, 1, 1, 1, 1, 1, 2, 3, 2, 5,
+                                          5, 0, 0, 0, 0, 2, 2, 1, 0, 0, 0, 3, 1, 1, 1, 1, 1, 1, 1, 4, 4, 7, 8, 8, 0};
+// bwtrle (LibZPAQ.cs:642-795): blocks up to 16 MiB / any size
 __device__ const uint8_t kBwt123[11] = {255, 8, 8, 8, 0, 255, 1, 255, 8, 0, 8};
 __device__ const uint8_t kBwt106[9] = {255, 8, 8, 8, 0, 255, 1, 255, 0};
+// The E8E9 forms are the plain ones plus the end-of-segment loop (LibZPAQ.cs:441-462, :581-601): a+= 4, a&= 254, a== 232,
+// a&= 254, a== 0, a<<= 8 (2), a>>= 8 (2).  Its nine operands stand behind the plain form's first in lzpre 165 and lazy2
+// 360 / 395 (the plain form's operand k >= 1 is word 9 + k).  (bwtrle 182, bwtrle 123's eleven and then the loop's, is
+// taken by zh_nibble.hip alone, which compares it itself.)
+__device__ const uint8_t kE8Tail[9] = {4, 254, 232, 254, 0, 8, 8, 8, 8};
+
+enum : uint32_t { kRefNone = 0, kRefLzpre, kRefLazy2, kRefBwtrle };
+struct ZhRefProg {
+  uint32_t prog;       // kRef*: whose structure the program has
+  bool same;           // ... and every operand that is not a parameter of the method is the reference's
+  bool e8;             // the form with E8E9
+  uint32_t minlen;     // lzpre: minimum match length
+  uint32_t rb;         // lazy2: low offset bits coded raw (0 in the forms for blocks up to 16 MiB)
+};
+// id = zh_pcomp_lookup's, words = zh_pcomp_operands' (visible to every lane).  The answer is the same in every lane.
+__device__ __attribute__((noinline)) ZhRefProg zh_ref_program(uint32_t id, const uint32_t *words) {
+  ZhRefProg r{kRefNone, false, false, 0u, 0u};
+  const bool e8_lz = id == ZH_PCOMP_LZPRE_165 || id == ZH_PCOMP_LAZY2_360 || id == ZH_PCOMP_LAZY2_395;
+  auto at = [&](int k) { return uni(words[e8_lz && k ? 9 + k : k]); };   // operand k of the plain form
+  bool ok = true;
+  if (e8_lz) for (int k = 0; k < 9; ++k) ok = ok && uni(words[1 + k]) == kE8Tail[k];
+  uint32_t prog = kRefNone;
+  if (id == ZH_PCOMP_LZPRE_108 || id == ZH_PCOMP_LZPRE_165) {
+    prog = kRefLzpre;
+    for (int k = 0; k < 12; ++k) ok = ok && (k == 5 || at(k) == kLzpre108[k]);
+    r.minlen = at(5);
+  } else if (id == ZH_PCOMP_LAZY2_302 || id == ZH_PCOMP_LAZY2_360) {
+    prog = kRefLazy2;
+    for (int k = 0; k < 43; ++k) ok = ok && at(k) == kLazy302[k];
+  } else if (id == ZH_PCOMP_LAZY2_337 || id == ZH_PCOMP_LAZY2_395) {
+    prog = kRefLazy2;
+    r.rb = at(27) + 1u;
+    ok = ok && r.rb >= 1u && r.rb <= 8u;
+    const uint32_t mk = (1u << (r.rb & 31u)) - 1u;
+    for (int k = 0; k < 51 && ok; ++k) {
+      uint32_t want = kLazy337[k];
+      if (k == 27) want = r.rb - 1u;
+      else if (k == 28 || k == 35) want = mk;
+      else if (k == 29 || k == 30 || k == 34) want = r.rb;
+      ok = at(k) == want;
+    }
+  } else if (id == ZH_PCOMP_BWTRLE_123 || id == ZH_PCOMP_BWTRLE_106) {
+    prog = kRefBwtrle;
+    const int nk = id == ZH_PCOMP_BWTRLE_106 ? 9 : 11;
+    for (int k = 0; k < nk; ++k) ok = ok && at(k) == (id == ZH_PCOMP_BWTRLE_106 ? kBwt106[k] : kBwt123[k]);
+  }
+  r.prog = prog; r.same = ok && prog != kRefNone; r.e8 = e8_lz;
+  return r;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Inverse BWT of `bwtrle` (LibZPAQ.cs:642-795) for a well-formed block, wave-wide.

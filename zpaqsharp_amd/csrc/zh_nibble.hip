@@ -1226,6 +1226,9 @@ __device__ __attribute__((noinline)) void nb_e8_pass(const ZhLaunch &L, LDS &S, 
 }
 
 // operands of the reference's lzpre / bwtrle with E8E9: the plain form's (zh_ibwt.h) and the nine of the loop
+// (compared here, not through zh_ibwt.h's zh_ref_program, which zh_store.hip uses: with that call in decode_nibble_body three
+// instances of nb_fast were no longer the parent's outside their loops — profiles/pp_front/resources.txt (d); re-measure before
+// wiring it up)
 __device__ const uint8_t kLzpre165[21] = {255, 4, 254, 232, 254, 0, 8, 8, 8, 8, 0, 6, 1, 63, 0 /* minimum match */, 1, 0, 2, 8, 8, 0};
 __device__ const uint8_t kBwt182[20] = {255, 8, 8, 8, 0, 255, 1, 255, 8, 0, 8, 4, 254, 232, 254, 0, 8, 8, 8, 8};
 

@@ -125,22 +125,6 @@ __device__ __forceinline__ int rd_chunk(Rd &r, StoreLds &S, uint32_t lane) {
   return 0;
 }
 
-// operands of the reference's programs (zh_zpaql_pcomp.h lists the disassembly): a block whose program differs in ANY
-// operand that is not a parameter of the method is not taken here
-// (kLzpre108: zh_ibwt.h, shared with zh_nibble.hip)
-__device__ const uint8_t kLazy302[43] = {255, 8, 0, 1, 3, 0, 3, 2, 7, 3, 5, 1, 2, 3, 1, 2, 1, 1, 1, 1, 1, 1, 2, 3, 2, 2,
-                                          2, 1, 0, 3, 1, 1, 1, 1, 1, 1, 1, 4, 4, 7, 8, 8, 0};
-// lazy2 with rb > 0 (blocks over 16 MiB): [26..35] = 5, rb-1, (1<<rb)-1, rb, rb, 2, 2, 1, rb, (1<<rb)-1
-__device__ const uint8_t kLazy337[51] = {255, 8, 0, 1, 3, 0, 3, 2, 7, 3, 5, 1, 2, 3, 1, 2, 1, 1, 1, 1, 1, 1, 2, 3, 2, 5,
-                                          5, 0, 0, 0, 0, 2, 2, 1, 0, 0, 0, 3, 1, 1, 1, 1, 1, 1, 1, 4, 4, 7, 8, 8, 0};
-
-// the end-of-segment loop of the E8E9 forms (LibZPAQ.cs:441-462, :581-601): a+= 4, a&= 254, a== 232, a&= 254, a== 0, a<<= 8 (2), a>>= 8 (2)
-__device__ const uint8_t kE8Tail[9] = {4, 254, 232, 254, 0, 8, 8, 8, 8};
-
-// bwtrle (LibZPAQ.cs:642-795), the two list traversals without E8E9: 16 MiB blocks at most / any size
-
-enum : uint32_t { kProgNone = 0, kProgLzpre = 1, kProgLazy2 = 2, kProgBwt = 3 };
-
 // ---------------------------------------------------------------------------------------------------------------
 // FLUSHER WAVE: ring -> Writer and M
 // ---------------------------------------------------------------------------------------------------------------
@@ -318,7 +302,7 @@ __device__ __attribute__((noinline)) void lz_window(StoreLds &S, Lz &Z, uint32_t
       const uint32_t kk = k++;
       return (rdlane(cur, kk >> 2) >> ((kk & 3u) * 8u)) & 255u;
     };
-    if (prog == kProgLzpre) {
+    if (prog == kRefLzpre) {
       // lzpre (LibZPAQ.cs:575-639): d = state, b = ptr, R1 = len, R2 = offset so far
       const uint32_t kend = avail - k < left ? avail : k + left;        // the window or the chunk ends here
       while (k < kend && !lost) {
@@ -713,8 +697,8 @@ extern "C" __global__ __launch_bounds__(128) void zh_decode_store(ZhLaunch L) {
 
     uint32_t wp = 0, wpub = 0;                          // bytes produced by this block = ring position = Writer position; last published
     uint32_t seg_base = 0;                              // ... when the segment began: the program's ptr = wp - seg_base
-    int pp_state = 0, pp_hsize = 0;                      // PostProcessor (PostProcessor.cs:12-16)
-    uint32_t pp_len = 0, prog = kProgNone;
+    PpHead pp{0, 0, 0};                                  // PostProcessor (PostProcessor.cs:12-16)
+    uint32_t prog = kRefNone;                            // the reference's program the block runs (zh_ibwt.h)
     uint32_t minlen = 0, rb = 0, bw_n = 0;               // (bwtrle: bytes of the segment collected in M)
     bool retry = false, failed = false, lost = false;
     bool e8 = false;                                    // an E8E9 form: the Writer gets its bytes at the end of a segment (e8_pass)
@@ -756,14 +740,7 @@ extern "C" __global__ __launch_bounds__(128) void zh_decode_store(ZhLaunch L) {
       const uint32_t si = first_seg + s;
       const uint32_t produced0 = wp;
       int status = 0;
-      if (failed) {
-        if (lane == 0) {
-          ZhSegResult res;
-          res.status = ZH_E_SKIPPED; res.pp_state = (uint32_t)pp_state; res.out_off = b_out_off + produced0; res.out_len = 0; res.in_used = 0;
-          L.results[si] = res;
-        }
-        continue;
-      }
+      if (failed) { seg_skipped(L.results, si, pp.state, b_out_off + produced0, lane); continue; }
       const uint64_t seg_off = uni64(L.segs[si].in_off);
       Rd r;
       r.in.stream = L.in; r.in.total = L.in_total; r.in.cbase = 0; r.in.k = 0; r.in.avail = 0; r.in.cur = 0;
@@ -774,19 +751,19 @@ extern "C" __global__ __launch_bounds__(128) void zh_decode_store(ZhLaunch L) {
 
       for (;;) {
         // (one value per wave, said once per round: the state machine below then runs on the scalar unit)
-        pp_state = (int)uni((uint32_t)pp_state); prog = uni(prog);
+        pp.state = (int)uni((uint32_t)pp.state); prog = uni(prog);
         wp = uni(wp); wpub = uni(wpub); r.left = uni(r.left);
         r.in.k = uni(r.in.k); r.in.avail = uni(r.in.avail); r.in.cbase = uni64(r.in.cbase); r.kdisc = uni(r.kdisc);
         rb = uni(rb); minlen = uni(minlen); fpos_seen = uni(fpos_seen); seg_base = uni(seg_base); bw_n = uni(bw_n);
         if (UNLIKELY(lost)) break;
         if (UNLIKELY(wp > 0xF0000000u)) { retry = true; break; }      // (positions are 32 bits)
-        if (wp - wpub >= 1024u && pp_state == 5) publish();            // the flusher follows in steps of 1 KiB
+        if (wp - wpub >= 1024u && pp.state == 5) publish();            // the flusher follows in steps of 1 KiB
         // the chunk the next byte comes from (Decoder.decompress, store path: header when the last chunk is used up)
         const int hrc = rd_chunk(r, S, lane);
         if (hrc == kDamaged) { retry = true; break; }
         const bool eos = hrc == kEos;
         // ---- PASS: the chunks' payload is the plaintext (copied past the ring: the flusher has nothing to do)
-        if (pp_state == 1) {
+        if (pp.state == 1) {
           if (eos) break;
           const uint64_t from = in_pos(r.in);
           const uint32_t n = r.left;
@@ -806,7 +783,7 @@ extern "C" __global__ __launch_bounds__(128) void zh_decode_store(ZhLaunch L) {
           continue;
         }
         // ---- bwtrle: the segment is collected in M (`*b=a b++`), the inverse BWT runs at its end
-        if (pp_state == 5 && prog == kProgBwt) {
+        if (pp.state == 5 && prog == kRefBwtrle) {
           if (!eos) {
             const uint64_t from = in_pos(r.in);
             const uint32_t n = r.left;
@@ -834,7 +811,7 @@ extern "C" __global__ __launch_bounds__(128) void zh_decode_store(ZhLaunch L) {
           break;
         }
         // ---- a program: the bytes of the window, as long as the chunk and the window last (lz_window)
-        if (pp_state == 5 && !eos) {
+        if (pp.state == 5 && !eos) {
           if (r.in.k >= r.in.avail) { rd_seek(r, S, in_pos(r.in), lane); if (r.in.k >= r.in.avail) { retry = true; break; } continue; }
           if (lane == 0) {
             S.z.k = r.in.k; S.z.avail = r.in.avail; S.z.left = r.left; S.z.kdisc = r.kdisc;
@@ -852,131 +829,61 @@ extern "C" __global__ __launch_bounds__(128) void zh_decode_store(ZhLaunch L) {
         // ---- one decoded byte (the end of the segment for a program; the post-processor's header)
         int c = -1;
         if (!eos) { --r.left; c = rd_byte(r, S, lane); }
-        if (pp_state == 5) {
+        if (pp.state == 5) {
           // a> 255: the programs reset their state (ptr = 0: the next segment's base) and halt
           if (lane == 0) { S.z.bits = 0; S.z.nb = 0; S.z.st = 0; S.z.len = 0; S.z.mbits = 0; S.z.off = 0; }
           break;
         }
         // ---- PostProcessor.write, states 0 and 2-4 (PostProcessor.cs:37-79)
-        if (pp_state == 0) {
-          if (c < 0) { status = ZH_E_PP_EOS; break; }
-          pp_state = c + 1;
-          if (pp_state > 2) { status = ZH_E_PP_TYPE; break; }
-        } else if (pp_state == 2) {
-          if (c < 0) { status = ZH_E_PP_EOS; break; }
-          pp_hsize = c; pp_state = 3;
-        } else if (pp_state == 3) {
-          if (c < 0) { status = ZH_E_PP_EOS; break; }
-          pp_hsize += c * 256;
-          if (pp_hsize < 1) { status = ZH_E_PP_EMPTY; break; }
-          pp_len = 0; pp_state = 4;
-        } else {                                        // state 4: the program's bytes
-          if (c < 0) { status = ZH_E_PP_EOS; break; }
-          if (lane == 0) pzbuf[pp_len] = (uint8_t)c;
-          if ((int)++pp_len == pp_hsize) {
+        const int prc = pp_head_step(pp, c, [&](uint32_t i, uint8_t v) { if (lane == 0) pzbuf[i] = v; });
+        if (prc < 0) { status = prc; break; }
+        if (prc == ZH_PP_LOADED) {
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+          __builtin_amdgcn_s_waitcnt(0);
+          const uint32_t id = uni(zh_pcomp_lookup(pzbuf, pp.len));
+          zh_pcomp_operands(id, pzbuf, S.words);
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+          const ZhRefProg rp = zh_ref_program(id, S.words);
+          // lzpre, lazy2 and bwtrle as the reference writes them; the E8E9 forms of lzpre and lazy2 on request and with an M
+          // that e8_pass can read in dwords; bwtrle with a list (H) that 32 bits can index
+          bool ok = uni(rp.prog) != kRefNone && (!rp.e8 || (L.flags & ZH_LAUNCH_STORE_E8));
+          if (ok) { prog = uni(rp.prog); minlen = uni(rp.minlen); rb = uni(rp.rb); e8 = uni(rp.e8 ? 1u : 0u) != 0u; }
+          ok = ok && rp.same;
+          if (rp.e8) ok = ok && pmb >= 2u;
+          if (rp.prog == kRefBwtrle) ok = ok && uni(Mo->ph) <= 31u;
+          ok = uni(ok ? 1u : 0u) != 0u;
+          // every other program (and an M that 32 bits of mask cannot address) is the generic kernel's
+          if (!ok || pmb > 31u) { retry = true; break; }
+          {                                             // ZPAQL.initp: M starts as zeros (ZPAQL.cs:1010-1026)
+            uint4 *q = reinterpret_cast<uint4 *>(slot + uni64(Mo->pm_off));
+            const uint64_t n16 = ((uint64_t)mmask + 1u) / 16u;
+            for (uint64_t i = lane; i < n16; i += 64) q[i] = make_uint4(0, 0, 0, 0);
+            if (mmask < 15u) { if (lane <= mmask) (slot + uni64(Mo->pm_off))[lane] = 0; }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
             __builtin_amdgcn_s_waitcnt(0);
-            const uint32_t id = uni(zh_pcomp_lookup(pzbuf, pp_len));
-            zh_pcomp_operands(id, pzbuf, S.words);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            bool ok = false;
-            if (id == ZH_PCOMP_LZPRE_108) {
-              ok = true;
-              for (int k = 0; k < 12; ++k) ok = ok && (k == 5 || S.words[k] == kLzpre108[k]);
-              minlen = uni(S.words[5]); prog = kProgLzpre;
-            } else if (id == ZH_PCOMP_LAZY2_302) {
-              ok = true;
-              for (int k = 0; k < 43; ++k) ok = ok && S.words[k] == kLazy302[k];
-              rb = 0; prog = kProgLazy2;
-            } else if (id == ZH_PCOMP_LAZY2_337) {
-              rb = uni(S.words[27]) + 1u;
-              ok = rb >= 1u && rb <= 8u;
-              const uint32_t mk = (1u << rb) - 1u;
-              for (int k = 0; k < 51 && ok; ++k) {
-                uint32_t want = kLazy337[k];
-                if (k == 27) want = rb - 1u;
-                else if (k == 28 || k == 35) want = mk;
-                else if (k == 29 || k == 30 || k == 34) want = rb;
-                ok = S.words[k] == want;
-              }
-              prog = kProgLazy2;
-            }
-            else if ((L.flags & ZH_LAUNCH_STORE_E8) && (id == ZH_PCOMP_LZPRE_165 || id == ZH_PCOMP_LAZY2_360 || id == ZH_PCOMP_LAZY2_395)) {
-              // the E8E9 forms: words[0] = 255, the nine operands of the end-of-segment loop, then the plain form's from [1] on
-              ok = S.words[0] == 255u;
-              for (int k = 0; k < 9; ++k) ok = ok && S.words[1 + k] == kE8Tail[k];
-              if (id == ZH_PCOMP_LZPRE_165) {
-                for (int k = 1; k < 12; ++k) ok = ok && (k == 5 || S.words[9 + k] == kLzpre108[k]);
-                minlen = uni(S.words[9 + 5]); prog = kProgLzpre;
-              } else if (id == ZH_PCOMP_LAZY2_360) {
-                for (int k = 1; k < 43; ++k) ok = ok && S.words[9 + k] == kLazy302[k];
-                rb = 0; prog = kProgLazy2;
-              } else {
-                rb = uni(S.words[9 + 27]) + 1u;
-                ok = ok && rb >= 1u && rb <= 8u;
-                const uint32_t mk = (1u << (rb & 31u)) - 1u;
-                for (int k = 1; k < 51 && ok; ++k) {
-                  uint32_t want = kLazy337[k];
-                  if (k == 27) want = rb - 1u;
-                  else if (k == 28 || k == 35) want = mk;
-                  else if (k == 29 || k == 30 || k == 34) want = rb;
-                  ok = S.words[9 + k] == want;
-                }
-                prog = kProgLazy2;
-              }
-              ok = ok && pmb >= 2u;                      // (e8_pass reads M in dwords)
-              e8 = true;
-            }
-            else if (id == ZH_PCOMP_BWTRLE_123 || id == ZH_PCOMP_BWTRLE_106) {
-              ok = true;
-              const int nk = id == ZH_PCOMP_BWTRLE_123 ? 11 : 9;
-              for (int k = 0; k < nk; ++k) ok = ok && S.words[k] == (id == ZH_PCOMP_BWTRLE_123 ? kBwt123[k] : kBwt106[k]);
-              ok = ok && uni(Mo->ph) <= 31u;
-              prog = kProgBwt;
-            }
-            ok = uni(ok ? 1u : 0u) != 0u;
-            // every other program (and an M that 32 bits of mask cannot address) is the generic kernel's
-            if (!ok || pmb > 31u) { retry = true; break; }
-            {                                           // ZPAQL.initp: M starts as zeros (ZPAQL.cs:1010-1026)
-              uint4 *q = reinterpret_cast<uint4 *>(slot + uni64(Mo->pm_off));
-              const uint64_t n16 = ((uint64_t)mmask + 1u) / 16u;
-              for (uint64_t i = lane; i < n16; i += 64) q[i] = make_uint4(0, 0, 0, 0);
-              if (mmask < 15u) { if (lane <= mmask) (slot + uni64(Mo->pm_off))[lane] = 0; }
-              __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-              __builtin_amdgcn_s_waitcnt(0);
-            }
-            if (lane == 0) {
-              S.z.bits = S.z.nb = S.z.st = S.z.len = S.z.mbits = S.z.r5 = S.z.off = 0;
-              S.z.rb = rb; S.z.minlen = minlen; S.z.mmask = mmask; S.z.prog = prog;
-              S.m_only = e8 ? 1u : 0u;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            pp_state = 5;
           }
+          if (lane == 0) {
+            S.z.bits = S.z.nb = S.z.st = S.z.len = S.z.mbits = S.z.r5 = S.z.off = 0;
+            S.z.rb = rb; S.z.minlen = minlen; S.z.mmask = mmask; S.z.prog = prog;
+            S.m_only = e8 ? 1u : 0u;
+          }
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         }
       }
 
       // ---- end of the segment: everything out of the ring before the results are written and M is read again
       if (flusher_on && !lost) {
-        if (pp_state == 1 || prog == kProgBwt) { st_put0(&S.skip_to, wp); wait_flushed(wp); }     // (PASS and the inverse BWT wrote the Writer themselves)
+        if (pp.state == 1 || prog == kRefBwtrle) { st_put0(&S.skip_to, wp); wait_flushed(wp); }     // (PASS and the inverse BWT wrote the Writer themselves)
         else flush_all();
       }
-      if (e8 && !retry && !lost && pp_state == 5) {      // the program's loop over what the segment wrote
+      if (e8 && !retry && !lost && pp.state == 5) {      // the program's loop over what the segment wrote
         const uint32_t d = wp - seg_base;
         if (d > mmask + 1u) retry = true;                // (it would run with wrapped indices)
         else if (d) e8_pass(S, slot + uni64(Mo->pm_off), outp + seg_base, b_out_cap > seg_base ? (uint32_t)(b_out_cap - seg_base < 0xFFFFFFFFull ? b_out_cap - seg_base : 0xFFFFFFFFull) : 0u, d, lane);
       }
       if (retry || lost) break;
       const uint64_t produced = wp;
-      if (!status && produced > b_out_cap) status = ZH_E_OUTPUT_FULL;
-      if (status && status != ZH_E_OUTPUT_FULL) failed = true;
-      if (lane == 0) {
-        ZhSegResult res;
-        res.status = status; res.pp_state = (uint32_t)pp_state | (uint32_t)pp_hsize << 8;
-        res.out_off = b_out_off + produced0; res.out_len = produced - produced0;
-        res.in_used = in_pos(r.in) - seg_off;
-        L.results[si] = res;
-      }
+      failed = seg_done(L.results, si, status, pp, b_out_off, b_out_cap, produced0, produced, in_pos(r.in) - seg_off, lane, failed) != 0;
     }
     if (flusher_on) {                                   // the flusher leaves the block
       ++cmd_seq;

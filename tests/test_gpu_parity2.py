@@ -302,20 +302,25 @@ def test_two_ranks_on_one_gpu_run_the_sharded_hip_decode(tmp_path, schedule):
     assert len(line["config"]["rank_kernel_ms"]) == 2 and max(line["config"]["rank_kernel_ms"]) > 0
 
 
+def _stored_block(d):
+    """An unmodelled (n = 0) store block, Decoder.cs:58-67: [len32 BE, bytes]*, 0, in two chunks."""
+    store_hdr = zpaql.assemble("comp 0 0 0 0 0 hcomp halt end").header
+    pay = b"\0" + d                                            # leading 0 = PASS
+    cut = len(pay) // 3
+    body = b"".join(len(c).to_bytes(4, "big") + c for c in (pay[:cut], pay[cut:])) + b"\0\0\0\0"
+    return (TAG + b"zPQ" + bytes([2, 1]) + store_hdr + b"\x01\0" + str(len(d)).encode() + b"\0\0" + body
+            + bytes([253]) + oracle.sha1(d) + bytes([255]))
+
+
 def _mixed_stream(n_blocks=23, seed=5):
     rng = np.random.default_rng(seed)
     parts, plain = [], []
-    store_hdr = zpaql.assemble("comp 0 0 0 0 0 hcomp halt end").header
     for i in range(n_blocks):
         if i % 5 == 3:
-            # unmodelled (n = 0) store block, Decoder.cs:58-67: [len32 BE, bytes]*, 0.  Chunks longer than one ragged read
-            # of the Reader test, so that a read ends inside a chunk (the scan has to ask for more input, not give up)
+            # Chunks longer than one ragged read of the Reader test, so that a read ends inside a chunk (the scan has to ask
+            # for more input, not give up)
             d = util.text(int(rng.integers(6000, 20000)), seed=100 + i)
-            pay = b"\0" + d                                    # leading 0 = PASS
-            cut = len(pay) // 3
-            body = b"".join(len(c).to_bytes(4, "big") + c for c in (pay[:cut], pay[cut:])) + b"\0\0\0\0"
-            parts.append(TAG + b"zPQ" + bytes([2, 1]) + store_hdr + b"\x01\0" + str(len(d)).encode() + b"\0\0" + body
-                         + bytes([253]) + oracle.sha1(d) + bytes([255]))
+            parts.append(_stored_block(d))
             plain.append(d)
             continue
         model = ("l1", "min", "mid")[i % 3]
@@ -544,6 +549,27 @@ def test_kernel_families_side_by_side_and_one_after_the_other_agree(ctx):
         assert ctx.decompress(s2, verify_sha1=True).tobytes() == want2
     finally:
         del os.environ["ZPAQHIP_SERIAL_FAMILIES"]
+
+
+def test_launches_and_blocks_in_flight_are_the_plan_s(ctx):
+    """The launch plan (zh_dec_plan.h, tests/test_dec_plan.py on the host) on a real launch: two blocks of 4 KiB of each of
+    l1, min, mid, max and stored are five kernel groups, one launch each, side by side or one after the other; a group has
+    min(2, slots) blocks in flight, and max_concurrent = 1 leaves every group one slot.  (_mixed_stream has no max block: the
+    stream is built here.)"""
+    plain = [util.text(4096, seed=700 + i) for i in range(10)]
+    s = b"".join(_stored_block(d) if i % 5 == 4 else util.block(("l1", "min", "mid", "max")[i % 5], d) for i, d in enumerate(plain))
+    want = b"".join(plain)
+    families = 5
+    assert ctx.decompress(s, verify_sha1=True).tobytes() == want
+    assert (ctx.stats().launches, ctx.stats().concurrent) == (families, 2)
+    os.environ["ZPAQHIP_SERIAL_FAMILIES"] = "1"
+    try:
+        assert ctx.decompress(s, verify_sha1=True).tobytes() == want
+        assert (ctx.stats().launches, ctx.stats().concurrent) == (families, 2)
+    finally:
+        del os.environ["ZPAQHIP_SERIAL_FAMILIES"]
+    assert ctx.decompress(s, verify_sha1=True, max_concurrent=1).tobytes() == want
+    assert (ctx.stats().launches, ctx.stats().concurrent) == (families, 1)
 
 
 def test_nibble_kernels_and_their_assembly_loops_match_the_oracle(ctx):

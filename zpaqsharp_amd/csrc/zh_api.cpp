@@ -21,6 +21,7 @@
 
 #include "zh_compress.h"
 #include "zh_ctx_view.h"
+#include "zh_dec_plan.h"
 #include "zh_host.h"
 #include "zh_zpaql_native.h"
 
@@ -35,7 +36,6 @@ extern "C" hipError_t zh_launch_chain2(const ZhLaunch *L, uint32_t grid, hipStre
 extern "C" int zh_chain2_has(uint32_t spec);
 extern "C" hipError_t zh_launch_nibble(const ZhLaunch *L, uint32_t grid, hipStream_t stream, uint32_t spec, int prof);
 extern "C" int zh_nibble_has(uint32_t spec);
-static size_t pool_trim_device(int device, size_t keep);   // idle contexts of zpaqhip_decompress_multi's pool (below)
 extern "C" hipError_t zh_launch_store(const ZhLaunch *L, uint32_t grid, hipStream_t stream);
 
 
@@ -97,36 +97,7 @@ zpaqhip_opts resolve_opts(const zpaqhip_opts *o) {
   return r;
 }
 
-// ---- which kernel decodes a block (the table is include/zpaqhip.h's): the one place that reads opts.kernel, but for zh_cm's
-// one / two blocks per workgroup, decided in decode_launch where the group's size is known.  `group` is the block's family
-// after opts.kernel's overrides (its work-queue head, arena region, stream and launch order); `spec` the kernel's specialisation
-enum class ZhKernel { Generic, Store, Cm, Chain, Chain2, Nibble };
-struct ZhRoute { uint32_t group; ZhKernel kernel; uint32_t spec; uint32_t flags = 0; };   // flags: ZH_LAUNCH_* of the launch
-
-ZhRoute route_block(const ZhModel &m, const zpaqhip_opts &o, bool pp_only) {
-  const uint32_t K = o.kernel, hk = (m.kind >> 8) & 255u;
-  uint32_t f = m.kind & 255u;
-  // the method models of min's / mid's shape (zh_framing.cpp) are known to zh_nibble.hip only: the older kernels of these
-  // families carry the built-in HCOMP programs
-  const bool method = hk == ZH_NATIVE_HCOMP_M4 || hk == ZH_NATIVE_HCOMP_M3 || hk == ZH_NATIVE_HCOMP_M2 || hk == ZH_NATIVE_HCOMP_M2E;
-  if (K == 1 || (f == ZH_FAM_STORE && pp_only)) f = ZH_FAM_GENERIC;
-  if (K == 3 && f == ZH_FAM_CM1) f = ZH_FAM_CHAIN;
-  if (K == 4 && f > ZH_FAM_CHAIN) f = ZH_FAM_CHAIN;                  // stored blocks included
-  if ((K == 5 || K == 9) && ((f > ZH_FAM_CHAIN && f < ZH_FAM_STORE && method) || f == ZH_FAM_CHAIN_MID8 || f == ZH_FAM_CHAIN_MIN1))
-    f = ZH_FAM_CHAIN;
-  const uint32_t nb_flags = K == 11 ? ZH_LAUNCH_MODEL_E8 : 0u;         // zh_nibble.hip: lzpre / bwtrle with E8E9 wave-wide
-  switch (f) {
-    case ZH_FAM_GENERIC: return {f, ZhKernel::Generic, 0};
-    case ZH_FAM_CM1: return {f, ZhKernel::Cm, 0};
-    case ZH_FAM_STORE: return {f, ZhKernel::Store, 0, K == 10 || K == 11 ? ZH_LAUNCH_STORE_E8 : 0u};   // the E8E9 forms of lazy2 / lzpre stay on it
-    case ZH_FAM_CHAIN_MID8: return {f, ZhKernel::Nibble, 5, nb_flags};  // mid's shape, eight mixer inputs
-    case ZH_FAM_CHAIN_MIN1: return {f, ZhKernel::Nibble, 6, nb_flags};  // one ICM on min's loop
-  }
-  const uint32_t spec = f - ZH_FAM_CHAIN;                              // 0: level walk at run time; 1 / 2 / 3: min / mid / max
-  if (spec && zh_nibble_has(spec) && K != 5 && K != 9) return {f, ZhKernel::Nibble, spec, nb_flags};   // 9: the bit-at-a-time form
-  if (spec && zh_chain2_has(spec) && K != 5) return {f, ZhKernel::Chain2, spec};
-  return {f, ZhKernel::Chain, spec};
-}
+const ZhKernelHas kKernelHas = {zh_nibble_has, zh_chain2_has};   // route_block: what the kernels are built with
 
 }  // namespace
 
@@ -254,6 +225,14 @@ int zpaqhip_read_device_tables(zpaqhip_ctx *c, uint16_t *squash, int16_t *stretc
 // neighbouring batches) while a batch's kernels run: decode_launch() enqueues everything on `stream` and returns,
 // decode_finish() waits for the stream and turns the device results into zpaqhip_seg_result records.  One launch may be
 // outstanding per context (the descriptor / result / arena buffers belong to the context).
+static size_t pool_trim_device(int device, size_t keep);   // idle contexts of zpaqhip_decompress_multi's pool (below)
+
+struct GroupLaunch {                      // what one kernel group of a launch was started with
+  ZhLaunch L{};                           // (L.n_blocks: the group's blocks)
+  size_t base = 0;                        // its first descriptor in bd_sorted
+  uint32_t slots = 0;
+};
+
 struct zh_pending {
   std::vector<uint32_t> sel;
   const zpaqhip_block *blocks = nullptr;
@@ -261,49 +240,35 @@ struct zh_pending {
   size_t n_segs = 0;
   hipStream_t stream = nullptr;
   uint64_t total_in = 0, total_model = 0;
-  uint32_t launches = 0, slots = 0, kind_used = 0;
-  bool prof = false, active = false;
+  bool active = false;
   // sources of the launch's asynchronous H2D copies: they must outlive decode_launch (the API does not promise that a
   // pageable hipMemcpyAsync has read its source when it returns)
   std::vector<ZhModel> models;
   std::vector<uint8_t> code;
   std::vector<ZhSegDesc> sd;
-  std::vector<ZhBlockDesc> bd_sorted;
+  DecPlan plan;                                         // (its bd_sorted)
   // zh_store.hip hands blocks it does not take (ZH_E_RETRY) back: they run on the generic kernel in decode_finish
   bool has_store = false;
-  ZhLaunch store_launch{};
-  size_t store_base = 0, store_count = 0;
-  uint32_t store_slots = 0;
+  GroupLaunch store;
   bool e8_wave = false;                                 // a launch had ZH_LAUNCH_MODEL_E8: word 1 of its work-queue head counts segments
 };
 
-static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, size_t in_len,
-                                 const zpaqhip_block *blocks,
-                                 size_t n_blocks, const zpaqhip_segment *segs, size_t n_segs, const uint32_t *ids,
-                                 size_t n_ids, void *d_out, const uint64_t *out_off, const uint64_t *out_cap,
-                                 const zpaqhip_opts &opts, hipStream_t stream, zh_pending &P,
-                                 zpaqhip_err *err) {
-  P = zh_pending();
-  P.blocks = blocks; P.segs = segs; P.n_segs = n_segs; P.stream = stream;
-  HIPCHK(hipSetDevice(c->device));
-  memset(&c->stats, 0, sizeof c->stats);
-
-  std::vector<uint32_t> &sel = P.sel;
-  if (ids) sel.assign(ids, ids + n_ids);
-  else { sel.resize(n_blocks); std::iota(sel.begin(), sel.end(), 0u); }
-  if (sel.empty()) return ZPAQHIP_OK;
-  for (uint32_t b : sel)
-    if (b >= n_blocks) { set_err(err, ZPAQHIP_E_ARG, (int)b, -1, "block id out of range"); return ZPAQHIP_E_ARG; }
-
-  // ---- models: one per distinct header
+// Step 1 of decode_launch: the headers of the selected blocks read, one model per distinct header built (P.models, P.code),
+// and per block its descriptor and weight (coded bytes), per segment its descriptor (P.sd); the totals of the statistics.
+static int collect_models(const void *d_in, const uint8_t *h_in, size_t in_len, const uint64_t *out_off, const uint64_t *out_cap,
+                          zh_pending &P, std::vector<ZhBlockDesc> &bd, std::vector<uint64_t> &weight, zpaqhip_err *err) {
+  const std::vector<uint32_t> &sel = P.sel;
+  const zpaqhip_block *blocks = P.blocks;
+  const zpaqhip_segment *segs = P.segs;
+  const size_t n_segs = P.n_segs;
   std::map<std::string, uint32_t> model_of;
   std::vector<ZhModel> &models = P.models;
   std::vector<uint8_t> &code = P.code;
-  std::vector<ZhBlockDesc> bd(sel.size());
+  bd.assign(sel.size(), ZhBlockDesc{});
   std::vector<ZhSegDesc> &sd = P.sd;
   sd.assign(n_segs, ZhSegDesc{});
   std::vector<uint8_t> hdr;
-  uint64_t total_in = 0, total_model = 0;
+  uint64_t &total_in = P.total_in, &total_model = P.total_model;
   for (size_t k = 0; k < sel.size(); ++k) {
     const zpaqhip_block &b = blocks[sel[k]];
     if (b.hdr_off + b.hdr_len > in_len || (uint64_t)b.first_seg + b.n_seg > n_segs) {
@@ -340,38 +305,82 @@ static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, 
       total_in += sg.data_len;
     }
   }
-  std::vector<uint64_t> weight(sel.size(), 0);
+  weight.assign(sel.size(), 0);
   for (size_t k = 0; k < sel.size(); ++k)
     for (uint32_t i = 0; i < bd[k].n_seg; ++i) weight[k] += sd[bd[k].first_seg + i].in_len;
+  return ZPAQHIP_OK;
+}
 
-  // ---- blocks grouped by route (route_block): one group, one kernel
+// Step 4 of decode_launch: the kernel of one group (plan_decode chose it and its shape), launched on `stream`.
+static int launch_group(zh_pending &P, const DecPlan &plan, const DecGroup &g, const ZhLaunch &L, hipStream_t stream, zpaqhip_err *err) {
+  const ZhRoute &r = g.route;
+  switch (r.kernel) {
+    case ZhKernel::Generic: HIPCHK(zh_launch_generic(&L, g.grid(), stream)); break;
+    case ZhKernel::Store:
+      HIPCHK(zh_launch_store(&L, g.grid(), stream));
+      P.has_store = true; P.store = {L, g.base, g.slots};
+      break;
+    case ZhKernel::Cm:
+      if (plan.prof) HIPCHK(zh_launch_cm_prof(&L, g.grid(), stream));
+      else if (g.cm_x2) HIPCHK(zh_launch_cm_x2(&L, g.grid(), stream));
+      else HIPCHK(zh_launch_cm(&L, g.grid(), stream));
+      break;
+    case ZhKernel::Chain:
+      if (g.mw.waves > 1) HIPCHK(zh_launch_chain_mw(&L, &g.mw, g.grid(), stream, g.pcall));
+      else HIPCHK(zh_launch_chain(&L, g.grid(), stream, r.spec, plan.prof, g.pcall));
+      break;
+    case ZhKernel::Chain2: HIPCHK(zh_launch_chain2(&L, g.grid(), stream, r.spec, plan.prof)); break;   // per-model bit loop
+    case ZhKernel::Nibble: HIPCHK(zh_launch_nibble(&L, g.grid(), stream, r.spec, plan.prof)); break;   // a nibble at a time
+  }
+  P.e8_wave |= (r.flags & ZH_LAUNCH_MODEL_E8) != 0;
+  return ZPAQHIP_OK;
+}
+
+// Four steps: collect_models; plan_decode (zh_dec_plan.h: every decision about slots, waves, workgroups and the arena); the
+// buffers reserved and the tables and descriptors uploaded; launch_group for every group of the plan.
+static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, size_t in_len,
+                                 const zpaqhip_block *blocks,
+                                 size_t n_blocks, const zpaqhip_segment *segs, size_t n_segs, const uint32_t *ids,
+                                 size_t n_ids, void *d_out, const uint64_t *out_off, const uint64_t *out_cap,
+                                 const zpaqhip_opts &opts, hipStream_t stream, zh_pending &P,
+                                 zpaqhip_err *err) {
+  P = zh_pending();
+  P.blocks = blocks; P.segs = segs; P.n_segs = n_segs; P.stream = stream;
+  HIPCHK(hipSetDevice(c->device));
+  memset(&c->stats, 0, sizeof c->stats);
+
+  std::vector<uint32_t> &sel = P.sel;
+  if (ids) sel.assign(ids, ids + n_ids);
+  else { sel.resize(n_blocks); std::iota(sel.begin(), sel.end(), 0u); }
+  if (sel.empty()) return ZPAQHIP_OK;
+  for (uint32_t b : sel)
+    if (b >= n_blocks) { set_err(err, ZPAQHIP_E_ARG, (int)b, -1, "block id out of range"); return ZPAQHIP_E_ARG; }
+
+  // ---- 1. models: one per distinct header
+  std::vector<ZhBlockDesc> bd;
+  std::vector<uint64_t> weight;
+  if (int rc = collect_models(d_in, h_in, in_len, out_off, out_cap, P, bd, weight, err)) return rc;
+  const std::vector<ZhModel> &models = P.models;
+  const std::vector<uint8_t> &code = P.code;
+  const std::vector<ZhSegDesc> &sd = P.sd;
+
+  // ---- 2. the plan
   const bool pp_only = opts.reserved[0] == kPpOnlyMagic;        // the library's own use of the reserved word (zpaqhip_block_pcomp)
   const bool prof = getenv("ZPAQHIP_PROF") != nullptr;   // diagnostic build with in-kernel stamps
-  std::vector<std::vector<uint32_t>> groups(ZH_NFAM_HOST);
-  ZhRoute route_of[ZH_NFAM_HOST] = {};
-  for (size_t k = 0; k < sel.size(); ++k) {
-    const ZhRoute r = route_block(models[bd[k].model], opts, pp_only);
-    route_of[r.group] = r;
-    groups[r.group].push_back((uint32_t)k);
-  }
-
+  std::vector<DecGroup> groups = group_blocks(models, bd, opts, pp_only, kKernelHas);
   uint64_t mem_budget = 0;
   HIPCHK(device_budget(c->mem_share, c->arena.cap, &mem_budget));     // our own cached arena is reusable
-  {
-    // Idle contexts zpaqhip_decompress_multi has pooled on this device keep their arenas (tens of GB for the larger models).
-    // If this launch could not give every block (up to 256) its slot, they are released first and the budget taken again
-    // (multi([0,0,0,0]) followed by a max-model decode on a context of one's own saw a quarter of the memory).
-    uint64_t wish = 0;
-    for (uint32_t g = 0; g < ZH_NFAM_HOST; ++g) {
-      uint64_t stride = 0;
-      for (uint32_t k : groups[g]) stride = std::max<uint64_t>(stride, models[bd[k].model].arena_bytes);
-      wish += stride * std::min<uint64_t>(groups[g].size(), opts.max_concurrent ? opts.max_concurrent : 256u);
-    }
-    if (wish > mem_budget && pool_trim_device(c->device, 0)) {
-      HIPCHK(device_budget(c->mem_share, c->arena.cap, &mem_budget));
-    }
-  }
+  // Idle contexts zpaqhip_decompress_multi has pooled on this device keep their arenas (tens of GB for the larger models).
+  // If this launch could not give every block (up to kDecBlocks) its slot, they are released first and the budget taken again
+  // (multi([0,0,0,0]) followed by a max-model decode on a context of one's own saw a quarter of the memory).
+  if (arena_wish(groups, opts) > mem_budget && pool_trim_device(c->device, 0))
+    HIPCHK(device_budget(c->mem_share, c->arena.cap, &mem_budget));
+  DecPlan &plan = P.plan;
+  if (int rc = plan_decode(std::move(groups), models, bd, weight, opts, prof, (uint32_t)c->cus, mem_budget,
+                           getenv("ZPAQHIP_SERIAL_FAMILIES") != nullptr, plan, err))
+    return rc;
 
+  // ---- 3. buffers, tables and descriptors
   HIPCHK(c->models.reserve(models.size() * sizeof(ZhModel)));
   HIPCHK(c->code.reserve(code.size() + 16));
   HIPCHK(c->bdesc.reserve(sel.size() * sizeof(ZhBlockDesc)));
@@ -385,88 +394,24 @@ static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, 
   HIPCHK(hipMemsetAsync(c->results.p, 0xff, n_segs * sizeof(ZhSegResult), stream));
   HIPCHK(hipMemsetAsync(c->queue.p, 0, kQueueBytes + kDebugBytes, stream));
 
-  // arena: one region per kernel family when all of them fit at once (the families then run side by side: an archive
-  // that mixes models fills the GPU with whatever blocks it has), else one region sized for the most demanding family,
-  // used by one family after the other
-  uint32_t slots_of[ZH_NFAM_HOST] = {};
-  bool cm_x2[ZH_NFAM_HOST] = {};
-  ZhChainWaves mw[ZH_NFAM_HOST] = {};     // waves > 1: the group runs on zh_decode_chain_mw, mw_grid workgroups of that many waves
-  uint32_t mw_grid[ZH_NFAM_HOST] = {};
-  uint64_t stride_of[ZH_NFAM_HOST], arena_need = 0, arena_sum = 0, arena_off[ZH_NFAM_HOST] = {};
-  uint32_t n_fam = 0;
-  for (auto &x : stride_of) x = 256;
-  for (uint32_t g = 0; g < ZH_NFAM_HOST; ++g) {
-    if (groups[g].empty()) continue;
-    for (uint32_t k : groups[g]) stride_of[g] = std::max<uint64_t>(stride_of[g], models[bd[k].model].arena_bytes);
-    uint64_t max_slots = mem_budget / stride_of[g];
-    if (max_slots == 0) { set_err(err, ZPAQHIP_E_DEVICE_MEM, -1, -1, "Out of memory"); return ZPAQHIP_E_DEVICE_MEM; }
-    uint32_t want = opts.max_concurrent ? opts.max_concurrent : 256u;   // one block per CU by default
-    // single-CM blocks beyond one per CU: two per workgroup (zh_decode_cm_x2: 32 LDS windows each instead of 64), so a stream
-    // of many blocks uses all four SIMDs of a CU; opts.kernel == 6 forces that form, 2 the one-block form (A/B runs, tests)
-    cm_x2[g] = route_of[g].kernel == ZhKernel::Cm && !prof && opts.kernel != 2 &&
-               (opts.kernel == 6 || (!opts.max_concurrent && groups[g].size() > 256));
-    if (cm_x2[g]) want = opts.max_concurrent ? opts.max_concurrent : 512u;
-    slots_of[g] = (uint32_t)std::min<uint64_t>({(uint64_t)want, max_slots, (uint64_t)groups[g].size()});
-    if (cm_x2[g]) { slots_of[g] = (slots_of[g] + 1u) & ~1u; if (slots_of[g] > max_slots) { slots_of[g] = (uint32_t)(max_slots & ~1ull); cm_x2[g] = slots_of[g] >= 2; if (!cm_x2[g]) slots_of[g] = 1; } }
-    // opts.dec_waves >= 2, blocks on zh_chain's run-time level walk: several decoder waves per workgroup, an arena slot
-    // each.  The blocks spread over the compute units first; a second, third and fourth wave come with more blocks than
-    // workgroups, as many as the LDS plan of the group's models (the smallest: one launch, its pool sized for the largest
-    // chain), opts.dec_waves and the blocks per workgroup allow; where memory (or opts.max_concurrent) is short of a slot
-    // per wave the waves go before the workgroups.  One wave left: the launch is the one-wave kernel's, as without the option.
-    if (route_of[g].kernel == ZhKernel::Chain && route_of[g].spec == 0 && !prof && opts.dec_waves >= 2) {
-      uint32_t plan = ZH_DEC_CHAIN_MAX_WAVES, units = 0;
-      for (uint32_t k : groups[g]) {
-        const DecChainPlan p = plan_dec_chain(models[bd[k].model]);
-        plan = std::min(plan, p.waves);
-        units = std::max(units, p.units);
-      }
-      const uint32_t grid = std::min<uint32_t>(slots_of[g], (uint32_t)c->cus);
-      const uint64_t room = std::min<uint64_t>(max_slots, opts.max_concurrent ? opts.max_concurrent : UINT32_MAX);
-      uint32_t w = (uint32_t)std::min<uint64_t>({(uint64_t)plan, opts.dec_waves, (groups[g].size() + grid - 1) / grid});
-      while (w > 1 && (uint64_t)grid * w > room) --w;
-      if (w > 1) {
-        mw[g].waves = w;
-        mw[g].lds_pool = units * 1024u;
-        mw[g].lds_stride = zh_dec_chain_stride(units);
-        mw_grid[g] = grid;
-        slots_of[g] = grid * w;                          // one arena slot per resident wave
-      }
-    }
-    arena_need = std::max<uint64_t>(arena_need, slots_of[g] * stride_of[g]);
-    arena_off[g] = arena_sum;
-    arena_sum += (slots_of[g] * stride_of[g] + 255) & ~255ull;
-    ++n_fam;
-  }
-  const bool side_by_side = n_fam > 1 && arena_sum <= mem_budget && !getenv("ZPAQHIP_SERIAL_FAMILIES");
-  if (!side_by_side) for (auto &x : arena_off) x = 0;
-  HIPCHK(c->arena.reserve((size_t)(side_by_side ? arena_sum : arena_need)));
-  if (side_by_side && !c->fork_ev) HIPCHK(hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
+  HIPCHK(c->arena.reserve((size_t)plan.arena_bytes));
+  if (plan.side_by_side && !c->fork_ev) HIPCHK(hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
+  HIPCHK(hipMemcpyAsync(c->bdesc.p, plan.bd_sorted.data(), plan.bd_sorted.size() * sizeof(ZhBlockDesc), hipMemcpyHostToDevice, stream));
 
-  std::vector<ZhBlockDesc> &bd_sorted = P.bd_sorted;
-  bd_sorted.reserve(sel.size());
-  size_t base_of[ZH_NFAM_HOST] = {};
-  for (uint32_t g = 0; g < ZH_NFAM_HOST; ++g) {
-    // Longest block first: the work queue then balances the tail (LPT order).
-    std::stable_sort(groups[g].begin(), groups[g].end(), [&](uint32_t a, uint32_t b) { return weight[a] > weight[b]; });
-    base_of[g] = bd_sorted.size();
-    for (uint32_t k : groups[g]) bd_sorted.push_back(bd[k]);
-  }
-  HIPCHK(hipMemcpyAsync(c->bdesc.p, bd_sorted.data(), bd_sorted.size() * sizeof(ZhBlockDesc), hipMemcpyHostToDevice, stream));
-
-  uint32_t launches = 0, slots = 0, kind_used = 0;
+  // ---- 4. one launch per group: on the launch stream one after the other, or side by side on the families' own streams,
+  // forked from the launch stream and joined to it
   HIPCHK(hipEventRecord(c->ev0, stream));
-  if (side_by_side) HIPCHK(hipEventRecord(c->fork_ev, stream));      // the tables and descriptors above are on `stream`
-  hipStream_t const launch_stream = stream;
-  for (uint32_t g = 0; g < ZH_NFAM_HOST; ++g) {
-    if (groups[g].empty()) continue;
-    hipStream_t stream = launch_stream;                  // (shadows: the family's own stream when families run side by side)
-    if (side_by_side) {
-      if (!c->fam_stream[g]) {
-        HIPCHK(hipStreamCreateWithFlags(&c->fam_stream[g], hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&c->fam_ev[g], hipEventDisableTiming));
+  if (plan.side_by_side) HIPCHK(hipEventRecord(c->fork_ev, stream));      // the tables and descriptors above are on `stream`
+  for (const DecGroup &g : plan.groups) {
+    const uint32_t f = g.route.group;
+    hipStream_t gs = stream;
+    if (plan.side_by_side) {
+      if (!c->fam_stream[f]) {
+        HIPCHK(hipStreamCreateWithFlags(&c->fam_stream[f], hipStreamNonBlocking));
+        HIPCHK(hipEventCreateWithFlags(&c->fam_ev[f], hipEventDisableTiming));
       }
-      stream = c->fam_stream[g];
-      HIPCHK(hipStreamWaitEvent(stream, c->fork_ev, 0));
+      gs = c->fam_stream[f];
+      HIPCHK(hipStreamWaitEvent(gs, c->fork_ev, 0));
     }
     ZhLaunch L;
     memset(&L, 0, sizeof L);
@@ -474,55 +419,25 @@ static int decode_launch(zpaqhip_ctx *c, const void *d_in, const uint8_t *h_in, 
     L.in_total = in_len;
     L.models = (const ZhModel *)c->models.p;
     L.code = (const uint8_t *)c->code.p;
-    L.blocks = (const ZhBlockDesc *)c->bdesc.p + base_of[g];
+    L.blocks = (const ZhBlockDesc *)c->bdesc.p + g.base;
     L.segs = (const ZhSegDesc *)c->sdesc.p;
     L.results = (ZhSegResult *)c->results.p;
     L.out = (uint8_t *)d_out;
-    L.arena = (uint8_t *)c->arena.p + arena_off[g];
-    L.arena_stride = stride_of[g];
+    L.arena = (uint8_t *)c->arena.p + g.arena_off;
+    L.arena_stride = g.stride;
     L.tables = (const ZhTables *)c->tables.p;
-    L.queue = (uint32_t *)c->queue.p + 8 * g;           // one work-queue head per launch
-    L.n_blocks = (uint32_t)groups[g].size();
+    L.queue = (uint32_t *)c->queue.p + 8 * f;           // one work-queue head per launch
+    L.n_blocks = (uint32_t)g.blocks.size();
     L.budget = opts.zpaql_budget;
-    L.flags = pp_only ? ZH_LAUNCH_PP_ONLY : 0u;
+    L.flags = (pp_only ? ZH_LAUNCH_PP_ONLY : 0u) | g.route.flags;
     if (prof) L.debug = (uint64_t *)((uint8_t *)c->queue.p + kQueueBytes);
-    const ZhRoute &r = route_of[g];
-    L.flags |= r.flags;
-    P.e8_wave |= (r.flags & ZH_LAUNCH_MODEL_E8) != 0;
-    switch (r.kernel) {
-      case ZhKernel::Generic: HIPCHK(zh_launch_generic(&L, slots_of[g], stream)); break;
-      case ZhKernel::Store:
-        HIPCHK(zh_launch_store(&L, slots_of[g], stream));
-        P.has_store = true; P.store_launch = L; P.store_base = base_of[g]; P.store_count = groups[g].size(); P.store_slots = slots_of[g];
-        break;
-      case ZhKernel::Cm:
-        if (prof) HIPCHK(zh_launch_cm_prof(&L, slots_of[g], stream));
-        else if (cm_x2[g]) HIPCHK(zh_launch_cm_x2(&L, slots_of[g] / 2, stream));
-        else HIPCHK(zh_launch_cm(&L, slots_of[g], stream));
-        break;
-      case ZhKernel::Chain: {
-        int pcall = 0;                                   // any model with PCOMP memory: the variant with translated post-processors
-        for (uint32_t k : groups[g]) pcall |= (models[bd[k].model].ph | models[bd[k].model].pm) != 0;
-        if (mw[g].waves > 1) HIPCHK(zh_launch_chain_mw(&L, &mw[g], mw_grid[g], stream, pcall));
-        else HIPCHK(zh_launch_chain(&L, slots_of[g], stream, r.spec, prof, pcall));
-        break;
-      }
-      case ZhKernel::Chain2: HIPCHK(zh_launch_chain2(&L, slots_of[g], stream, r.spec, prof)); break;   // per-model bit loop
-      case ZhKernel::Nibble: HIPCHK(zh_launch_nibble(&L, slots_of[g], stream, r.spec, prof)); break;   // a nibble at a time
+    if (int rc = launch_group(P, plan, g, L, gs, err)) return rc;
+    if (plan.side_by_side) {                             // join: the launch stream goes on when every family is done
+      HIPCHK(hipEventRecord(c->fam_ev[f], gs));
+      HIPCHK(hipStreamWaitEvent(stream, c->fam_ev[f], 0));
     }
-    if (side_by_side) {                                  // join: the launch stream goes on when every family is done
-      HIPCHK(hipEventRecord(c->fam_ev[g], stream));
-      HIPCHK(hipStreamWaitEvent(launch_stream, c->fam_ev[g], 0));
-    }
-    ++launches;
-    // (a several-waves launch: the blocks in flight are its waves with a block)
-    slots = std::max(slots, mw[g].waves > 1 ? (uint32_t)std::min<uint64_t>(slots_of[g], groups[g].size()) : slots_of[g]);
-    kind_used = std::max(kind_used, r.kernel == ZhKernel::Generic || r.kernel == ZhKernel::Store ? 1u : r.kernel == ZhKernel::Cm ? 2u : 3u);
   }
   HIPCHK(hipEventRecord(c->ev1, stream));
-  P.total_in = total_in; P.total_model = total_model;
-  P.launches = launches; P.slots = slots; P.kind_used = kind_used;
-  P.prof = prof;
   P.active = true;
   return ZPAQHIP_OK;
 }
@@ -536,8 +451,8 @@ static int decode_finish(zpaqhip_ctx *c, zh_pending &P, zpaqhip_seg_result *resu
   const size_t n_segs = P.n_segs;
   hipStream_t stream = P.stream;
   const uint64_t total_in = P.total_in, total_model = P.total_model;
-  const uint32_t launches = P.launches, slots = P.slots, kind_used = P.kind_used;
-  if (P.prof) {
+  const uint32_t launches = P.plan.launches, slots = P.plan.concurrent, kind_used = P.plan.kernel_kind;
+  if (P.plan.prof) {
     uint64_t dbg[16];
     HIPCHK(hipStreamSynchronize(stream));
     HIPCHK(hipMemcpy(dbg, (uint8_t *)c->queue.p + kQueueBytes, kDebugBytes, hipMemcpyDeviceToHost));
@@ -556,17 +471,17 @@ static int decode_finish(zpaqhip_ctx *c, zh_pending &P, zpaqhip_seg_result *resu
     // blocks the store kernel handed back (programs other than the reference's LZ77 ones, damaged chunks): the generic
     // kernel is the complete implementation.  Same arena slots, same output places.
     std::vector<ZhBlockDesc> redo;
-    for (size_t k = 0; k < P.store_count; ++k) {
-      const ZhBlockDesc &b = P.bd_sorted[P.store_base + k];
+    for (size_t k = 0; k < P.store.L.n_blocks; ++k) {
+      const ZhBlockDesc &b = P.plan.bd_sorted[P.store.base + k];
       if (b.n_seg && res[b.first_seg].status == ZH_E_RETRY) redo.push_back(b);
     }
     if (!redo.empty()) {
-      ZhLaunch L = P.store_launch;
+      ZhLaunch L = P.store.L;
       HIPCHK(hipMemcpyAsync((void *)L.blocks, redo.data(), redo.size() * sizeof(ZhBlockDesc), hipMemcpyHostToDevice, stream));
       HIPCHK(hipMemsetAsync(L.queue, 0, 32, stream));
       L.n_blocks = (uint32_t)redo.size();
       HIPCHK(hipEventRecord(c->ev0, stream));
-      HIPCHK(zh_launch_generic(&L, std::min<uint32_t>(P.store_slots, L.n_blocks), stream));
+      HIPCHK(zh_launch_generic(&L, std::min<uint32_t>(P.store.slots, L.n_blocks), stream));
       HIPCHK(hipEventRecord(c->ev1, stream));
       HIPCHK(hipMemcpyAsync(res.data(), c->results.p, n_segs * sizeof(ZhSegResult), hipMemcpyDeviceToHost, stream));
       HIPCHK(hipStreamSynchronize(stream));
@@ -685,7 +600,6 @@ struct Batch {
   bool last = false;
 };
 
-struct Batch;
 int sha1_mismatches(zpaqhip_ctx *c, const Batch &bt, std::vector<int> &bad, zpaqhip_err *err);
 
 struct Sinkk {
@@ -1148,7 +1062,6 @@ int run_pipeline_impl(zpaqhip_ctx *c, Source &src, Sinkk &sink, const zpaqhip_op
     }
     if (segsink) {
       uint64_t base = sink.total;                       // stream-order offset of this batch's first byte ...
-      if (have_prev) base += 0;
       uint64_t run = 0;
       for (size_t b = 0; b < B.so.blocks.size(); ++b) {
         const zpaqhip_block &Bk = B.so.blocks[b];
@@ -1230,7 +1143,7 @@ int zpaqhip_block_costs(const uint8_t *in, size_t in_len, const zpaqhip_block *b
       zpaqhip_err e2{};
       uint64_t w = 6000;                                  // a header the model builder refuses costs nothing real; keep it finite
       if (build_model(in + B.hdr_off, B.hdr_len, m, code, &e2) == ZPAQHIP_OK) {
-        const ZhRoute r = route_block(m, resolve_opts(nullptr), false);
+        const ZhRoute r = route_block(m, resolve_opts(nullptr), false, kKernelHas);
         const bool pcomp = (m.ph | m.pm) != 0;
         // measured cycles of the owning workgroup per plaintext byte (profiles/r03: 256 x 4 MiB, one block per CU), rounded;
         // estimates for the fallback kernels

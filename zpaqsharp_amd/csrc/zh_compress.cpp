@@ -76,7 +76,7 @@ int zh::finish_call(const CtxView &v, zpaqhip_stats st, uint64_t pos, size_t n_b
 
 namespace {
 
-// ---- which kernel encodes a block (the encode-side twin of zh_api.cpp's route_block): the window-parallel CM encoder for
+// ---- which kernel encodes a block (the encode-side twin of zh_dec_plan.h's route_block): the window-parallel CM encoder for
 // ZH_FAM_CM1 models with opts.kernel 0 or 2, the lane-per-component encoder for the chain families with opts.kernel 2, the
 // generic encoder for everything else (and for a block too long for zh_enc_cm's 28-bit positions)
 enum class EncKernel { Generic, Cm, Chain };

@@ -355,6 +355,19 @@ def test_pipeline_batches_and_unknown_sizes_cost_one_decode(ctx):
     # a hostile size hint (12-digit "size") neither allocates terabytes nor fails
     s3 = util.block("l1", b"abc" * 1000, comment=b"999999999999")
     assert ctx.decompress(s3, out_cap=3000, verify_sha1=True).tobytes() == b"abc" * 1000
+    # a caller's buffer smaller than the plaintext, over three batches: what fits arrives, nothing behind out_cap is touched,
+    # *out_len reports the full size
+    import ctypes as C
+    parts = [util.text(500 + 190 * i, seed=70 + i) for i in range(8)]
+    s4 = np.frombuffer(b"".join(util.block(("l1", "min", "mid")[i % 3], d, **({"comment": b"no size"} if i == 4 else {}))
+                                for i, d in enumerate(parts)), np.uint8)
+    want4 = b"".join(parts)
+    for cap in (len(want4) - 1, len(want4) // 2, 0):
+        buf = np.full(len(want4) + 64, 0xA5, np.uint8)
+        o, err, n = z.make_opts(batch_blocks=3), z.api.Err(), C.c_size_t(0)
+        rc = ctx._L.zpaqhip_decompress(ctx._h, s4.ctypes.data, s4.size, buf.ctypes.data, cap, C.byref(n), C.byref(o), C.byref(err))
+        assert rc == -20 and n.value == len(want4), (cap, rc, n.value)       # ZPAQHIP_E_OUTPUT_FULL
+        assert buf[:cap].tobytes() == want4[:cap] and (buf[cap:] == 0xA5).all(), cap
 
 
 def test_reader_writer_streaming_in_batches(ctx):

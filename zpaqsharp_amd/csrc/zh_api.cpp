@@ -23,6 +23,7 @@
 #include "zh_ctx_view.h"
 #include "zh_dec_plan.h"
 #include "zh_host.h"
+#include "zh_stream_plan.h"
 #include "zh_zpaql_native.h"
 
 extern "C" hipError_t zh_launch_generic(const ZhLaunch *L, uint32_t grid, hipStream_t stream);
@@ -570,174 +571,14 @@ extern "C" int zpaqhip_decode_blocks_device(zpaqhip_ctx *c, const void *d_in, co
 // ---------------------------------------------------------------------------
 namespace {
 
-bool data_error(int rc) {                 // per-segment outcomes, as opposed to failures of the call itself
-  return rc < 0 && rc != ZPAQHIP_E_HIP && rc != ZPAQHIP_E_ARG && rc != ZPAQHIP_E_DEVICE_MEM && rc != ZPAQHIP_E_NO_DEVICE &&
-         rc != ZPAQHIP_E_HEADER && rc != ZPAQHIP_E_COMPONENT && rc != ZPAQHIP_E_HM_TOO_BIG && rc != ZPAQHIP_E_CALLBACK;
-}
-
-struct Source {
-  const uint8_t *mem = nullptr;           // memory form
-  size_t mem_len = 0, mem_pos = 0;
-  zpaqhip_read_fn rd = nullptr;           // callback form (Reader.read, Reader.cs:14-25)
-  void *user = nullptr;
-  std::vector<uint8_t> buf;               // bytes read and not yet handed to a batch
-  bool eof = false;
-  uint64_t consumed = 0;                  // stream offset of the next unconsumed byte
-};
-
-struct Batch {
-  std::vector<uint8_t> own;               // callback form: the batch's bytes (moved out of Source::buf)
-  const uint8_t *h = nullptr;             // host bytes [0, len): whole blocks; tables in `so` are relative to h
-  size_t len = 0;
-  uint64_t stream_off = 0;
-  ScanOut so;
-  size_t blk0 = 0, seg0 = 0;              // global index of the first block / segment
-  std::vector<uint64_t> off, cap, real;   // staging offset / capacity / plaintext length per block
-  std::vector<zpaqhip_seg_result> res;    // per segment; out_off relative to the staging buffer
-  int slot = 0;
-  int rc_after = 0;                       // framing error that follows the last block of this batch ...
-  zpaqhip_err err_after{};                // ... reported once everything before it has been delivered
-  bool last = false;
-};
-
-int sha1_mismatches(zpaqhip_ctx *c, const Batch &bt, std::vector<int> &bad, zpaqhip_err *err);
-
-struct Sinkk {
-  uint8_t *mem = nullptr; size_t cap = 0; // memory form
-  zpaqhip_write_fn wr = nullptr;          // callback form (Writer.write, Writer.cs:19-24)
-  void *user = nullptr;
-  uint64_t total = 0;                     // plaintext bytes so far (counted past `cap` too)
-  // multi-device form: block k of this source goes to mem + place[k] (sizes promised by the caller); sizes[k] = what
-  // it really produced
-  const uint64_t *place = nullptr;
-  std::vector<uint64_t> *sizes = nullptr;
-  // ... and at most place_cap[k] bytes of it; a block that is larger (a wrong or missing size in its comment) is kept
-  // whole in spill[k] and put in place by the caller once every size is known
-  const uint64_t *place_cap = nullptr;
-  std::vector<std::vector<uint8_t>> *spill = nullptr;
-};
-
-constexpr size_t kBatchMinBlocks = 512, kBatchMinBlocksOther = 256, kBatchMinBytes = 32u << 20, kBatchMaxBlocks = 4096;   // 512: single-CM blocks run two per CU (zh_decode_cm_x2); every other kernel holds 256 blocks per launch, and a second batch overlaps its copies with this one's kernels
-constexpr size_t kReadChunk = 4u << 20, kPinChunk = 32u << 20;
-
-// A header the framing scan accepts can still be refused when the model is built (component limits, table sizes:
-// Predictor.cs:94-167).  The reference raises that at the block's Predictor.init, after everything before the block has
-// been written; so the batch is cut in front of the first such block and the error is reported behind the cut.
-void cut_at_bad_model(Batch &bt) {
-  std::map<std::string, int> seen;
-  for (size_t b = 0; b < bt.so.blocks.size(); ++b) {
-    const zpaqhip_block &B = bt.so.blocks[b];
-    std::string key((const char *)bt.h + B.hdr_off, B.hdr_len);
-    auto it = seen.find(key);
-    zpaqhip_err e2{};
-    if (it == seen.end()) {
-      ZhModel m;
-      std::vector<uint8_t> code;
-      it = seen.emplace(key, build_model(bt.h + B.hdr_off, B.hdr_len, m, code, &e2)).first;
-    } else if (it->second) {
-      ZhModel m;
-      std::vector<uint8_t> code;
-      (void)build_model(bt.h + B.hdr_off, B.hdr_len, m, code, &e2);     // (again, for the message)
-    }
-    if (!it->second) continue;
-    e2.block = (int32_t)b; e2.segment = -1;
-    bt.rc_after = it->second; bt.err_after = e2; bt.last = true;
-    bt.so.blocks.resize(b);
-    bt.so.segs.resize(b ? bt.so.blocks.back().first_seg + bt.so.blocks.back().n_seg : 0);
-    bt.so.stopped = false;
-    bt.len = b ? (size_t)bt.so.blocks.back().end_off : 0;
-    return;
-  }
-}
-
-// Next batch of whole blocks, or batch.so.blocks.empty() at the end of the stream.  Returns a call-level error only.
-int next_batch(Source &src, Batch &bt, size_t blk0, size_t seg0, size_t batch_blocks, size_t dec_waves, zpaqhip_err *err) {
-  ScanLimit lim;
-  lim.min_blocks = kBatchMinBlocks; lim.min_blocks_other = kBatchMinBlocksOther; lim.min_bytes = kBatchMinBytes; lim.max_blocks = kBatchMaxBlocks;
-  // opts.dec_waves >= 2: a batch of 256 blocks would leave zh_chain's second to fourth wave of a compute unit without a block
-  if (dec_waves > 1) lim.min_blocks_other = kBatchMinBlocksOther * dec_waves;
-  if (batch_blocks) { lim.min_blocks = lim.max_blocks = batch_blocks; lim.min_blocks_other = 0; lim.min_bytes = 0; }   // zpaqhip_opts.batch_blocks
-  bt = Batch();
-  bt.blk0 = blk0; bt.seg0 = seg0;
-  zpaqhip_err e2{};
-  if (src.mem || !src.rd) {
-    const uint8_t *w = src.mem + src.mem_pos;
-    const size_t wl = src.mem_len - src.mem_pos;
-    int rc = scan_stream(w, wl, bt.so, &e2, lim);
-    bt.h = w; bt.stream_off = src.mem_pos;
-    bt.len = bt.so.blocks.empty() ? 0 : (size_t)bt.so.blocks.back().end_off;
-    if (rc) { bt.rc_after = rc; bt.err_after = e2; bt.last = true; src.mem_pos = src.mem_len; }
-    else if (bt.so.stopped) src.mem_pos += bt.so.resume_off;
-    else { bt.last = true; src.mem_pos = src.mem_len; }
-    cut_at_bad_model(bt);
-    if (bt.last) src.mem_pos = src.mem_len;
-    return ZPAQHIP_OK;
-  }
-  for (;;) {                                            // Reader form: read until a batch is complete or the input ends
-    int rc = scan_stream(src.buf.data(), src.buf.size(), bt.so, &e2, lim);
-    const bool complete = bt.so.stopped || src.eof;
-    if (rc && !(bt.so.hit_eof && !src.eof)) {           // damage that more input cannot repair
-      bt.rc_after = rc; bt.err_after = e2; bt.last = true;
-    } else if (!complete) {
-      const size_t old = src.buf.size();
-      src.buf.resize(old + kReadChunk);
-      int n = src.rd(src.user, src.buf.data() + old, (int)kReadChunk);
-      if (n < 0) { set_err(err, ZPAQHIP_E_CALLBACK, -1, -1); return ZPAQHIP_E_CALLBACK; }
-      src.buf.resize(old + (size_t)n);
-      if (n == 0) src.eof = true;
-      continue;
-    } else if (rc) {                                    // input ended inside a block
-      bt.rc_after = rc; bt.err_after = e2; bt.last = true;
-    }
-    if (!bt.so.stopped) bt.last = true;
-    bt.len = bt.so.blocks.empty() ? 0 : (size_t)bt.so.blocks.back().end_off;
-    bt.stream_off = src.consumed;
-    // hand the batch its bytes; keep the unconsumed tail for the next one
-    const size_t keep_from = bt.last ? src.buf.size() : bt.so.resume_off;
-    bt.own.assign(src.buf.begin(), src.buf.begin() + (ptrdiff_t)bt.len);
-    src.buf.erase(src.buf.begin(), src.buf.begin() + (ptrdiff_t)keep_from);
-    src.consumed += keep_from;
-    bt.h = bt.own.data();
-    cut_at_bad_model(bt);
-    return ZPAQHIP_OK;
-  }
-}
-
-void rebase_err(zpaqhip_err *err, const Batch &bt) {
-  if (!err) return;
-  if (err->block >= 0) err->block += (int)bt.blk0;
-  if (err->segment >= 0) err->segment += (int)bt.seg0;
-}
-
-// Staging layout of a batch: the size hint of a block when the stream carries one, else a provisional slot.
+// Staging buffer of a batch: plan_slots (zh_stream_plan.h) within a quarter of the free memory.
 int plan_staging(zpaqhip_ctx *c, Batch &bt, zpaqhip_err *err) {
-  const size_t nb = bt.so.blocks.size();
-  bt.off.assign(nb, 0); bt.cap.assign(nb, 0); bt.real.assign(nb, 0);
+  bt.real.assign(bt.so.blocks.size(), 0);
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
   free_b += c->out2[0].cap + c->out2[1].cap;
   const uint64_t budget = free_b / 4 / std::max(1u, c->mem_share);   // per staging buffer; the arena needs the rest
-  uint64_t sum = 0;
-  for (size_t b = 0; b < nb; ++b) {
-    const zpaqhip_block &B = bt.so.blocks[b];
-    uint64_t coded = 0;
-    for (uint32_t i = 0; i < B.n_seg; ++i) coded += bt.so.segs[B.first_seg + i].data_len;
-    uint64_t cap = B.usize_hint;
-    // The hint is untrusted text (a comment that merely starts with digits, or a hostile archive): it only places the
-    // block when it is plausible; anything else gets the provisional slot and, if that overflows, an exact second pass.
-    if (cap == UINT64_MAX || cap > (1ull << 40) || cap > budget)
-      cap = std::min<uint64_t>(std::max<uint64_t>(16 * coded, 64u << 10), 256ull << 20);
-    bt.cap[b] = cap;
-    sum += cap;
-  }
-  if (sum > budget) {                                   // does not fit: count-only for the largest slots until it does
-    std::vector<size_t> order(nb);
-    std::iota(order.begin(), order.end(), (size_t)0);
-    std::sort(order.begin(), order.end(), [&](size_t a, size_t b2) { return bt.cap[a] > bt.cap[b2]; });
-    for (size_t k = 0; k < nb && sum > budget; ++k) { sum -= bt.cap[order[k]]; bt.cap[order[k]] = 0; }
-  }
-  uint64_t pos = 0;
-  for (size_t b = 0; b < nb; ++b) { bt.off[b] = pos; pos += bt.cap[b]; }
+  const uint64_t pos = plan_slots(bt.so.blocks, bt.so.segs, budget, bt.cap, bt.off);
   if (c->out2[bt.slot].reserve((size_t)pos + 16) != hipSuccess) {   // not even that: everything count-only, exact second pass
     (void)hipGetLastError();
     std::fill(bt.cap.begin(), bt.cap.end(), 0ull);
@@ -791,45 +632,24 @@ int sha1_mismatches(zpaqhip_ctx *c, const Batch &bt, std::vector<int> &bad, zpaq
 }
 
 // After decode_finish: plaintext sizes, and a second decode of the blocks that did not fit their staging slot.
-int settle_batch(zpaqhip_ctx *c, Batch &bt, const zpaqhip_opts &opts, bool tolerate, zpaqhip_stats &acc, zpaqhip_err *err) {
-  const size_t nb = bt.so.blocks.size();
-  std::vector<uint32_t> redo;
-  for (size_t b = 0; b < nb; ++b) {
-    const zpaqhip_block &B = bt.so.blocks[b];
-    uint64_t real = 0;
-    bool full = false;
-    for (uint32_t i = 0; i < B.n_seg; ++i) {
-      real += bt.res[B.first_seg + i].out_len;
-      full |= bt.res[B.first_seg + i].status == ZPAQHIP_E_OUTPUT_FULL;
-    }
-    bt.real[b] = real;
-    if (full || real > bt.cap[b]) redo.push_back((uint32_t)b);
-  }
-  if (redo.empty()) return ZPAQHIP_OK;
+int settle_batch(zpaqhip_ctx *c, Batch &bt, const zpaqhip_opts &opts, zpaqhip_stats &acc, zpaqhip_err *err) {
+  const SecondPass sp = plan_second_pass(bt);
+  if (sp.redo.empty()) return ZPAQHIP_OK;
   // exact sizes are known now: these blocks go to a buffer of their own
-  std::vector<uint64_t> off2(redo.size()), cap2(redo.size());
-  uint64_t pos = 0;
-  for (size_t k = 0; k < redo.size(); ++k) { off2[k] = pos; cap2[k] = bt.real[redo[k]]; pos += cap2[k]; }
-  HIPCHK(c->out_fix[bt.slot].reserve((size_t)pos + 16));
+  HIPCHK(c->out_fix[bt.slot].reserve((size_t)sp.bytes + 16));
   zh_pending P;
-  int rc = decode_launch(c, c->in2[bt.slot].p, bt.h, bt.len, bt.so.blocks.data(), nb, bt.so.segs.data(), bt.so.segs.size(),
-                         redo.data(), redo.size(), c->out_fix[bt.slot].p, off2.data(), cap2.data(), opts, c->stream, P, err);
+  int rc = decode_launch(c, c->in2[bt.slot].p, bt.h, bt.len, bt.so.blocks.data(), bt.so.blocks.size(), bt.so.segs.data(), bt.so.segs.size(),
+                         sp.redo.data(), sp.redo.size(), c->out_fix[bt.slot].p, sp.off2.data(), sp.cap2.data(), opts, c->stream, P, err);
   if (!rc) rc = decode_finish(c, P, bt.res.data(), err);
-  acc.kernel_ms += c->stats.kernel_ms; acc.launches += c->stats.launches; acc.e8_wave_segs += c->stats.e8_wave_segs;
-  if (rc && !(tolerate && data_error(rc)) && !data_error(rc)) return rc;
-  for (size_t k = 0; k < redo.size(); ++k) {            // mark: lives in out_fix (offset | top bit)
-    bt.off[redo[k]] = off2[k] | (1ull << 63);
-    bt.cap[redo[k]] = cap2[k];
+  add_kernel_stats(acc, c->stats);
+  if (rc && !data_error(rc)) return rc;
+  for (size_t k = 0; k < sp.redo.size(); ++k) {         // mark: lives in out_fix
+    bt.off[sp.redo[k]] = sp.off2[k] | kInFix;
+    bt.cap[sp.redo[k]] = sp.cap2[k];
   }
   return ZPAQHIP_OK;
 }
 
-const uint8_t *block_dev_ptr(zpaqhip_ctx *c, const Batch &bt, size_t b) {
-  const uint64_t o = bt.off[b];
-  return (o >> 63) ? (const uint8_t *)c->out_fix[bt.slot].p + (o & ~(1ull << 63)) : (const uint8_t *)c->out2[bt.slot].p + o;
-}
-
-// Deliver the first `upto_blocks` blocks (plus `partial` bytes of the next one) of a decoded batch to the sink, in order.
 // D2H time of a batch slot's last drain (memory and placed forms), added to c->d2h_acc once the copies are done
 int harvest_d2h(zpaqhip_ctx *c, int slot, zpaqhip_err *err) {
   if (!c->d_pending[slot]) return ZPAQHIP_OK;
@@ -841,48 +661,28 @@ int harvest_d2h(zpaqhip_ctx *c, int slot, zpaqhip_err *err) {
   return ZPAQHIP_OK;
 }
 
+// Deliver the first `upto_blocks` blocks (plus `partial` bytes of the next one) of a decoded batch to the sink, in order:
+// the copies of plan_delivery (zh_stream_plan.h) on s_out.
 int drain_batch(zpaqhip_ctx *c, const Batch &bt, size_t upto_blocks, uint64_t partial, Sinkk &sink, zpaqhip_err *err) {
-  struct Piece { const uint8_t *p; uint64_t n; };
-  const bool timed = sink.place || sink.mem || !sink.wr;
+  const bool timed = !sink.writer();
   if (timed) {
     int hrc = harvest_d2h(c, bt.slot, err);
     if (hrc) return hrc;
     HIPCHK(hipEventRecord(c->ev_d[bt.slot][0], c->s_out));
   }
-  std::vector<Piece> pieces;
-  for (size_t b = 0; b <= upto_blocks && b < bt.so.blocks.size(); ++b) {
-    const uint64_t n = b < upto_blocks ? bt.real[b] : std::min<uint64_t>(partial, bt.real[b]);
-    if (!n) continue;
-    const uint8_t *p = block_dev_ptr(c, bt, b);
-    if (!pieces.empty() && pieces.back().p + pieces.back().n == p) pieces.back().n += n;     // contiguous on the device too
-    else pieces.push_back({p, n});
-  }
-  if (sink.place) {                                     // placed form: every block at its own offset
-    for (size_t b = 0; b < upto_blocks && b < bt.so.blocks.size(); ++b) {
-      const uint64_t n = bt.real[b], at = sink.place[bt.blk0 + b];
-      if (sink.sizes) (*sink.sizes)[bt.blk0 + b] = n;
-      if (sink.place_cap && n > sink.place_cap[bt.blk0 + b]) {
-        if (sink.spill) {
-          std::vector<uint8_t> &sp = (*sink.spill)[bt.blk0 + b];
-          sp.resize((size_t)n);
-          HIPCHK(hipMemcpyAsync(sp.data(), block_dev_ptr(c, bt, b), (size_t)n, hipMemcpyDeviceToHost, c->s_out));
-        }
-      } else if (n && at < sink.cap)
-        HIPCHK(hipMemcpyAsync(sink.mem + at, block_dev_ptr(c, bt, b), (size_t)std::min<uint64_t>(n, sink.cap - at), hipMemcpyDeviceToHost, c->s_out));
-      sink.total += n;
-    }
-    HIPCHK(hipEventRecord(c->ev_d[bt.slot][1], c->s_out));
-    c->d_pending[bt.slot] = true;
-    return ZPAQHIP_OK;
-  }
-  if (sink.mem || !sink.wr) {
-    for (const Piece &pc : pieces) {
-      if (sink.total < sink.cap) {
-        const uint64_t n = std::min<uint64_t>(pc.n, sink.cap - sink.total);
-        HIPCHK(hipMemcpyAsync(sink.mem + sink.total, pc.p, (size_t)n, hipMemcpyDeviceToHost, c->s_out));
+  const Delivery d = plan_delivery(bt, upto_blocks, partial, sink);
+  auto src_of = [&](const Copy &cp) { return (const uint8_t *)(cp.fix ? c->out_fix[bt.slot].p : c->out2[bt.slot].p) + cp.src_off; };
+  if (timed) {                                          // memory and placed forms
+    for (const Copy &cp : d.copies) {
+      uint8_t *dst = sink.mem + cp.dst;
+      if (cp.spill >= 0) {
+        std::vector<uint8_t> &sp = (*sink.spill)[(size_t)cp.spill];
+        sp.resize((size_t)cp.n);
+        dst = sp.data();
       }
-      sink.total += pc.n;
+      HIPCHK(hipMemcpyAsync(dst, src_of(cp), (size_t)cp.n, hipMemcpyDeviceToHost, c->s_out));
     }
+    sink.total = d.total;
     HIPCHK(hipEventRecord(c->ev_d[bt.slot][1], c->s_out));
     c->d_pending[bt.slot] = true;
     return ZPAQHIP_OK;
@@ -890,7 +690,6 @@ int drain_batch(zpaqhip_ctx *c, const Batch &bt, size_t upto_blocks, uint64_t pa
   // Writer form: pinned double buffer; the copy of chunk i+1 runs while write_fn consumes chunk i
   for (int i = 0; i < 2; ++i)
     if (!c->pin[i]) HIPCHK(hipHostMalloc((void **)&c->pin[i], kPinChunk, hipHostMallocDefault));
-  struct Chunk { uint64_t n; };
   int cur = 0;
   uint64_t fill[2] = {0, 0};
   bool inflight[2] = {false, false};
@@ -907,10 +706,10 @@ int drain_batch(zpaqhip_ctx *c, const Batch &bt, size_t upto_blocks, uint64_t pa
     fill[i] = 0;
     return ZPAQHIP_OK;
   };
-  for (const Piece &pc : pieces) {
-    for (uint64_t done = 0; done < pc.n;) {
-      const uint64_t n = std::min<uint64_t>(pc.n - done, kPinChunk - fill[cur]);
-      HIPCHK(hipMemcpyAsync(c->pin[cur] + fill[cur], pc.p + done, (size_t)n, hipMemcpyDeviceToHost, c->s_out));
+  for (const Copy &cp : d.copies) {
+    for (uint64_t done = 0; done < cp.n;) {
+      const uint64_t n = std::min<uint64_t>(cp.n - done, kPinChunk - fill[cur]);
+      HIPCHK(hipMemcpyAsync(c->pin[cur] + fill[cur], src_of(cp) + done, (size_t)n, hipMemcpyDeviceToHost, c->s_out));
       fill[cur] += n; done += n;
       if (fill[cur] == kPinChunk) {
         HIPCHK(hipEventRecord(c->ev_pin[cur], c->s_out));
@@ -926,11 +725,6 @@ int drain_batch(zpaqhip_ctx *c, const Batch &bt, size_t upto_blocks, uint64_t pa
   if (!rc) rc = flush(cur);
   return rc;
 }
-
-struct SegSink {                          // zpaqhip_decompress_segments: per-segment records in stream order
-  std::vector<zpaqhip_seg_result> res;
-  std::vector<zpaqhip_segment> segs;
-};
 
 // The pipeline.  `tolerate`: per-segment data errors do not end the call (zpaqhip_decompress_segments).
 // *stream_error: the returned code describes the stream (damage behind the delivered blocks), not a failure of the call.
@@ -966,72 +760,42 @@ int run_pipeline_impl(zpaqhip_ctx *c, Source &src, Sinkk &sink, const zpaqhip_op
   c->d2h_acc = 0; c->d_pending[0] = c->d_pending[1] = false;
   Batch bt[2];
   zh_pending P;
-  size_t blk0 = 0, seg0 = 0;
   int final_rc = ZPAQHIP_OK;
   zpaqhip_err final_err{};
-  bool have_prev = false, stop = false;
-  int cur = 0;
   float h2d_ms = 0;
 
-  auto upload = [&](Batch &b) -> int {
+  // ---- the steps of a batch
+  // fetch: the next batch of the source (global indices from blk0 / seg0), its bytes on their way to device slot `slot`
+  auto fetch = [&](int slot, size_t blk0, size_t seg0) -> int {
+    Batch &b = bt[slot];
+    if (int rc = next_batch(src, b, blk0, seg0, (size_t)opts.batch_blocks, (size_t)opts.dec_waves, err)) return rc;
+    b.slot = slot;
     if (b.so.blocks.empty()) return ZPAQHIP_OK;
-    HIPCHK(c->in2[b.slot].reserve(b.len + 16));
+    HIPCHK(c->in2[slot].reserve(b.len + 16));
     HIPCHK(hipEventRecord(c->ev_h0, c->s_in));
-    HIPCHK(hipMemcpyAsync(c->in2[b.slot].p, b.h, b.len, hipMemcpyHostToDevice, c->s_in));
+    HIPCHK(hipMemcpyAsync(c->in2[slot].p, b.h, b.len, hipMemcpyHostToDevice, c->s_in));
     HIPCHK(hipEventRecord(c->ev_h1, c->s_in));
-    HIPCHK(hipEventRecord(c->ev_in[b.slot], c->s_in));
+    HIPCHK(hipEventRecord(c->ev_in[slot], c->s_in));
     return ZPAQHIP_OK;
   };
-
-  int rc = next_batch(src, bt[cur], blk0, seg0, (size_t)opts.batch_blocks, (size_t)opts.dec_waves, err);
-  if (rc) return rc;
-  bt[cur].slot = cur;
-  rc = upload(bt[cur]);
-  if (rc) return rc;
-  for (;;) {
-    Batch &B = bt[cur];
-    const bool have = !B.so.blocks.empty();
-    if (have) {
-      rc = plan_staging(c, B, err);
-      if (rc) return rc;
-      B.res.assign(B.so.segs.size(), zpaqhip_seg_result{});
-      HIPCHK(hipStreamWaitEvent(c->stream, c->ev_in[B.slot], 0));
-      rc = decode_launch(c, c->in2[B.slot].p, B.h, B.len, B.so.blocks.data(), B.so.blocks.size(), B.so.segs.data(),
+  auto add_h2d_time = [&] {                              // of the last upload
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->ev_h0, c->ev_h1) == hipSuccess) h2d_ms += ms; else (void)hipGetLastError();
+  };
+  // launch: the batch's kernels enqueued behind its upload, writing to its staging buffer
+  auto launch = [&](Batch &B) -> int {
+    B.res.assign(B.so.segs.size(), zpaqhip_seg_result{});
+    HIPCHK(hipStreamWaitEvent(c->stream, c->ev_in[B.slot], 0));
+    return decode_launch(c, c->in2[B.slot].p, B.h, B.len, B.so.blocks.data(), B.so.blocks.size(), B.so.segs.data(),
                          B.so.segs.size(), nullptr, 0, c->out2[B.slot].p, B.off.data(), B.cap.data(), opts, c->stream, P, err);
-      if (rc) {                                          // (device memory, HIP): what is already decoded is delivered first
-        rebase_err(err, B);
-        if (have_prev) { zpaqhip_err e3{}; (void)drain_batch(c, bt[cur ^ 1], bt[cur ^ 1].so.blocks.size(), 0, sink, &e3); (void)hipStreamSynchronize(c->s_out); }
-        return rc;
-      }
-    }
-    // ---- while the kernels run: deliver the previous batch, fetch and upload the next one
-    Batch &prev = bt[cur ^ 1];
-    if (have_prev) {
-      rc = drain_batch(c, prev, prev.so.blocks.size(), 0, sink, err);
-      if (rc) return rc;
-      have_prev = false;
-    }
-    bool more = have && !B.last;
-    if (more) {
-      { float ms = 0; if (hipEventElapsedTime(&ms, c->ev_h0, c->ev_h1) == hipSuccess) h2d_ms += ms; else (void)hipGetLastError(); }
-      HIPCHK(hipStreamSynchronize(c->s_out));          // prev's device buffers are about to be reused
-      rc = next_batch(src, prev, blk0 + B.so.blocks.size(), seg0 + B.so.segs.size(), (size_t)opts.batch_blocks, (size_t)opts.dec_waves, err);
-      if (rc) return rc;
-      prev.slot = cur ^ 1;
-      rc = upload(prev);
-      if (rc) return rc;
-    }
-    if (!have) {
-      if (B.rc_after) { final_rc = B.rc_after; final_err = B.err_after; rebase_err(&final_err, B); }
-      break;
-    }
-    // ---- finish this batch
-    rc = decode_finish(c, P, B.res.data(), err);
-    acc.kernel_ms += c->stats.kernel_ms; acc.launches += c->stats.launches; acc.e8_wave_segs += c->stats.e8_wave_segs;
-    acc.blocks += c->stats.blocks; acc.in_bytes += c->stats.in_bytes; acc.model_bytes += c->stats.model_bytes;
-    acc.concurrent = std::max(acc.concurrent, c->stats.concurrent); acc.kernel_kind = std::max(acc.kernel_kind, c->stats.kernel_kind);
+  };
+  // finish: the kernels waited for, the blocks that overflowed their slot decoded again, the checksums compared
+  auto finish = [&](Batch &B) -> int {
+    int rc = decode_finish(c, P, B.res.data(), err);
+    add_kernel_stats(acc, c->stats);
+    add_block_stats(acc, c->stats);
     if (rc && !data_error(rc)) { rebase_err(err, B); return rc; }
-    rc = settle_batch(c, B, opts, tolerate, acc, err);
+    rc = settle_batch(c, B, opts, acc, err);
     if (rc) { rebase_err(err, B); return rc; }
     if (opts.verify_sha1) {
       std::vector<int> bad;
@@ -1040,59 +804,50 @@ int run_pipeline_impl(zpaqhip_ctx *c, Source &src, Sinkk &sink, const zpaqhip_op
       for (size_t s2 = 0; s2 < bad.size(); ++s2)
         if (bad[s2] && B.res[s2].status == ZPAQHIP_OK) B.res[s2].status = ZPAQHIP_E_SHA1;
     }
-    // first segment that failed: everything before it is delivered, then the call ends with its error (the reference
-    // raises on reaching the damaged segment, Decompresser.cs:121-153)
-    size_t ok_blocks = B.so.blocks.size();
-    uint64_t partial = 0;
-    if (!tolerate) {
-      for (size_t b = 0; b < B.so.blocks.size() && !stop; ++b) {
-        const zpaqhip_block &Bk = B.so.blocks[b];
-        uint64_t before = 0;
-        for (uint32_t i = 0; i < Bk.n_seg; ++i) {
-          const zpaqhip_seg_result &r = B.res[Bk.first_seg + i];
-          if (r.status != ZPAQHIP_OK) {
-            stop = true; ok_blocks = b; partial = before;
-            final_rc = r.status == ZH_E_SKIPPED ? ZPAQHIP_E_CORRUPT : r.status;
-            set_err(&final_err, final_rc, (int)(B.blk0 + b), (int)(B.seg0 + Bk.first_seg + i));
-            break;
-          }
-          before += r.out_len;
-        }
-      }
+    return ZPAQHIP_OK;
+  };
+  auto end_of_stream = [&](const Batch &B) {             // a framing error behind the last block: reported when all is delivered
+    if (B.rc_after) { final_rc = B.rc_after; final_err = B.err_after; rebase_err(&final_err, B); }
+  };
+
+  int rc = fetch(0, 0, 0);
+  if (rc) return rc;
+  bool have_prev = false;
+  for (int cur = 0;; cur ^= 1) {
+    Batch &B = bt[cur], &prev = bt[cur ^ 1];
+    const bool have = !B.so.blocks.empty();
+    if (have && (rc = plan_staging(c, B, err))) return rc;
+    if (have && (rc = launch(B))) {                      // (device memory, HIP): what is already decoded is delivered first
+      rebase_err(err, B);
+      if (have_prev) { zpaqhip_err e3{}; (void)drain_batch(c, prev, prev.so.blocks.size(), 0, sink, &e3); (void)hipStreamSynchronize(c->s_out); }
+      return rc;
     }
-    if (segsink) {
-      uint64_t base = sink.total;                       // stream-order offset of this batch's first byte ...
-      uint64_t run = 0;
-      for (size_t b = 0; b < B.so.blocks.size(); ++b) {
-        const zpaqhip_block &Bk = B.so.blocks[b];
-        const uint64_t st_off = (B.off[b] >> 63) ? (B.off[b] & ~(1ull << 63)) : B.off[b];
-        for (uint32_t i = 0; i < Bk.n_seg; ++i) {
-          zpaqhip_seg_result r = B.res[Bk.first_seg + i];
-          r.out_off = base + run + (r.out_off - st_off);
-          segsink->res.push_back(r);
-          zpaqhip_segment sg = B.so.segs[Bk.first_seg + i];
-          sg.block += (uint32_t)B.blk0;
-          segsink->segs.push_back(sg);
-        }
-        run += B.real[b];
-      }
+    // ---- while the kernels run: deliver the previous batch, fetch and upload the next one
+    if (have_prev && (rc = drain_batch(c, prev, prev.so.blocks.size(), 0, sink, err))) return rc;
+    have_prev = false;
+    const bool more = have && !B.last;
+    if (more) {
+      add_h2d_time();
+      HIPCHK(hipStreamSynchronize(c->s_out));          // prev's device buffers are about to be reused
+      if ((rc = fetch(cur ^ 1, B.blk0 + B.so.blocks.size(), B.seg0 + B.so.segs.size()))) return rc;
     }
-    if (stop) {
-      rc = drain_batch(c, B, ok_blocks, partial, sink, err);
-      if (rc) return rc;
+    if (!have) { end_of_stream(B); break; }
+    if ((rc = finish(B))) return rc;
+    const FirstBad bad = tolerate ? FirstBad() : first_failure(B);
+    if (segsink) append_segment_records(B, sink.total, *segsink);
+    if (bad.found) {                                     // everything before the failed segment, then its error
+      final_rc = bad.rc; final_err = bad.err;
+      if ((rc = drain_batch(c, B, bad.ok_blocks, bad.partial, sink, err))) return rc;
       break;
     }
     if (!more) {
-      rc = drain_batch(c, B, B.so.blocks.size(), 0, sink, err);
-      if (rc) return rc;
-      if (B.rc_after) { final_rc = B.rc_after; final_err = B.err_after; rebase_err(&final_err, B); }
+      if ((rc = drain_batch(c, B, B.so.blocks.size(), 0, sink, err))) return rc;
+      end_of_stream(B);
       break;
     }
     have_prev = true;
-    blk0 += B.so.blocks.size(); seg0 += B.so.segs.size();
-    cur ^= 1;
   }
-  { float ms = 0; if (hipEventElapsedTime(&ms, c->ev_h0, c->ev_h1) == hipSuccess) h2d_ms += ms; else (void)hipGetLastError(); }
+  add_h2d_time();
   HIPCHK(hipStreamSynchronize(c->s_out));
   for (int i = 0; i < 2; ++i) { int hrc = harvest_d2h(c, i, err); if (hrc) return hrc; }
   c->stats = acc;
@@ -1161,7 +916,7 @@ int zpaqhip_block_costs(const uint8_t *in, size_t in_len, const zpaqhip_block *b
     }
     uint64_t coded = 0;
     for (uint32_t i = 0; i < B.n_seg; ++i) coded += segs[B.first_seg + i].data_len;
-    const bool hinted = B.usize_hint != UINT64_MAX && B.usize_hint <= (1ull << 40);
+    const bool hinted = plausible_hint(B.usize_hint);
     const uint64_t plain = hinted ? B.usize_hint : coded * 4;
     uint64_t w = it->second;
     if (w >= kCm1Marker - 1) {
@@ -1241,33 +996,22 @@ int zpaqhip_decompress_multi_stats(const int *devices, size_t n_dev, const uint8
   const int scan_rc = scan_stream(in ? in : (const uint8_t *)"", in_len, so, &scan_err);   // blocks before damage are decoded
   const size_t nb = so.blocks.size();
   if (!nb) { if (scan_rc && err) *err = scan_err; return scan_rc; }
-  // ---- the queue
+  // ---- the queue: the blocks by cost, dealt into K chunks
   std::vector<uint64_t> cost(nb, 0);
   { int rc = zpaqhip_block_costs(in, in_len, so.blocks.data(), nb, so.segs.data(), so.segs.size(), cost.data(), err); if (rc) return rc; }
-  std::vector<size_t> order(nb);
-  std::iota(order.begin(), order.end(), (size_t)0);
-  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return cost[a] > cost[b]; });
-  // blocks per pull: what the caller says, or a chunk that fills a GPU (256: one block per CU; 512 where every block is a
-  // single-CM one: two per CU) — but at least four pulls per device, or the queue has nothing to rebalance with
-  // (multigpu.default_queue_blocks is the same rule)
-  size_t chunk_blocks = (size_t)opts.queue_blocks;
+  const std::vector<size_t> order = queue_order(cost);
+  size_t chunk_blocks = (size_t)opts.queue_blocks;      // blocks per pull: what the caller says, or default_chunk_blocks
   if (!chunk_blocks) {
     bool all_cm1 = true;
     for (size_t b = 0; b < nb; ++b) all_cm1 = all_cm1 && so.blocks[b].n_comp == 1;
-    const size_t full = all_cm1 ? 512 : 256, per4 = (nb + 4 * n_dev - 1) / (4 * n_dev);
-    chunk_blocks = n_dev <= 1 ? full : std::max<size_t>(1, std::min(full, per4));     // (one taker: nothing to balance)
+    chunk_blocks = default_chunk_blocks(nb, n_dev, all_cm1);
   }
   const size_t K = (nb + chunk_blocks - 1) / chunk_blocks;
   std::atomic<size_t> next_chunk{0};
   std::atomic<bool> abort_all{false};
-  // ---- placing
-  std::vector<uint64_t> slot_off(nb + 1, 0), slot_cap(nb, 0), real(nb, 0);
-  for (size_t b = 0; b < nb; ++b) {
-    const uint64_t h = so.blocks[b].usize_hint;
-    const bool plausible = h != UINT64_MAX && h <= (1ull << 40) && slot_off[b] + h <= out_cap;
-    slot_cap[b] = plausible ? h : 0;
-    slot_off[b + 1] = slot_off[b] + slot_cap[b];
-  }
+  // ---- slots
+  std::vector<uint64_t> slot_off, slot_cap, real(nb, 0);
+  place_slots(so.blocks, out_cap, slot_off, slot_cap);
   std::vector<std::vector<uint8_t>> spill(nb);
   std::vector<uint8_t> done(nb, 0);
   {  // idle pooled contexts beyond what this call uses on a device give their memory back before the workers size their arenas
@@ -1275,10 +1019,10 @@ int zpaqhip_decompress_multi_stats(const int *devices, size_t n_dev, const uint8
     for (size_t r = 0; r < n_dev; ++r) ++use[devices[r]];
     for (auto &kv : use) pool_trim_device(kv.first, kv.second);
   }
-  struct Job { int rc = 0; zpaqhip_err err{}; long bad = -1; zpaqhip_stats st{}; };
-  std::vector<Job> jobs(n_dev);
+  // ---- workers
+  std::vector<MultiJob> jobs(n_dev);
   auto worker = [&](size_t r) {
-    Job &J = jobs[r];
+    MultiJob &J = jobs[r];
     zpaqhip_ctx *c = pool_take(devices[r], &J.rc, &J.err);
     if (!c) { abort_all = true; return; }
     c->mem_share = 1;
@@ -1290,13 +1034,8 @@ int zpaqhip_decompress_multi_stats(const int *devices, size_t n_dev, const uint8
     while (!abort_all) {
       const size_t k = next_chunk.fetch_add(1);
       if (k >= K) break;
-      ids.clear();
-      for (size_t i = k; i < nb; i += K) ids.push_back(order[i]);
-      std::sort(ids.begin(), ids.end());                 // stream order inside the chunk: the pipeline delivers in order
+      const bool run = queue_chunk(order, k, K, ids);
       sub.clear(); place.clear(); cap.clear();
-      // a chunk of consecutive blocks (one chunk for the whole archive, typically) is decoded where it lies; a strided one
-      // is gathered first
-      const bool run = ids.back() - ids.front() + 1 == ids.size();
       for (size_t b : ids) {
         if (!run) sub.insert(sub.end(), in + so.blocks[b].tag_off, in + so.blocks[b].end_off);
         place.push_back(slot_off[b]); cap.push_back(slot_cap[b]);
@@ -1311,18 +1050,12 @@ int zpaqhip_decompress_multi_stats(const int *devices, size_t n_dev, const uint8
       zpaqhip_err e2{};
       bool stream_error = false;
       const int rc = run_pipeline(c, src, sink, opts, false, nullptr, &e2, &stream_error);
+      add_block_stats(J.st, c->stats);
       J.st.kernel_ms += c->stats.kernel_ms; J.st.h2d_ms += c->stats.h2d_ms; J.st.d2h_ms += c->stats.d2h_ms;
-      J.st.blocks += c->stats.blocks; J.st.in_bytes += c->stats.in_bytes; J.st.out_bytes += c->stats.out_bytes;
-      J.st.model_bytes += c->stats.model_bytes; J.st.launches += 1; J.st.e8_wave_segs += c->stats.e8_wave_segs;
-      J.st.concurrent = std::max(J.st.concurrent, c->stats.concurrent); J.st.kernel_kind = std::max(J.st.kernel_kind, c->stats.kernel_kind);
-      size_t good = ids.size();
-      if (rc) {
-        const bool at_block = (stream_error || data_error(rc)) && e2.block >= 0 && (size_t)e2.block < ids.size();
-        if (!at_block) { if (!J.rc) { J.rc = rc; J.err = e2; J.bad = -1; } abort_all = true; break; }   // the call itself failed
-        good = (size_t)e2.block;
-        const long g = (long)ids[good];
-        if (J.bad < 0 || g < J.bad) { J.rc = rc; J.err = e2; J.bad = g; }
-      }
+      J.st.out_bytes += c->stats.out_bytes; J.st.launches += 1; J.st.e8_wave_segs += c->stats.e8_wave_segs;   // (launches: chunks taken)
+      bool call_failed = false;
+      const size_t good = note_chunk(J, ids, rc, e2, stream_error, &call_failed);
+      if (call_failed) { abort_all = true; break; }
       for (size_t j = 0; j < good; ++j) { real[ids[j]] = sizes[j]; spill[ids[j]].swap(sp[j]); done[ids[j]] = 1; }
     }
     if (J.rc && J.bad < 0) zpaqhip_ctx_destroy(c);       // a failure of the call itself (HIP, memory): do not keep that context
@@ -1334,33 +1067,14 @@ int zpaqhip_decompress_multi_stats(const int *devices, size_t n_dev, const uint8
     for (auto &t : th) t.join();
   }
   if (per_device) for (size_t r = 0; r < n_dev; ++r) per_device[r] = jobs[r].st;
-  // ---- outcome: a failure of the call itself first; else the first damaged block of the stream
-  for (size_t r = 0; r < n_dev; ++r)
-    if (jobs[r].rc && jobs[r].bad < 0) { if (err) *err = jobs[r].err; return jobs[r].rc; }
-  size_t limit = nb;
-  int data_rc = 0;
-  zpaqhip_err data_err{};
-  for (size_t r = 0; r < n_dev; ++r)
-    if (jobs[r].rc && (size_t)jobs[r].bad < limit) { limit = (size_t)jobs[r].bad; data_rc = jobs[r].rc; data_err = jobs[r].err; data_err.block = (int32_t)limit; data_err.segment = -1; }
-  for (size_t b = 0; b < limit; ++b)
+  // ---- merge: a failure of the call itself first; else the first damaged block of the stream
+  const MultiOutcome oc = merge_jobs(jobs, nb);
+  if (oc.rc) { if (err) *err = oc.err; return oc.rc; }
+  for (size_t b = 0; b < oc.limit; ++b)
     if (!done[b]) { set_err(err, ZPAQHIP_E_HIP, (int)b, -1, "multi-device queue: a block was left undecoded"); return ZPAQHIP_E_HIP; }
   // ---- put the blocks whose size was not the promised one in place
-  std::vector<uint64_t> new_off(limit + 1, 0);
-  bool moved = false;
-  for (size_t b = 0; b < limit; ++b) { new_off[b + 1] = new_off[b] + real[b]; moved |= real[b] != slot_cap[b]; }
-  *out_len = (size_t)new_off[limit];
-  if (new_off[limit] > out_cap) { set_err(err, ZPAQHIP_E_OUTPUT_FULL, -1, -1); return ZPAQHIP_E_OUTPUT_FULL; }
-  if (moved) {
-    // blocks that lie in their slot (real <= promised) and move up: last first; those that move down: first first;
-    // a block kept in a host buffer is written last, when every other block is where it belongs
-    for (size_t b = limit; b-- > 0;)
-      if (spill[b].empty() && real[b] && new_off[b] > slot_off[b]) memmove(out + new_off[b], out + slot_off[b], (size_t)real[b]);
-    for (size_t b = 0; b < limit; ++b)
-      if (spill[b].empty() && real[b] && new_off[b] < slot_off[b]) memmove(out + new_off[b], out + slot_off[b], (size_t)real[b]);
-    for (size_t b = 0; b < limit; ++b)
-      if (!spill[b].empty()) memcpy(out + new_off[b], spill[b].data(), (size_t)real[b]);
-  }
-  if (data_rc) { if (err) *err = data_err; return data_rc; }
+  if (int rc = settle_places(out, out_cap, oc.limit, slot_off, slot_cap, real, spill, out_len)) { set_err(err, rc, -1, -1); return rc; }
+  if (oc.data_rc) { if (err) *err = oc.data_err; return oc.data_rc; }
   if (scan_rc) { if (err) *err = scan_err; return scan_rc; }
   return ZPAQHIP_OK;
 }

@@ -57,7 +57,8 @@ def default_queue_blocks(n_blocks: int, world: int, all_single_cm: bool = False)
 
 
 def queue_chunks(costs: Sequence[int], queue_blocks: int = 256) -> List[List[int]]:
-    """The chunks of the dynamic queue (== zpaqhip_decompress_multi): blocks sorted by cost, descending, ties by index;
+    """The chunks of the dynamic queue (== zpaqhip_decompress_multi's, zh_stream_plan.h: tests/test_stream_plan.py holds the
+    two and default_queue_blocks against each other): blocks sorted by cost, descending, ties by index;
     K = ceil(n / queue_blocks) chunks; chunk k = every K-th block of that order starting at k, in stream order.
     Every chunk is a cross-section of the cost distribution, and the chunks' total costs differ by at most one
     block's cost per stride."""

@@ -280,6 +280,45 @@ int zpaqhip_decode_blocks_device(zpaqhip_ctx *ctx, const void *d_in, const uint8
                                  zpaqhip_seg_result *results,
                                  const zpaqhip_opts *opts, void *hip_stream, zpaqhip_err *err);
 
+/* ---- framing of a device-resident stream: zpaqhip_scan with the stream in device memory ------------------------------------
+ * `d_in` is the whole stream on the context's device, under the requirements of zpaqhip_decode_blocks_device: 4-byte aligned
+ * (ZPAQHIP_E_ARG otherwise) and readable up to in_len rounded up to a multiple of 4; nothing behind that is touched.  The
+ * contract is zpaqhip_scan's, field for field, on the same bytes: the same tables (host memory), model_mem included, the same
+ * return code and err.code / block / segment / msg, the same prefix of blocks and segments kept in front of framing damage,
+ * count-only with NULL tables of zero capacity, ZPAQHIP_E_ARG with the required counts when a table is too small.  The
+ * stream stays where it is: one streaming kernel (zh_scan.hip) lists where findBlock's hash matches and where runs of four
+ * or more zero bytes lie, every listed tag is parsed in parallel, and one short serial pass on the device picks the blocks
+ * (DESIGN.md 2.9).  Only the sums of the lists, the scan's result record and the tables cross the bus.  `hip_stream` is a
+ * hipStream_t (NULL = the context's own stream) on which d_in is read; the call returns after its work has completed.
+ * zpaqhip_last_stats: kernel_ms = init_ms = the scan's kernels, launches = their number, blocks, in_bytes = in_len. */
+int zpaqhip_scan_device(zpaqhip_ctx *ctx, const void *d_in, size_t in_len,
+                        zpaqhip_block *blocks, size_t block_cap, size_t *n_blocks,
+                        zpaqhip_segment *segs, size_t seg_cap, size_t *n_segs,
+                        void *hip_stream, zpaqhip_err *err);
+
+/* ---- whole stream, device buffers: LibZPAQ.decompress(Reader, Writer) (LibZPAQ.cs:65-79) with both ends in device memory ---
+ * d_in as for zpaqhip_scan_device, whose tables the call works from; the plaintext arrives in stream order at d_out.
+ * *out_len is always the total; when it exceeds out_cap the call returns ZPAQHIP_E_OUTPUT_FULL and nothing is written at or
+ * past d_out + out_cap.  opts (kernel, verify_sha1, dec_waves, max_concurrent, zpaql_budget) mean what they mean for
+ * zpaqhip_decompress; the SHA-1 is computed on the device.  results (optional: NULL with result_cap 0) receives one record
+ * per segment as zpaqhip_decompress_segments does, out_off relative to d_out; *n_results (optional) their number;
+ * ZPAQHIP_E_ARG with *n_results = the required count when result_cap is too small.
+ * Placement: as long as every block so far has a plausible decimal size in its comments, a block is decoded straight to its
+ * final place.  The first block without one, and what follows it, is decoded to staging slots (those of zpaqhip_decompress)
+ * and gathered into place by the packing kernel (zh_frame.hip) in one launch.  A size that turns out wrong (too small: the
+ * block reports its real length; too large: a gap) makes that block and what follows it move.  No block is decoded more than
+ * twice.  No plaintext and no coded byte crosses the bus: the tables, the block headers and the per-segment results do.
+ * A damaged block: zpaqhip_decompress_multi's contract, not zpaqhip_decompress's: whole blocks only; every block in front of
+ * the damaged one is delivered, *out_len = their bytes, and the damaged block's error is returned (the bytes that block
+ * produced before its error are not delivered).  A framing error behind the last good block is returned after those blocks
+ * have been delivered, as by zpaqhip_decompress.
+ * zpaqhip_last_stats: h2d_ms = d2h_ms = 0; init_ms = the scan's kernels, which also count in kernel_ms and launches (as do
+ * the packing kernel's); blocks, in_bytes, model_bytes, concurrent, kernel_kind as for zpaqhip_decompress. */
+int zpaqhip_decompress_device(zpaqhip_ctx *ctx, const void *d_in, size_t in_len,
+                              void *d_out, size_t out_cap, size_t *out_len,
+                              zpaqhip_seg_result *results, size_t result_cap, size_t *n_results,
+                              const zpaqhip_opts *opts, void *hip_stream, zpaqhip_err *err);
+
 /* zh_chain's LDS plan for the model of a block header (`hdr` as the stream carries it: hsize lo, hsize hi, hh hm ph pm n,
  * components, 0, HCOMP, 0): *waves = the most decoder waves one compute unit holds for it, 1 to 4 (what opts.dec_waves uses
  * at most), or 0 for a model that kernel does not take; *lds_bytes = the LDS of a workgroup of that many waves (the shared

@@ -67,7 +67,8 @@ SYMBOLS = ("zpaqhip_version", "zpaqhip_strerror", "zpaqhip_device_count", "zpaqh
            "zpaqhip_block_pcomp", "zpaqhip_decompress_multi", "zpaqhip_decompress_multi_stats", "zpaqhip_block_costs", "zpaqhip_multi_trim",
            "zpaqhip_compress_blocks", "zpaqhip_preprocess_blocks", "zpaqhip_compress_method_blocks", "zpaqhip_bwt_blocks",
            "zpaqhip_gap_hist_blocks", "zpaqhip_lzsa_blocks", "zpaqhip_lzht_blocks", "zpaqhip_enc_chain_plan",
-           "zpaqhip_dec_chain_plan", "zpaqhip_compress_blocks_device", "zpaqhip_compress_method_blocks_device")
+           "zpaqhip_dec_chain_plan", "zpaqhip_compress_blocks_device", "zpaqhip_compress_method_blocks_device",
+           "zpaqhip_scan_device", "zpaqhip_decompress_device")
 
 _lib = None
 
@@ -123,6 +124,9 @@ def load():
     # the device forms: the host forms' lists with the hip_stream in front of err
     L.zpaqhip_compress_blocks_device.argtypes = L.zpaqhip_compress_blocks.argtypes[:-1] + [vp, errp]
     L.zpaqhip_compress_method_blocks_device.argtypes = L.zpaqhip_compress_method_blocks.argtypes[:-1] + [vp, errp]
+    L.zpaqhip_scan_device.argtypes = [vp, vp, sz, C.POINTER(Block), sz, C.POINTER(sz), C.POINTER(Segment), sz, C.POINTER(sz), vp, errp]
+    L.zpaqhip_decompress_device.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(SegResult), sz, C.POINTER(sz),
+                                            C.POINTER(Opts), vp, errp]
     L.zpaqhip_gap_hist_blocks.argtypes = [vp, vp, vp, sz, vp, errp]
     L.zpaqhip_enc_chain_plan.argtypes = [vp, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), errp]
     L.zpaqhip_dec_chain_plan.argtypes = [vp, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), errp]

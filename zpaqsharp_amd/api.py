@@ -629,6 +629,52 @@ class Context:
         if rc:
             _raise(err, rc)
 
+    def scan_device(self, d_in: int, in_len: int, stream=None, partial: bool = False):
+        """zpaqhip_scan_device: scan() of a stream that lies in device memory (d_in: pointer as int, 4-byte aligned, readable
+        up to in_len rounded up to a multiple of 4; `stream`: a hipStream_t as int, None = the context's own).  Returns what
+        scan() returns for the same bytes, and raises what it raises; partial=True as for scan()."""
+        nb, ns, err = C.c_size_t(0), C.c_size_t(0), Err()
+        hs = int(stream) if stream else None
+        rc = self._L.zpaqhip_scan_device(self._h, d_in or None, in_len, None, 0, C.byref(nb), None, 0, C.byref(ns), hs, C.byref(err))
+        if rc and not partial:
+            _raise(err, rc)
+        blocks = (Block * max(1, nb.value))()
+        segs = (Segment * max(1, ns.value))()
+        if nb.value:
+            rc = self._L.zpaqhip_scan_device(self._h, d_in or None, in_len, blocks, nb.value, C.byref(nb), segs, ns.value,
+                                             C.byref(ns), hs, C.byref(err))
+            if rc and not partial:
+                _raise(err, rc)
+        res = ScanResult((Block * nb.value).from_buffer(blocks) if nb.value else (Block * 0)(),
+                         (Segment * ns.value).from_buffer(segs) if ns.value else (Segment * 0)())
+        if partial:
+            return res, (ZpaqError(rc, err.block, err.segment, err.msg.decode(errors="replace")) if rc else None)
+        return res
+
+    def decompress_device(self, d_in: int, in_len: int, d_out: int, out_cap: int, *, results: bool = False, stream=None,
+                          raise_on_error: bool = True, **opt):
+        """zpaqhip_decompress_device: decompress() with the stream at d_in and the plaintext to d_out, both in device memory
+        (pointers as ints; `stream`: a hipStream_t as int, None = the context's own).  Returns (rc, out_len), with
+        results=True (rc, out_len, SegResult array): rc 0, or -20 (ZPAQHIP_E_OUTPUT_FULL) with out_len the bytes needed and
+        nothing written at or past d_out + out_cap.  Any other status raises unless raise_on_error is False; then rc is the
+        status, out_len the bytes of the whole blocks in front of the damaged one, which are at d_out, and self.last_error
+        the error.  **opt as for decompress()."""
+        o = make_opts(**opt)
+        err, n, nr = Err(), C.c_size_t(0), C.c_size_t(0)
+        hs = int(stream) if stream else None
+        res, rcap = None, 0
+        if results:
+            rcap = max(1, self.scan_device(d_in, in_len, stream, partial=True)[0].n_segments)
+            res = (SegResult * rcap)()
+        rc = self._L.zpaqhip_decompress_device(self._h, d_in or None, in_len, d_out or None, out_cap, C.byref(n), res, rcap,
+                                               C.byref(nr), C.byref(o), hs, C.byref(err))
+        self.last_error = ZpaqError(rc, err.block, err.segment, err.msg.decode(errors="replace")) if rc else None
+        if rc and rc != -20 and raise_on_error:
+            _raise(err, rc)
+        if results:
+            return rc, n.value, (SegResult * nr.value).from_buffer(res) if nr.value else (SegResult * 0)()
+        return rc, n.value
+
     def decode_blocks_device(self, d_in: int, in_len: int, sc: ScanResult, d_out: int,
                              out_off: Sequence[int], out_cap: Sequence[int], ids: Optional[Sequence[int]] = None,
                              h_in=None, hip_stream: int = 0, raise_on_error: bool = True, **opt):

@@ -22,7 +22,9 @@
 #include "zh_compress.h"
 #include "zh_ctx_view.h"
 #include "zh_dec_plan.h"
+#include "zh_frame.h"
 #include "zh_host.h"
+#include "zh_scan.h"
 #include "zh_stream_plan.h"
 #include "zh_zpaql_native.h"
 
@@ -38,6 +40,7 @@ extern "C" int zh_chain2_has(uint32_t spec);
 extern "C" hipError_t zh_launch_nibble(const ZhLaunch *L, uint32_t grid, hipStream_t stream, uint32_t spec, int prof);
 extern "C" int zh_nibble_has(uint32_t spec);
 extern "C" hipError_t zh_launch_store(const ZhLaunch *L, uint32_t grid, hipStream_t stream);
+extern "C" hipError_t zh_launch_frame_pack(const ZhFrameLaunch *L, hipStream_t stream, uint32_t *launches);
 
 
 using namespace zh;
@@ -81,6 +84,9 @@ struct zpaqhip_ctx {
   hipStream_t fam_stream[ZH_NFAM_HOST] = {};
   hipEvent_t fam_ev[ZH_NFAM_HOST] = {};
   hipEvent_t fork_ev = nullptr;
+  // zpaqhip_scan_device: per-piece counts with totals and result, the lists, the per-hit records, the block and segment tables;
+  // zpaqhip_decompress_device: the table of the packing kernel
+  DevBuf scan_cnt, scan_list, scan_rec, scan_blk, scan_seg, pack_tab;
   std::vector<uint32_t> raw_pp;           // last decode: per segment pp_state | PCOMP length << 8, as the kernels report it
 };
 
@@ -152,7 +158,8 @@ void zpaqhip_ctx_destroy(zpaqhip_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   for (DevBuf *b : {&c->tables, &c->arena, &c->models, &c->code, &c->bdesc, &c->sdesc, &c->results, &c->queue, &c->in, &c->out,
-                    &c->in2[0], &c->in2[1], &c->out2[0], &c->out2[1], &c->out_fix[0], &c->out_fix[1]})
+                    &c->in2[0], &c->in2[1], &c->out2[0], &c->out2[1], &c->out_fix[0], &c->out_fix[1], &c->scan_cnt, &c->scan_list, &c->scan_rec,
+                    &c->scan_blk, &c->scan_seg, &c->pack_tab})
     b->release();
   for (int i = 0; i < 2; ++i) {
     if (c->pin[i]) (void)hipHostFree(c->pin[i]);
@@ -1180,6 +1187,380 @@ int zpaqhip_decompress_cb(zpaqhip_ctx *c, zpaqhip_read_fn read_fn, zpaqhip_write
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Device-resident streams: the framing scan on the GPU (zh_scan.hip, zh_scan_walk.h) and the whole-stream form over it
+// ---------------------------------------------------------------------------
+namespace {
+
+struct DevScan {
+  ZhScanLists L{};                        // the lists, in c->scan_list
+  ZhScanResult R{};
+  float ms = 0;                           // HIP-event time of the kernels
+  uint32_t launches = 0;
+};
+
+// The kernels of a timed phase are enqueued by `enqueue`; waits for them
+template <class F>
+int timed_phase(zpaqhip_ctx *c, hipStream_t stream, DevScan &S, zpaqhip_err *err, F enqueue) {
+  HIPCHK(hipEventRecord(c->ev0, stream));
+  if (int rc = enqueue()) return rc;
+  HIPCHK(hipEventRecord(c->ev1, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  S.ms += ms;
+  return ZPAQHIP_OK;
+}
+
+// Lists, per-hit records and the chain: S.R says how many blocks and segments the stream has and how the scan ended; the
+// chosen blocks are in c->scan_blk.  Three words of totals and the result record are all that crosses the bus.
+int scan_device_chain(zpaqhip_ctx *c, const uint8_t *d_in, size_t n, hipStream_t stream, DevScan &S, zpaqhip_err *err) {
+  HIPCHK(hipSetDevice(c->device));
+  const uint64_t np = zh_scan_pieces(n);
+  HIPCHK(c->scan_cnt.reserve((size_t)(3 * np + 8) * 8 + sizeof(ZhScanResult)));
+  uint64_t *d_cnt = (uint64_t *)c->scan_cnt.p, *d_total = d_cnt + 3 * np;
+  ZhScanResult *d_res = (ZhScanResult *)(d_total + 8);
+  uint64_t total[3] = {0, 0, 0};
+  int rc = timed_phase(c, stream, S, err, [&]() -> int {
+    HIPCHK(zh_launch_scan_count(d_in, n, d_cnt, d_total, stream));
+    HIPCHK(hipMemcpyAsync(total, d_total, sizeof total, hipMemcpyDeviceToHost, stream));
+    return ZPAQHIP_OK;
+  });
+  if (rc) return rc;
+  S.launches += 2;
+  if (total[1] != total[2]) { set_err(err, ZPAQHIP_E_HIP, -1, -1, "framing scan: zero-run starts and ends differ"); return ZPAQHIP_E_HIP; }
+  const uint64_t n_tag = total[0], n_run = total[1];
+  HIPCHK(c->scan_list.reserve((size_t)(n_tag + 2 * n_run) * 8 + 16));
+  HIPCHK(c->scan_rec.reserve((size_t)n_tag * sizeof(ZhScanRec) + 16));
+  uint64_t *d_tag = (uint64_t *)c->scan_list.p;
+  S.L = ZhScanLists{d_tag, d_tag + n_tag, d_tag + n_tag + n_run, n_tag, n_run};
+  for (int pass = 0; pass < 2; ++pass) {                // (a second time only for more blocks than tag hits and a few: bare "zPQ" blocks)
+    const uint64_t cap = pass ? S.R.n_blocks : n_tag + 64;
+    HIPCHK(c->scan_blk.reserve((size_t)cap * sizeof(zpaqhip_block) + 16));
+    rc = timed_phase(c, stream, S, err, [&]() -> int {
+      if (!pass) {
+        HIPCHK(zh_launch_scan_fill(d_in, n, d_cnt, d_tag, d_tag + n_tag, d_tag + n_tag + n_run, n_tag, n_run, stream));
+        HIPCHK(zh_launch_scan_parse(d_in, n, &S.L, (ZhScanRec *)c->scan_rec.p, stream));
+        S.launches += n_tag ? 2 : 1;
+      }
+      HIPCHK(zh_launch_scan_chain(d_in, n, &S.L, (const ZhScanRec *)c->scan_rec.p, (zpaqhip_block *)c->scan_blk.p, cap, d_res, stream));
+      ++S.launches;
+      HIPCHK(hipMemcpyAsync(&S.R, d_res, sizeof S.R, hipMemcpyDeviceToHost, stream));
+      return ZPAQHIP_OK;
+    });
+    if (rc) return rc;
+    if (S.R.n_blocks <= cap) break;
+  }
+  return ZPAQHIP_OK;
+}
+
+// The tables of the chain's blocks to the host
+int scan_device_tables(zpaqhip_ctx *c, const uint8_t *d_in, size_t n, hipStream_t stream, DevScan &S, zpaqhip_block *blocks,
+                       zpaqhip_segment *segs, zpaqhip_err *err) {
+  const uint64_t nb = S.R.n_blocks, ns = S.R.n_segs;
+  if (!nb) return ZPAQHIP_OK;
+  HIPCHK(c->scan_seg.reserve((size_t)ns * sizeof(zpaqhip_segment) + 16));
+  return timed_phase(c, stream, S, err, [&]() -> int {
+    HIPCHK(zh_launch_scan_segments(d_in, n, &S.L, (const zpaqhip_block *)c->scan_blk.p, nb, (zpaqhip_segment *)c->scan_seg.p, ns, stream));
+    ++S.launches;
+    HIPCHK(hipMemcpyAsync(blocks, c->scan_blk.p, (size_t)nb * sizeof(zpaqhip_block), hipMemcpyDeviceToHost, stream));
+    if (ns) HIPCHK(hipMemcpyAsync(segs, c->scan_seg.p, (size_t)ns * sizeof(zpaqhip_segment), hipMemcpyDeviceToHost, stream));
+    return ZPAQHIP_OK;
+  });
+}
+
+void scan_device_err(const DevScan &S, zpaqhip_err *e) {
+  set_err(e, S.R.status, S.R.err_block, S.R.err_seg, zh_scan_message(S.R.msg));
+}
+
+bool device_stream_ok(const void *d_in, size_t in_len) { return (d_in || !in_len) && ((uintptr_t)d_in & 3u) == 0; }
+
+}  // namespace
+
+extern "C" int zpaqhip_scan_device(zpaqhip_ctx *c, const void *d_in, size_t in_len, zpaqhip_block *blocks, size_t block_cap,
+                                   size_t *n_blocks, zpaqhip_segment *segs, size_t seg_cap, size_t *n_segs, void *hip_stream,
+                                   zpaqhip_err *err) {
+  if (!c || !device_stream_ok(d_in, in_len) || !n_blocks || !n_segs || (!blocks && block_cap) || (!segs && seg_cap)) {
+    set_err(err, ZPAQHIP_E_ARG, -1, -1);
+    return ZPAQHIP_E_ARG;
+  }
+  hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  DevScan S;
+  if (int rc = scan_device_chain(c, (const uint8_t *)d_in, in_len, stream, S, err)) return rc;
+  const int rc = S.R.status;
+  zpaqhip_err e2{};
+  if (rc) scan_device_err(S, &e2);
+  *n_blocks = (size_t)S.R.n_blocks;
+  *n_segs = (size_t)S.R.n_segs;
+  memset(&c->stats, 0, sizeof c->stats);
+  c->stats.blocks = S.R.n_blocks;
+  c->stats.in_bytes = in_len;
+  auto done = [&](int r) { c->stats.kernel_ms = c->stats.init_ms = S.ms; c->stats.launches = S.launches; return r; };
+  if (S.R.n_blocks > block_cap || S.R.n_segs > seg_cap) {      // zpaqhip_scan's rules: count only, or a table too small
+    if (block_cap || seg_cap) { set_err(err, ZPAQHIP_E_ARG, -1, -1, "block/segment table too small"); return done(ZPAQHIP_E_ARG); }
+    if (rc && err) *err = e2;
+    return done(rc);
+  }
+  if (int rc2 = scan_device_tables(c, (const uint8_t *)d_in, in_len, stream, S, blocks, segs, err)) return rc2;
+  if (rc && err) *err = e2;
+  return done(rc);
+}
+
+extern "C" int zpaqhip_decompress_device(zpaqhip_ctx *c, const void *d_in, size_t in_len, void *d_out, size_t out_cap,
+                                         size_t *out_len, zpaqhip_seg_result *results, size_t result_cap, size_t *n_results,
+                                         const zpaqhip_opts *opts_in, void *hip_stream, zpaqhip_err *err) {
+  if (!c || !device_stream_ok(d_in, in_len) || !out_len || (!d_out && out_cap) || (!results && result_cap)) {
+    set_err(err, ZPAQHIP_E_ARG, -1, -1);
+    return ZPAQHIP_E_ARG;
+  }
+  const zpaqhip_opts opts = resolve_opts(opts_in);
+  hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : c->stream;
+  const uint8_t *in = (const uint8_t *)d_in;
+  *out_len = 0;
+  if (n_results) *n_results = 0;
+
+  // ---- the tables
+  DevScan S;
+  if (int rc = scan_device_chain(c, in, in_len, stream, S, err)) return rc;
+  std::vector<zpaqhip_block> blocks((size_t)S.R.n_blocks);
+  std::vector<zpaqhip_segment> segs((size_t)S.R.n_segs);
+  if (int rc = scan_device_tables(c, in, in_len, stream, S, blocks.data(), segs.data(), err)) return rc;
+  int after_rc = S.R.status;                            // what ends the stream behind the last good block
+  zpaqhip_err after_err{};
+  if (after_rc) scan_device_err(S, &after_err);
+  zpaqhip_stats acc{};
+  acc.kernel_ms = acc.init_ms = S.ms;
+  acc.launches = S.launches;
+  size_t nb = blocks.size();
+  {
+    // a header the scan accepts can still be refused when the model is built: the stream ends in front of the first such
+    // block, with its error (cut_at_bad_model, zh_stream_plan.h)
+    std::map<std::string, int> seen;
+    std::vector<uint8_t> hdr, code;
+    for (size_t b = 0; b < nb; ++b) {
+      hdr.resize(blocks[b].hdr_len);
+      HIPCHK(hipMemcpyAsync(hdr.data(), in + blocks[b].hdr_off, hdr.size(), hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      std::string key((const char *)hdr.data(), hdr.size());
+      auto it = seen.find(key);
+      if (it != seen.end() && !it->second) continue;
+      ZhModel m;
+      zpaqhip_err e2{};
+      code.clear();
+      const int mrc = build_model(hdr.data(), hdr.size(), m, code, &e2);
+      seen[key] = mrc;
+      if (!mrc) continue;
+      e2.block = (int32_t)b; e2.segment = -1;
+      after_rc = mrc; after_err = e2; nb = b;
+      break;
+    }
+  }
+  const size_t ns = nb ? blocks[nb - 1].first_seg + blocks[nb - 1].n_seg : 0;
+
+  // ---- first decode: the blocks in front of the first one without a plausible size straight to their place (what lies
+  // behind out_cap counted, not written), the rest to staging slots
+  std::vector<zpaqhip_seg_result> res(segs.size());
+  std::vector<uint64_t> place(nb + 1, 0), cap(nb, 0), real(nb, 0), at(nb, 0);   // at: where the block lies in its buffer
+  enum Where : uint8_t { kPlace, kStaged, kMoved, kFix };
+  std::vector<uint8_t> where(nb, kPlace);
+  size_t k = 0;
+  while (k < nb && plausible_hint(blocks[k].usize_hint)) { place[k + 1] = place[k] + blocks[k].usize_hint; ++k; }
+  size_t limit = nb;                                    // the first block with a data error: nothing from it on is delivered
+  int bad_rc = ZPAQHIP_OK;
+  zpaqhip_err bad_err{};
+  bool first_time = true;
+  // decodes blocks `ids` to base + off[i], at most cp[i] bytes; notes their plaintext sizes and the first failure
+  auto decode = [&](const std::vector<uint32_t> &ids, void *base, const std::vector<uint64_t> &off, const std::vector<uint64_t> &cp) -> int {
+    if (ids.empty()) return ZPAQHIP_OK;
+    zh_pending P;
+    zpaqhip_err e2{};
+    int rc = decode_launch(c, in, nullptr, in_len, blocks.data(), nb, segs.data(), ns, ids.data(), ids.size(), base, off.data(),
+                           cp.data(), opts, stream, P, &e2);
+    if (!rc) rc = decode_finish(c, P, res.data(), &e2);
+    add_kernel_stats(acc, c->stats);
+    if (first_time) add_block_stats(acc, c->stats);
+    if (rc && !data_error(rc)) { if (err) *err = e2; return rc; }
+    for (uint32_t b : ids) {
+      real[b] = 0;
+      for (uint32_t i = 0; i < blocks[b].n_seg; ++i) real[b] += res[blocks[b].first_seg + i].out_len;
+    }
+    return ZPAQHIP_OK;
+  };
+  auto note_failures = [&]() {                          // the lowest block with a segment that failed
+    for (size_t b = 0; b < limit; ++b)
+      for (uint32_t i = 0; i < blocks[b].n_seg; ++i) {
+        const int st = res[blocks[b].first_seg + i].status;
+        if (st == ZPAQHIP_OK || st == ZPAQHIP_E_OUTPUT_FULL) continue;
+        limit = b;
+        bad_rc = st == ZH_E_SKIPPED ? ZPAQHIP_E_CORRUPT : st;
+        set_err(&bad_err, bad_rc, (int)b, (int)(blocks[b].first_seg + i));
+        return;
+      }
+  };
+  std::vector<uint32_t> ids;
+  std::vector<uint64_t> off, cp;
+  for (size_t b = 0; b < k; ++b) {
+    ids.push_back((uint32_t)b);
+    off.push_back(place[b]);
+    cap[b] = place[b] >= out_cap ? 0 : std::min<uint64_t>(blocks[b].usize_hint, out_cap - place[b]);
+    cp.push_back(cap[b]);
+    at[b] = place[b];
+  }
+  if (int rc = decode(ids, d_out, off, cp)) return rc;
+  note_failures();
+  if (limit > k) {                                      // staging for the rest
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    free_b += c->out2[0].cap;
+    std::vector<zpaqhip_block> rest(blocks.begin() + (ptrdiff_t)k, blocks.begin() + (ptrdiff_t)nb);
+    std::vector<uint64_t> rcap, roff;
+    const uint64_t bytes = plan_slots(rest, segs, free_b / 4 / std::max(1u, c->mem_share), rcap, roff);
+    if (c->out2[0].reserve((size_t)bytes + 16) != hipSuccess) {   // not even that: everything count-only, exact second pass
+      (void)hipGetLastError();
+      std::fill(rcap.begin(), rcap.end(), 0ull);
+      std::fill(roff.begin(), roff.end(), 0ull);
+      HIPCHK(c->out2[0].reserve(16));
+    }
+    ids.clear();
+    for (size_t b = k; b < nb; ++b) { ids.push_back((uint32_t)b); cap[b] = rcap[b - k]; at[b] = roff[b - k]; where[b] = kStaged; }
+    if (int rc = decode(ids, c->out2[0].p, roff, rcap)) return rc;
+    note_failures();
+  }
+  first_time = false;
+
+  // ---- a size comment that was wrong: the first such block keeps its place when it is shorter, everything behind it moves
+  size_t wrong = k;
+  for (size_t b = 0; b < k && b < limit; ++b)
+    if (real[b] != blocks[b].usize_hint) { wrong = b; break; }
+  // second decode, with the exact size, of every block that outgrew its slot (a block is decoded twice at most)
+  ids.clear(); off.clear(); cp.clear();
+  uint64_t fix_bytes = 0;
+  std::vector<ZhFrameEntry> move;                        // blocks decoded to a wrong place that are whole: out of the way first
+  for (size_t b = 0; b < limit; ++b) {
+    if (real[b] > cap[b]) {
+      ids.push_back((uint32_t)b); off.push_back(fix_bytes); cp.push_back(real[b]);
+      where[b] = kFix; at[b] = fix_bytes; cap[b] = real[b];
+    } else if (b < k && b > wrong) {
+      ZhFrameEntry e{};
+      e.dst_off = fix_bytes; e.src_off = place[b]; e.body_len = real[b]; e.src = ZH_FRAME_SRC_INPUT;
+      if (real[b]) move.push_back(e);
+      where[b] = kMoved; at[b] = fix_bytes;
+    } else continue;
+    fix_bytes += real[b];
+  }
+  float pack_ms = 0;
+  uint32_t pack_launches = 0;
+  // zh_frame.hip over entries without head and tail: bodies from staging (FIRST), the second-pass buffer (REDO) or d_out (INPUT)
+  auto pack = [&](const std::vector<ZhFrameEntry> &tab, uint8_t *dst) -> int {
+    if (tab.empty()) return ZPAQHIP_OK;
+    const size_t tb = tab.size() * sizeof(ZhFrameEntry);
+    HIPCHK(c->pack_tab.reserve(tb + 32));
+    HIPCHK(hipMemcpyAsync(c->pack_tab.p, tab.data(), tb, hipMemcpyHostToDevice, stream));
+    ZhFrameLaunch L;
+    memset(&L, 0, sizeof L);
+    L.table = (const ZhFrameEntry *)c->pack_tab.p;
+    L.blob = (const uint8_t *)c->pack_tab.p + tb;
+    L.src[ZH_FRAME_SRC_FIRST] = (const uint8_t *)c->out2[0].p;
+    L.src[ZH_FRAME_SRC_REDO] = (const uint8_t *)c->out_fix[0].p;
+    L.src[ZH_FRAME_SRC_INPUT] = (const uint8_t *)d_out;
+    L.out = dst;
+    L.n = (uint32_t)tab.size();
+    uint64_t longest = 0;
+    for (const ZhFrameEntry &e : tab) longest = std::max(longest, e.body_len);
+    L.pieces = (uint32_t)std::max<uint64_t>(1, (longest + ZH_FRAME_PIECE - 1) / ZH_FRAME_PIECE);
+    HIPCHK(hipEventRecord(c->ev0, stream));
+    HIPCHK(zh_launch_frame_pack(&L, stream, &pack_launches));
+    HIPCHK(hipEventRecord(c->ev1, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    pack_ms += ms;
+    return ZPAQHIP_OK;
+  };
+  if (fix_bytes) HIPCHK(c->out_fix[0].reserve((size_t)fix_bytes + 16));
+  if (int rc = pack(move, (uint8_t *)c->out_fix[0].p)) return rc;
+  if (int rc = decode(ids, c->out_fix[0].p, off, cp)) return rc;
+  note_failures();
+
+  // ---- checksums, on the device, where the plaintext lies
+  auto base_of = [&](size_t b) -> const uint8_t * {
+    return where[b] == kPlace ? (const uint8_t *)d_out : where[b] == kStaged ? (const uint8_t *)c->out2[0].p : (const uint8_t *)c->out_fix[0].p;
+  };
+  // a moved block's results still speak of its first place
+  auto seg_at = [&](size_t b, size_t s) { return where[b] == kMoved ? at[b] + (res[s].out_off - place[b]) : res[s].out_off; };
+  if (opts.verify_sha1) {
+    for (int w = 0; w < 3; ++w) {                       // d_out, staging, second-pass buffer
+      std::vector<uint64_t> tab;
+      std::vector<uint32_t> which;
+      const uint8_t *base = nullptr;
+      for (size_t b = 0; b < limit; ++b) {
+        if ((where[b] == kPlace ? 0 : where[b] == kStaged ? 1 : 2) != w) continue;
+        base = base_of(b);
+        for (uint32_t i = 0; i < blocks[b].n_seg; ++i) {
+          const size_t s = blocks[b].first_seg + i;
+          if (!(segs[s].flags & 1) || res[s].status != ZPAQHIP_OK) continue;
+          tab.push_back(seg_at(b, s)); tab.push_back(res[s].out_len); which.push_back((uint32_t)s);
+        }
+      }
+      if (which.empty()) continue;
+      const size_t tab_bytes = tab.size() * 8, dig_bytes = which.size() * 20;
+      HIPCHK(c->sdesc.reserve(tab_bytes + dig_bytes + 64));
+      uint8_t *d_tab = (uint8_t *)c->sdesc.p, *d_dig = d_tab + ((tab_bytes + 15) & ~(size_t)15);
+      HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, stream));
+      HIPCHK(zh_launch_sha1(base, (const uint64_t *)d_tab, (uint32_t)which.size(), (uint32_t *)d_dig, stream));
+      std::vector<uint32_t> dig(which.size() * 5);
+      HIPCHK(hipMemcpyAsync(dig.data(), d_dig, dig_bytes, hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+      for (size_t j = 0; j < which.size(); ++j) {
+        uint8_t d[20];
+        for (int i = 0; i < 5; ++i) {
+          const uint32_t v = dig[5 * j + i];
+          d[4 * i] = (uint8_t)(v >> 24); d[4 * i + 1] = (uint8_t)(v >> 16); d[4 * i + 2] = (uint8_t)(v >> 8); d[4 * i + 3] = (uint8_t)v;
+        }
+        if (memcmp(d, segs[which[j]].sha1, 20) != 0) res[which[j]].status = ZPAQHIP_E_SHA1;
+      }
+    }
+    note_failures();
+  }
+
+  // ---- every delivered block that is not in its place yet gathered there in one launch, clipped at out_cap
+  std::vector<uint64_t> dst(limit + 1, 0);
+  for (size_t b = 0; b < limit; ++b) dst[b + 1] = dst[b] + real[b];
+  std::vector<ZhFrameEntry> gather;
+  for (size_t b = 0; b < limit; ++b) {
+    if (where[b] == kPlace || !real[b] || dst[b] >= out_cap) continue;
+    ZhFrameEntry e{};
+    e.dst_off = dst[b]; e.src_off = at[b]; e.body_len = std::min<uint64_t>(real[b], out_cap - dst[b]);
+    e.src = where[b] == kStaged ? ZH_FRAME_SRC_FIRST : ZH_FRAME_SRC_REDO;
+    gather.push_back(e);
+  }
+  if (int rc = pack(gather, (uint8_t *)d_out)) return rc;
+  *out_len = (size_t)dst[limit];
+
+  // ---- per-segment outcomes (optional), out_off in stream order
+  const size_t n_res = limit < nb ? blocks[limit].first_seg + blocks[limit].n_seg : ns;
+  if (n_results) *n_results = n_res;
+  memset(&c->stats, 0, sizeof c->stats);
+  c->stats = acc;
+  c->stats.kernel_ms += pack_ms;
+  c->stats.launches += pack_launches;
+  c->stats.out_bytes = dst[limit];
+  if (results || result_cap) {
+    if (n_res > result_cap) { set_err(err, ZPAQHIP_E_ARG, -1, -1, "result table too small"); return ZPAQHIP_E_ARG; }
+    for (size_t b = 0; b < nb && b <= limit; ++b)
+      for (uint32_t i = 0; i < blocks[b].n_seg; ++i) {
+        const size_t s = blocks[b].first_seg + i;
+        zpaqhip_seg_result r = res[s];
+        if (b < limit) r.out_off = dst[b] + (seg_at(b, s) - at[b]);
+        results[s] = r;
+      }
+  }
+  if (bad_rc) { if (err) *err = bad_err; return bad_rc; }
+  if (after_rc) { if (err) *err = after_err; return after_rc; }
+  if (dst[limit] > out_cap) { set_err(err, ZPAQHIP_E_OUTPUT_FULL, -1, -1); return ZPAQHIP_E_OUTPUT_FULL; }
+  return ZPAQHIP_OK;
+}
 
 // zh_compress.cpp works on a context through this view (zh_ctx_view.h)
 zh::CtxView zh::ctx_view(zpaqhip_ctx *c) {

@@ -491,6 +491,40 @@ int zpaqhip_compress_method_blocks_device(zpaqhip_ctx *ctx, const int32_t args[9
                                           size_t *out_len, uint64_t *block_off, const zpaqhip_compress_opts *opts,
                                           void *hip_stream, zpaqhip_err *err);
 
+/* ---- a method per block: what LibZPAQ.compressBlock does with a numeric level (LibZPAQ.cs:84-283), device-resident ----------
+ * zpaqhip_compress_method_blocks_device for blocks that do not all take the same method: methods[0, n_methods) is the list
+ * (args, hdr and pcomp of each as for zpaqhip_compress_method_blocks; `reserved` must be 0), method_of[i] the entry block i
+ * takes.  d_out[0, *out_len) holds the blocks in input order, block i exactly the bytes zpaqhip_compress_method_blocks writes
+ * for it with methods[method_of[i]] and the same opts (bits 0 to 4 of opts.flags apply to every method), block_off[0..n_blocks]
+ * their offsets.  With out_cap too small: ZPAQHIP_E_OUTPUT_FULL with *out_len = the bytes needed, every block that fits in
+ * whole written (the offsets only grow, so these are the first blocks of the call) and nothing written at or past d_out +
+ * out_cap.  ZPAQHIP_E_ARG before the device is touched: a NULL context, d_out == NULL with a capacity, decreasing offsets,
+ * n_methods == 0 with blocks, a method_of[i] >= n_methods (err->block = i), a non-zero `reserved`, and whatever the method form
+ * refuses for a method and the length of a block that takes it; err->block is always the block's index in this call.  A
+ * method that no block takes is not checked against any block.
+ * How: the blocks of each method that is used run as one group through the method form's path, whose stream goes to a scratch
+ * stream in device memory that the call owns; the groups lie back to back in it.  The scratch grows to what the groups
+ * turn out to need (it doubles, keeping what it holds; ZPAQHIP_E_DEVICE_MEM when it cannot), so it ends between one and two
+ * times the size of the output.  One more launch of the packing kernel then gathers the blocks into d_out in input order:
+ * one device-to-device pass over the coded bytes.  No plaintext and no coded byte crosses the bus.  Alignment and hip_stream
+ * as for the two calls above.
+ * zpaqhip_last_stats: kernel_ms and init_ms summed over the groups, the gather's time added to kernel_ms; launches = the
+ * groups' launches plus the gather's; blocks, in_bytes and out_bytes of the whole call; kernel_kind and concurrent the
+ * largest among the groups; and, for this call only, model_bytes = the scratch stream's capacity at the end of the call and
+ * e8_wave_segs = the gather launch's own time in microseconds (both 0 in every other compressing call). */
+typedef struct zpaqhip_method {          /* one entry of the method list of a mixed call */
+  int32_t args[9];                       /* as for zpaqhip_compress_method_blocks */
+  uint32_t reserved;                     /* must be 0 */
+  const uint8_t *hdr;   size_t hdr_len;
+  const uint8_t *pcomp; size_t pcomp_len;
+} zpaqhip_method;
+
+int zpaqhip_compress_mixed_blocks_device(zpaqhip_ctx *ctx, const zpaqhip_method *methods, size_t n_methods,
+                                         const uint32_t *method_of, const void *d_in, const uint64_t *in_off, size_t n_blocks,
+                                         const char *const *filenames, void *d_out, size_t out_cap, size_t *out_len,
+                                         uint64_t *block_off, const zpaqhip_compress_opts *opts, void *hip_stream,
+                                         zpaqhip_err *err);
+
 /* ---- the data analysis of LibZPAQ.compressBlock's numeric levels 5..9 (LibZPAQ.cs:242-255) -------------------------------
  * The histogram of repetition gaps of each block p = in[in_off[i], in_off[i+1]): with pt[256] and r[4096] all zero,
  *     for j in 0..n-1:  k = j - pt[p[j]];  if 0 < k < 4096: ++r[k];  pt[p[j]] = j
@@ -503,6 +537,14 @@ int zpaqhip_compress_method_blocks_device(zpaqhip_ctx *ctx, const int32_t args[9
  * in_bytes = plaintext, out_bytes = n_blocks * 16 384. */
 int zpaqhip_gap_hist_blocks(zpaqhip_ctx *ctx, const uint8_t *in, const uint64_t *in_off, size_t n_blocks, uint32_t *hist,
                             zpaqhip_err *err);
+
+/* zpaqhip_gap_hist_blocks with the plaintext in device memory: block i is d_in[in_off[i], in_off[i+1]) on the context's
+ * device; in_off and hist stay host memory, and the histograms (16 384 bytes per block) are all that crosses the bus.  The
+ * same limits and the same histograms.  `hip_stream` as for zpaqhip_compress_blocks_device.  Alignment: none is asked of
+ * d_in; the kernel reads it where it is, in aligned 16-byte groups that hold at least one byte of the block it walks.
+ * zpaqhip_last_stats as for the host form, with h2d_ms = 0. */
+int zpaqhip_gap_hist_blocks_device(zpaqhip_ctx *ctx, const void *d_in, const uint64_t *in_off, size_t n_blocks, uint32_t *hist,
+                                   void *hip_stream, zpaqhip_err *err);
 
 #ifdef __cplusplus
 }

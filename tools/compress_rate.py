@@ -33,8 +33,9 @@ values alternated in the same way, inside each --kernel value; "in_flight" is st
 with that decoder kernel (4 = zh_chain.hip, level walk at run time).  --no-cpu skips the CPU writer and with it every
 comparison with it (cpu16_MBps, identical, cpu16_ratio); the round trip and same_as_first remain.
 
---device (with --model or --method): the host form (Context.compress_blocks / compress_method) and the device form
-(compress_blocks_device / compress_method_device) on the same blocks, ALTERNATED in one process, --rounds times each
+--device (with --model, --method or --level): the host form (Context.compress_blocks / compress_method / compress_level) and
+the device form (compress_blocks_device / compress_method_device / compress_level_device, whose rows also carry the gather
+launch's own time and the scratch stream's bytes) on the same blocks, ALTERNATED in one process, --rounds times each
 (default 2 here), one JSON line per call: wall time of the call, kernel_ms, launches.  The device form's input tensor is
 filled before the clock starts and its output is compared with the host form's stream on the device ("identical").  A last
 line gives the packing kernel's own rate for a method without a model (the store layout): there kernel_ms is the
@@ -114,14 +115,19 @@ def run_device(ctx, a, kernels):
         d_in = torch.empty(a.blocks * a.block_size, dtype=torch.uint8, device="cuda")
         for i, b in enumerate(blocks):          # the generator is a host one: block by block, before any clock starts
             d_in[i * a.block_size:(i + 1) * a.block_size].copy_(torch.from_numpy(b))
-        what = {"method": a.method} if a.method else {"model": a.model}
+        what = {"level": a.level} if a.level else {"method": a.method} if a.method else {"model": a.model}
         for k in kernels:
             def host(bl, k=k):
+                if a.level:
+                    return ctx.compress_level(a.level, bl, kernel=k, sa=a.sa, ht=a.ht)
                 if a.method:
                     return ctx.compress_method(a.method, bl, bwt=a.bwt, kernel=k, sa=a.sa, ht=a.ht)
                 return ctx.compress_blocks(a.model, bl, kernel=k)
 
             def device(n, d_out, k=k):
+                if a.level:
+                    return ctx.compress_level_device(a.level, d_in.data_ptr(), in_off[:n + 1], d_out.data_ptr(), d_out.numel(),
+                                                     kernel=k, sa=a.sa, ht=a.ht)
                 if a.method:
                     return ctx.compress_method_device(a.method, d_in.data_ptr(), in_off[:n + 1], d_out.data_ptr(), d_out.numel(),
                                                       bwt=a.bwt, kernel=k, sa=a.sa, ht=a.ht)
@@ -131,7 +137,7 @@ def run_device(ctx, a, kernels):
             d_want = torch.from_numpy(np.frombuffer(want, np.uint8).copy()).cuda()
             d_out = torch.empty(len(want) + 4096, dtype=torch.uint8, device="cuda")
             device(a.blocks, d_out)                                          # (the full shape: the first call of a size pays its allocations)
-            store = bool(a.method) and method.model_of(a.method)[0].header[6] == 0
+            store = bool(a.method) and not a.level and method.model_of(a.method)[0].header[6] == 0
             pack_ms = None
             for rnd in range(a.rounds):
                 for form in ("host", "device"):
@@ -148,9 +154,16 @@ def run_device(ctx, a, kernels):
                         same = bool(rc == 0 and n == len(want) and torch.equal(d_out[:n], d_want))
                     if form == "device" and store:
                         pack_ms = min(pack_ms or 1e30, st.kernel_ms - st.init_ms)
-                    print(json.dumps({**what, "kind": kind, "blocks": a.blocks, "block_size": a.block_size, "kernel": k, "form": form,
-                                      "round": rnd, "wall_s": wall, "MBps": mb / wall, "kernel_ms": st.kernel_ms, "pre_ms": st.init_ms,
-                                      "launches": st.launches, "out_bytes": st.out_bytes, "identical": same}), flush=True)
+                    row = {**what, "kind": kind, "blocks": a.blocks, "block_size": a.block_size, "kernel": k, "form": form,
+                           "round": rnd, "wall_s": wall, "MBps": mb / wall, "kernel_ms": st.kernel_ms, "pre_ms": st.init_ms,
+                           "launches": st.launches, "out_bytes": st.out_bytes, "identical": same}
+                    if a.level and form == "device":          # the mixed call's own figures: the gather launch, the scratch stream
+                        row.update({"gather_ms": st.e8_wave_segs / 1e3, "scratch_bytes": st.model_bytes,
+                                    "groups": len(set(ctx.level_methods))})
+                    elif a.level:                             # the host form's statistics are its last group's: its wall time splits instead
+                        row.update({"kernel_ms": None, "pre_ms": None, "launches": None, "out_bytes": len(got),
+                                    "analysis_ms": ctx.level_ms["analysis"], "encode_ms": ctx.level_ms["encode"]})
+                    print(json.dumps(row), flush=True)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             d2d = 1e30
             for _ in range(3):

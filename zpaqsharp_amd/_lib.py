@@ -57,7 +57,13 @@ class CompressOpts(C.Structure):
                 ("batch_blocks", C.c_uint64), ("slot_bytes", C.c_uint64), ("reserved", C.c_uint64 * 2)]
 
 
-READ_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_int)
+class Method(C.Structure):
+    """zpaqhip_method: one entry of the method list of zpaqhip_compress_mixed_blocks_device."""
+    _fields_ = [("args", C.c_int32 * 9), ("reserved", C.c_uint32), ("hdr", C.c_void_p), ("hdr_len", C.c_size_t),
+                ("pcomp", C.c_void_p), ("pcomp_len", C.c_size_t)]
+
+
+READ_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_int)
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_int)
 
 # Every symbol include/zpaqhip.h declares; tests check the library exports them all.
@@ -68,7 +74,8 @@ SYMBOLS = ("zpaqhip_version", "zpaqhip_strerror", "zpaqhip_device_count", "zpaqh
            "zpaqhip_compress_blocks", "zpaqhip_preprocess_blocks", "zpaqhip_compress_method_blocks", "zpaqhip_bwt_blocks",
            "zpaqhip_gap_hist_blocks", "zpaqhip_lzsa_blocks", "zpaqhip_lzht_blocks", "zpaqhip_enc_chain_plan",
            "zpaqhip_dec_chain_plan", "zpaqhip_compress_blocks_device", "zpaqhip_compress_method_blocks_device",
-           "zpaqhip_scan_device", "zpaqhip_decompress_device")
+           "zpaqhip_scan_device", "zpaqhip_decompress_device", "zpaqhip_compress_mixed_blocks_device",
+           "zpaqhip_gap_hist_blocks_device")
 
 _lib = None
 
@@ -127,7 +134,10 @@ def load():
     L.zpaqhip_scan_device.argtypes = [vp, vp, sz, C.POINTER(Block), sz, C.POINTER(sz), C.POINTER(Segment), sz, C.POINTER(sz), vp, errp]
     L.zpaqhip_decompress_device.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(SegResult), sz, C.POINTER(sz),
                                             C.POINTER(Opts), vp, errp]
+    L.zpaqhip_compress_mixed_blocks_device.argtypes = [vp, C.POINTER(Method), sz, vp, vp, vp, sz, vp, vp, sz, C.POINTER(sz), vp,
+                                                       C.POINTER(CompressOpts), vp, errp]
     L.zpaqhip_gap_hist_blocks.argtypes = [vp, vp, vp, sz, vp, errp]
+    L.zpaqhip_gap_hist_blocks_device.argtypes = L.zpaqhip_gap_hist_blocks.argtypes[:-1] + [vp, errp]
     L.zpaqhip_enc_chain_plan.argtypes = [vp, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), errp]
     L.zpaqhip_dec_chain_plan.argtypes = [vp, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), errp]
     _lib = L

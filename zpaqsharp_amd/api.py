@@ -533,6 +533,106 @@ class Context:
             _raise(err, rc)
         return rc, got.value, boffs
 
+    def gap_hist_blocks_device(self, d_in: int, in_off: Sequence[int], hip_stream: int = 0) -> np.ndarray:
+        """zpaqhip_gap_hist_blocks_device: gap_hist_blocks of blocks in device memory (block i at d_in + in_off[i], read where
+        it is, any alignment): the same array, and all that crosses the bus."""
+        offs = np.ascontiguousarray(in_off, dtype=np.uint64)
+        n = max(0, offs.size - 1)
+        for i in range(n):
+            if int(offs[i + 1]) - int(offs[i]) > (1 << 31) - 1:
+                raise ValueError(f"block {i} has {int(offs[i + 1]) - int(offs[i])} bytes; the analysis takes at most 2^31 - 1")
+        hist = np.zeros((n, 4096), np.uint32)
+        if not n:
+            return hist
+        err = Err()
+        rc = self._L.zpaqhip_gap_hist_blocks_device(self._h, d_in or None, offs.ctypes.data, n, hist.ctypes.data, hip_stream or None,
+                                                    C.byref(err))
+        if rc:
+            _raise(err, rc)
+        return hist
+
+    def compress_mixed_device(self, methods: List[str], method_of: Sequence[int], d_in: int, in_off: Sequence[int], d_out: int,
+                              out_cap: int, *, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 0,
+                              batch_blocks: int = 0, slot_bytes: int = 0, bwt: bool = False, sa: bool = False, ht: bool = False,
+                              enc_waves: int = 0, hip_stream: int = 0, raise_on_error: bool = True):
+        """zpaqhip_compress_mixed_blocks_device: compress_method_device with a method per block: block i takes
+        methods[method_of[i]], and the stream in d_out has the blocks in input order, each the bytes compress_method writes
+        for it.  (rc, out_len, block_off) as compress_method_device.  Every method that a block takes is checked against
+        its own blocks (compress_method's refusals: ValueError before the device is touched); one that no block takes is
+        not."""
+        from . import method as mth
+        off = [int(x) for x in in_off]
+        n = max(0, len(off) - 1)
+        which = np.ascontiguousarray(method_of, dtype=np.int64).reshape(-1)
+        if which.size != n:
+            raise ValueError("method_of needs one entry per block")
+        if n and (which.min() < 0 or which.max() >= len(methods)):
+            raise ValueError("method_of names no entry of methods")
+        if filenames is not None and len(filenames) != n:
+            raise ValueError("filenames needs one entry per block")
+        lens = [b - a for a, b in zip(off, off[1:])]
+        table = (_lib.Method * max(1, len(methods)))()
+        keep = []                                          # the headers and programs the table points into
+        for g, m in enumerate(methods):
+            args = mth.parse_args(m)[1]
+            used = [lens[i] for i in range(n) if which[i] == g]
+            if used:
+                mth.check_blocks(args, used, bwt=bwt, sa=sa, ht=ht)
+            model, _ = mth.model_of(m)
+            hdr, pc = _as_u8(model.header), _as_u8(model.pcomp) if model.pcomp else None
+            keep += [hdr, pc]
+            table[g].args = (C.c_int32 * 9)(*args)
+            table[g].hdr, table[g].hdr_len = hdr.ctypes.data, hdr.size
+            table[g].pcomp, table[g].pcomp_len = (pc.ctypes.data, pc.size) if pc is not None else (None, 0)
+        which = np.ascontiguousarray(which, dtype=np.uint32)
+        coffs = np.ascontiguousarray(off, dtype=np.uint64)
+        names = None
+        if filenames is not None:
+            names = (C.c_char_p * max(1, n))(*[(f.encode() if isinstance(f, str) else f) for f in filenames])
+        o = CompressOpts()
+        o.struct_size = C.sizeof(CompressOpts)
+        o.flags = (1 if sha1 else 0) | (2 if tag else 0) | (4 if bwt else 0) | (8 if sa else 0) | (16 if ht else 0)
+        o.kernel, o.batch_blocks, o.slot_bytes, o.enc_waves = kernel, batch_blocks, slot_bytes, enc_waves
+        boffs = np.zeros(n + 1, np.uint64)
+        err, got = Err(), C.c_size_t(0)
+        rc = self._L.zpaqhip_compress_mixed_blocks_device(
+            self._h, table, len(methods), which.ctypes.data, d_in or None, coffs.ctypes.data, n, names, d_out or None, out_cap,
+            C.byref(got), boffs.ctypes.data, C.byref(o), hip_stream or None, C.byref(err))
+        if rc and rc != -20 and raise_on_error:
+            _raise(err, rc)
+        return rc, got.value, boffs
+
+    def compress_level_device(self, level: str, d_in: int, in_off: Sequence[int], d_out: int, out_cap: int, *, filenames=None,
+                              sha1: bool = True, tag: bool = True, kernel: int = 2, batch_blocks: int = 0, slot_bytes: int = 0,
+                              sa: bool = False, ht: bool = False, enc_waves: int = 0, hip_stream: int = 0,
+                              raise_on_error: bool = True):
+        """compress_level on device buffers, in the style of compress_method_device: the plaintext of block i at d_in +
+        in_off[i], the stream of compress_level(level, ...) to d_out, (rc, out_len, block_off) back.  At levels 5..9 the
+        histogram is taken where the blocks are (gap_hist_blocks_device); method.expand_level runs per block on the host,
+        from lengths and histograms alone; one compress_mixed_device call (bwt=True) then codes every block with the string
+        it got.  `level_methods` and `level_ms` as compress_level sets them."""
+        import time
+
+        from . import method as mth
+        if not level or not level[0].isdigit():
+            raise ValueError("a numeric method starts with its level, a digit")
+        off = [int(x) for x in in_off]
+        n = max(0, len(off) - 1)
+        if filenames is not None and len(filenames) != n:
+            raise ValueError("filenames needs one entry per block")
+        t0 = time.perf_counter()
+        hist = self.gap_hist_blocks_device(d_in, off, hip_stream) if int(level[0]) >= 5 else None
+        t1 = time.perf_counter()
+        expanded = [mth.expand_level(level, off[i + 1] - off[i], None if hist is None else hist[i]) for i in range(n)]
+        index = {}
+        which = [index.setdefault(m, len(index)) for m in expanded]
+        r = self.compress_mixed_device(list(index), which, d_in, off, d_out, out_cap, filenames=filenames, sha1=sha1, tag=tag,
+                                       kernel=kernel, batch_blocks=batch_blocks, slot_bytes=slot_bytes, bwt=True, sa=sa, ht=ht,
+                                       enc_waves=enc_waves, hip_stream=hip_stream, raise_on_error=raise_on_error)
+        self.level_methods = expanded
+        self.level_ms = {"analysis": (t1 - t0) * 1e3, "encode": (time.perf_counter() - t1) * 1e3}
+        return r
+
     def decompress(self, stream, out_cap: Optional[int] = None, **opt) -> np.ndarray:
         """LibZPAQ.decompress(Reader, Writer) (LibZPAQ.cs:65-79) on host buffers."""
         a = _as_u8(stream)

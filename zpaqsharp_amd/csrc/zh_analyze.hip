@@ -38,19 +38,19 @@ __global__ __launch_bounds__(64) void zh_gap_hist(ZhGapLaunch L) {
   const uint64_t s64 = first + (uint64_t)lane * ZH_GAP_SLICE;
   if (s64 < n) {
     const uint32_t s = (uint32_t)s64;
-    const uint32_t e = n - s < ZH_GAP_SLICE ? n : s + ZH_GAP_SLICE;
-    const uint32_t w0 = s >= ZH_GAP_NR ? s - ZH_GAP_NR : 0;
-    const uint32_t len = e - w0, from = s - w0;                      // the walk; its first counted position
-    // 16 aligned bytes per load; the bytes in front of w0 and behind e are skipped (the buffer is padded for the last load)
-    const uint64_t a0 = (off + w0) & ~15ull;
-    int64_t r0 = (int64_t)a0 - (int64_t)(off + w0);                  // walk position of the first byte of the load
-    const uint4 *src = (const uint4 *)(L.in + a0);
+    const ZhGapSlice c = zh_gap_slice(n, s);
+    const uint32_t len = c.e - c.w0, from = s - c.w0;                // the walk; its first counted position
+    // 16 bytes per load, aligned on the address itself (the input may be the caller's memory, of any alignment); the bytes
+    // in front of w0 and behind e are skipped, and no group without a byte of the walk is loaded (zh_analyze.h)
+    const ZhGapFirst f = zh_gap_first_load((uint64_t)(uintptr_t)(L.in + off), c.w0);
+    int64_t r0 = f.r0;                                               // walk position of the first byte of the load
+    const uint4 *src = (const uint4 *)(uintptr_t)f.addr;
     uint16_t *mine = pt + lane;
     uint32_t ones = 0;
     uint4 next = *src;
     while (r0 < (int64_t)len) {
       const uint4 cur = next;
-      if (r0 + 16 < (int64_t)len) next = *++src;
+      if (zh_gap_load_next(r0, len)) next = *++src;
       const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
 #pragma unroll
       for (int t = 0; t < 16; ++t) {

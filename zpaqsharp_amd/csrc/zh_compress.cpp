@@ -61,6 +61,26 @@ int zh::sha1_segments(const CtxView &v, const uint8_t *d_base, const std::vector
   return ZPAQHIP_OK;
 }
 
+hipError_t zh::DevSink::reserve(uint64_t need, uint64_t keep, hipStream_t stream) {
+  if (need <= cap) return hipSuccess;
+  const uint64_t grown = std::max(need, 2 * cap);
+  void *p = nullptr;
+  hipError_t e = hipMalloc(&p, grown + 16);                          // (+ 16: zh_frame.hip reads aligned 16-byte groups)
+  if (e != hipSuccess) return e;
+  if (keep) {
+    e = hipMemcpyAsync(p, mem.p, keep, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) {
+      (void)hipFree(p);
+      return e;
+    }
+  }
+  if (mem.p) (void)hipFree(mem.p);
+  mem.p = p;
+  cap = grown;
+  return hipSuccess;
+}
+
 int zh::finish_call(const CtxView &v, zpaqhip_stats st, uint64_t pos, size_t n_blocks, uint64_t *off, size_t out_cap, size_t *out_len,
                     zpaqhip_err *err) {
   if (off) off[n_blocks] = pos;
@@ -141,6 +161,7 @@ struct Call {
   zpaqhip_compress_opts o;
   bool dev_in = false, dev_out = false;   // the device form: `in` and `orig`, `out` are device memory; stage and frame differ
   hipStream_t user_stream = nullptr;
+  DevSink *sink = nullptr;                // the device form appends to it instead of writing to `out`
   uint32_t pack_launches = 0;             // zh_frame.hip's launches, of staging and of framing
   ZhModel M;
   std::vector<uint8_t> code, sel, dev_prefix;   // the selector prefix; what of it goes in front of the bytes on the device
@@ -490,7 +511,15 @@ int Call::frame(Batch &B) {
   }
   const uint64_t pos0 = pos;
   FrameTable T;
-  pos = build_frame_table(items, store ? &sel : nullptr, pos0, out_cap, T, block_off ? block_off + B.b0 : nullptr);
+  pos = build_frame_table(items, store ? &sel : nullptr, pos0, sink ? ~0ull : out_cap, T, block_off ? block_off + B.b0 : nullptr);
+  if (sink) {                             // room for the batch behind what the sink holds
+    if (sink->reserve(pos, pos0, v.stream) != hipSuccess) {
+      (void)hipGetLastError();
+      set_err(err, ZPAQHIP_E_DEVICE_MEM, (int)B.b0, -1, "no device memory for the scratch stream");
+      return ZPAQHIP_E_DEVICE_MEM;
+    }
+    out = sink->base();
+  }
   if (dev_out) {
     float ms = 0;
     const int rc = pack(T, B, out, &ms);
@@ -580,6 +609,8 @@ int zh::compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, cons
   if (dev) {
     c.dev_in = c.dev_out = true;
     c.user_stream = dev->stream;
+    c.sink = dev->sink;
+    if (c.sink) c.pos = c.sink->used;
   }
   int rc = build_model(hdr, hdr_len, c.M, c.code, err);
   if (rc) return rc;
@@ -605,5 +636,6 @@ int zh::compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, cons
   if (c.store) c.st.launches = pre->launches;
   c.st.launches += c.pack_launches;
   c.st.kernel_kind = c.store ? 0 : c.any_chain ? 3 : c.any_cm ? 2 : 1;
-  return finish_call(c.v, c.st, c.pos, n_blocks, block_off, out_cap, out_len, err);
+  if (c.sink) c.sink->used = c.pos;
+  return finish_call(c.v, c.st, c.pos, n_blocks, block_off, c.sink ? ~(size_t)0 : out_cap, out_len, err);
 }

@@ -91,8 +91,10 @@ class DevPre {
  public:
   // `in_dev`: `in` is device memory; run then copies the batch device to device (the kernels read past a block's end in
   // aligned groups, so they always work on the stage's own aligned copy)
-  DevPre(const Method &M, const uint8_t *in, const uint64_t *in_off, bool in_dev = false)
-      : M_(M), in_(in), in_off_(in_off), in_dev_(in_dev) {}
+  // `src_off` (with in_dev): block i's bytes are at in + src_off[i] instead of in + in_off[i], which then only gives the
+  // lengths: the blocks of one group of a mixed call, which lie anywhere in the caller's memory
+  DevPre(const Method &M, const uint8_t *in, const uint64_t *in_off, bool in_dev = false, const uint64_t *src_off = nullptr)
+      : M_(M), in_(in), in_off_(in_off), in_dev_(in_dev), src_off_(src_off) {}
   uint64_t n_of(size_t i) const { return in_off_[i + 1] - in_off_[i]; }
   uint64_t bound(size_t i) const;         // pre-processed bytes of block i at most
   uint64_t scratch(size_t i) const;       // device bytes the stage needs for block i
@@ -106,6 +108,7 @@ class DevPre {
   const uint8_t *in_;
   const uint64_t *in_off_;
   bool in_dev_;
+  const uint64_t *src_off_;
   DevMem plain_, e8_, len_, desc_, pref_;
   DevMem tab_, chain_, prev_;             // Greedy: ZhPreLaunch's table, chain and prev
   DevMem starts_, arena_;                 // slot routes: the slot starts of every launch; zh_pre.cpp's SortArena
@@ -115,7 +118,18 @@ class DevPre {
 // size comment and SHA-1 describe.  With `pre` (the method path) `in` is the plaintext and `orig` NULL; a header with n = 0
 // then gets the store layout instead of an encoder.  `dev`, when given, is the device form: `in`, `orig` and `out` are then
 // device pointers on the context's device, `pre` was made with in_dev, and the work runs on dev->stream when that is set.
-struct DeviceEnds { hipStream_t stream = nullptr; };
+// A stream in device memory that a call owns and several compress_impl runs append to (the scratch of a mixed call): it
+// grows to what the runs turn out to need, keeping what it holds.
+struct DevSink {
+  DevMem mem;
+  uint64_t cap = 0, used = 0;
+  uint8_t *base() const { return mem.as<uint8_t>(); }
+  // room for `need` bytes, keeping [0, keep): when it grows, to at least twice the old capacity
+  hipError_t reserve(uint64_t need, uint64_t keep, hipStream_t stream);
+};
+// With `sink`, `out` and `out_cap` are not used: the stream is appended to the sink at sink->used (block_off counts from
+// there) and nothing is ever too small.
+struct DeviceEnds { hipStream_t stream = nullptr; DevSink *sink = nullptr; };
 int compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
                   const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
                   const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,

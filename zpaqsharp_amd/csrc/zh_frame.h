@@ -77,4 +77,13 @@ struct FrameTable {
 uint64_t build_frame_table(const std::vector<FrameItem> &items, const std::vector<uint8_t> *sel, uint64_t pos, uint64_t out_cap,
                            FrameTable &T, uint64_t *block_pos);
 
+// The gather table of a mixed call (zpaqhip_compress_mixed_blocks_device): item i is block i of the call, framed already,
+// `len` bytes at `src_off` of the call's scratch stream, where the blocks lie group by group.  The stream has them in input
+// order from offset 0: block_pos[i] (optional) is the running sum, and every block that fits in whole under out_cap gets a
+// body-only entry (no head, no tail, src = ZH_FRAME_SRC_FIRST, as they are).  build_frame_table's rule, settled: the
+// offsets only grow, so a block behind one that did not fit starts past out_cap and does not fit either, not even an
+// empty one; the entries are a prefix of the blocks, item[e] == e.  Returns the bytes the whole stream needs.
+struct GatherItem { uint64_t src_off, len; };
+uint64_t build_gather_table(const std::vector<GatherItem> &items, uint64_t out_cap, FrameTable &T, uint64_t *block_pos);
+
 }  // namespace zh

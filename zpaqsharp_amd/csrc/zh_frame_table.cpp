@@ -82,3 +82,25 @@ uint64_t zh::build_frame_table(const std::vector<FrameItem> &items, const std::v
   }
   return pos;
 }
+
+uint64_t zh::build_gather_table(const std::vector<GatherItem> &items, uint64_t out_cap, FrameTable &T, uint64_t *block_pos) {
+  T = FrameTable();
+  uint64_t pos = 0;
+  for (size_t i = 0; i < items.size(); ++i) {
+    const GatherItem &it = items[i];
+    if (block_pos) block_pos[i] = pos;
+    if (it.len <= out_cap && pos <= out_cap - it.len) {
+      ZhFrameEntry e;
+      memset(&e, 0, sizeof e);
+      e.dst_off = pos;
+      e.src = ZH_FRAME_SRC_FIRST;
+      e.src_off = it.src_off;
+      e.body_len = it.len;
+      T.entry.push_back(e);
+      T.item.push_back(i);
+      T.pieces = (uint32_t)std::max<uint64_t>(T.pieces, (it.len + ZH_FRAME_PIECE - 1) / ZH_FRAME_PIECE);
+    }
+    pos += it.len;
+  }
+  return pos;
+}

@@ -292,7 +292,14 @@ int zh::DevPre::run(const CtxView &v, size_t b0, size_t b1, uint8_t *d_out, cons
   HIPCHK(plain_.alloc(plain));
   HIPCHK(desc_.alloc(nb * sizeof(ZhPreBlock)));
   HIPCHK(len_.alloc(nb * 8));
-  if (plain && in_dev_) HIPCHK(hipMemcpyAsync(plain_.p, in_ + base, plain, hipMemcpyDeviceToDevice, v.stream));
+  if (plain && in_dev_ && src_off_) {     // blocks from anywhere: one copy per run of blocks that lie back to back at the caller's
+    for (size_t j = 0, k; j < nb; j = k) {
+      for (k = j + 1; k < nb && src_off_[b0 + k] == src_off_[b0 + k - 1] + desc[k - 1].n;) ++k;
+      const uint64_t bytes = desc[k - 1].in_off + desc[k - 1].n - desc[j].in_off;
+      if (bytes)
+        HIPCHK(hipMemcpyAsync(plain_.as<uint8_t>() + desc[j].in_off, in_ + src_off_[b0 + j], bytes, hipMemcpyDeviceToDevice, v.stream));
+    }
+  } else if (plain && in_dev_) HIPCHK(hipMemcpyAsync(plain_.p, in_ + base, plain, hipMemcpyDeviceToDevice, v.stream));
   else if (plain) HIPCHK(hipMemcpy(plain_.p, in_ + base, plain, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(desc_.p, desc.data(), nb * sizeof(ZhPreBlock), hipMemcpyHostToDevice));
   if (np) {
@@ -445,10 +452,13 @@ int preprocess_entry(zpaqhip_ctx *ctx, const int32_t *args, uint32_t flags, Rout
 }
 
 // the repetition-gap histograms of compressBlock's levels 5..9 (LibZPAQ.cs:242-255), zh_analyze.hip
-int gap_hist_impl(zpaqhip_ctx *ctx, const uint8_t *in, const uint64_t *in_off, size_t n_blocks, uint32_t *hist, zpaqhip_err *err) {
+// (`dev`: `in` is device memory, read where it is on dev->stream)
+int gap_hist_impl(zpaqhip_ctx *ctx, const uint8_t *in, const uint64_t *in_off, size_t n_blocks, uint32_t *hist, zpaqhip_err *err,
+                  const DeviceEnds *dev = nullptr) {
   // 32-bit positions and counters
   if (const int rc = check_offsets(in, in_off, n_blocks, (1ull << 31) - 1, "block longer than 2^31 - 1 bytes", err)) return rc;
   CtxView v = ctx_view(ctx);
+  if (dev && dev->stream) v.stream = dev->stream;
   HIPCHK(hipSetDevice(v.device));
   uint64_t budget = 0;
   HIPCHK(device_budget(v.mem_share, 0, &budget));
@@ -458,22 +468,22 @@ int gap_hist_impl(zpaqhip_ctx *ctx, const uint8_t *in, const uint64_t *in_off, s
   auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
   DevMem d_in, d_off, d_hist;
   for (size_t b0 = 0; b0 < n_blocks;) {
-    const size_t b1 = batch_end(b0, n_blocks, 0, budget, [&](size_t i) { return in_off[i + 1] - in_off[i] + 4 * ZH_GAP_NR + 8; });
+    const size_t b1 = batch_end(b0, n_blocks, 0, budget, [&](size_t i) { return (dev ? 0 : in_off[i + 1] - in_off[i]) + 4 * ZH_GAP_NR + 8; });
     const size_t nb = b1 - b0;
     const uint64_t base = in_off[b0], plain = in_off[b1] - base;
     uint64_t max_n = 0;
     for (size_t i = b0; i < b1; ++i) max_n = std::max(max_n, in_off[i + 1] - in_off[i]);
-    HIPCHK(d_in.alloc(plain + 16));       // the kernel loads aligned 16-byte groups: the last may reach past the data
+    if (!dev) HIPCHK(d_in.alloc(plain + 16));       // the kernel loads aligned 16-byte groups: the last may reach past the data
     HIPCHK(d_off.alloc((nb + 1) * 8));
     HIPCHK(d_hist.alloc(nb * 4 * ZH_GAP_NR));
     auto t = clk::now();
-    if (plain) HIPCHK(hipMemcpy(d_in.p, in + base, plain, hipMemcpyHostToDevice));
+    if (plain && !dev) HIPCHK(hipMemcpy(d_in.p, in + base, plain, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_off.p, in_off + b0, (nb + 1) * 8, hipMemcpyHostToDevice));
-    st.h2d_ms += ms_since(t);
+    if (!dev) st.h2d_ms += ms_since(t);   // (the device form uploads the offsets only)
     ZhGapLaunch L;
-    L.in = d_in.as<uint8_t>();
+    L.in = dev ? in : d_in.as<uint8_t>();
     L.in_off = d_off.as<uint64_t>();
-    L.base = base;
+    L.base = dev ? 0 : base;
     L.hist = d_hist.as<uint32_t>();
     HIPCHK(hipMemsetAsync(d_hist.p, 0, nb * 4 * ZH_GAP_NR, v.stream));
     HIPCHK(hipEventRecord(v.ev0, v.stream));
@@ -502,6 +512,13 @@ extern "C" int zpaqhip_gap_hist_blocks(zpaqhip_ctx *ctx, const uint8_t *in, cons
                                        zpaqhip_err *err) {
   if (!ctx || (n_blocks && (!in_off || !hist))) return refuse(err);
   return gap_hist_impl(ctx, in, in_off, n_blocks, hist, err);
+}
+
+extern "C" int zpaqhip_gap_hist_blocks_device(zpaqhip_ctx *ctx, const void *d_in, const uint64_t *in_off, size_t n_blocks,
+                                              uint32_t *hist, void *hip_stream, zpaqhip_err *err) {
+  if (!ctx || (n_blocks && (!in_off || !hist))) return refuse(err);
+  const DeviceEnds dev{(hipStream_t)hip_stream};
+  return gap_hist_impl(ctx, (const uint8_t *)d_in, in_off, n_blocks, hist, err, &dev);
 }
 
 extern "C" int zpaqhip_preprocess_blocks(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *in, const uint64_t *in_off,
@@ -566,4 +583,129 @@ extern "C" int zpaqhip_compress_method_blocks_device(zpaqhip_ctx *ctx, const int
   const DeviceEnds dev{(hipStream_t)hip_stream};
   return compress_method_impl(ctx, args, hdr, hdr_len, pcomp, pcomp_len, (const uint8_t *)d_in, in_off, n_blocks, filenames,
                               (uint8_t *)d_out, out_cap, out_len, block_off, opts, err, &dev);
+}
+
+// ---- a method per block ---------------------------------------------------------------------------------------------------
+// The blocks of every method that is used run as one group through compress_impl's device form, which appends the group's
+// stream to a sink the call owns; one launch of the packing kernel over build_gather_table's entries then puts the blocks
+// into d_out in input order.
+extern "C" hipError_t zh_launch_frame_pack(const ZhFrameLaunch *L, hipStream_t stream, uint32_t *launches);
+
+namespace {
+
+int refuse_block(zpaqhip_err *err, size_t block, const char *why) {
+  set_err(err, ZPAQHIP_E_ARG, (int)block, -1, why);
+  return ZPAQHIP_E_ARG;
+}
+
+// the gather: uploads the table and packs d_out from the scratch stream; its time and its launches
+int gather(const CtxView &v, hipStream_t stream, const FrameTable &T, const uint8_t *scratch, uint8_t *d_out, float *ms,
+           uint32_t *launches, zpaqhip_err *err) {
+  if (T.entry.empty()) return ZPAQHIP_OK;
+  const size_t tb = T.entry.size() * sizeof(ZhFrameEntry);
+  DevMem d_tab;
+  HIPCHK(d_tab.alloc(tb));
+  HIPCHK(hipMemcpy(d_tab.p, T.entry.data(), tb, hipMemcpyHostToDevice));
+  ZhFrameLaunch L;
+  memset(&L, 0, sizeof L);
+  L.table = d_tab.as<ZhFrameEntry>();
+  L.blob = d_tab.as<uint8_t>();             // no entry has a head or a tail: nothing of it is read
+  L.src[ZH_FRAME_SRC_FIRST] = scratch;
+  L.out = d_out;
+  L.n = (uint32_t)T.entry.size();
+  L.pieces = T.pieces;
+  HIPCHK(hipEventRecord(v.ev0, stream));
+  HIPCHK(zh_launch_frame_pack(&L, stream, launches));
+  HIPCHK(hipEventRecord(v.ev1, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  HIPCHK(hipEventElapsedTime(ms, v.ev0, v.ev1));
+  return ZPAQHIP_OK;
+}
+
+}  // namespace
+
+extern "C" int zpaqhip_compress_mixed_blocks_device(zpaqhip_ctx *ctx, const zpaqhip_method *methods, size_t n_methods,
+                                                    const uint32_t *method_of, const void *d_in, const uint64_t *in_off,
+                                                    size_t n_blocks, const char *const *filenames, void *d_out, size_t out_cap,
+                                                    size_t *out_len, uint64_t *block_off, const zpaqhip_compress_opts *opts,
+                                                    void *hip_stream, zpaqhip_err *err) {
+  if (!ctx || !out_len || (!d_out && out_cap) || (n_blocks && (!in_off || !method_of)) || (n_methods && !methods)) return refuse(err);
+  *out_len = 0;
+  if (n_blocks && !n_methods) return refuse(err, "blocks, but no method");
+  if (n_blocks > 0x7FFFFFFFull) return refuse(err, "more blocks than a call takes (2^31 - 1)");
+  for (size_t g = 0; g < n_methods; ++g)
+    if (methods[g].reserved) return refuse(err, "zpaqhip_method.reserved must be 0");
+
+  // every argument check, in block order, before anything touches the device
+  const uint32_t flags = resolve_compress_opts(opts).flags;
+  std::vector<Method> M(n_methods);
+  std::vector<std::vector<size_t>> ids(n_methods);          // the blocks of each method, in input order
+  for (size_t i = 0; i < n_blocks; ++i) {
+    if (in_off[i + 1] < in_off[i] || (!d_in && in_off[i + 1] > in_off[i])) return refuse_block(err, i, "block offsets must not decrease");
+    const size_t g = method_of[i];
+    if (g >= n_methods) return refuse_block(err, i, "method_of names no entry of the method list");
+    const zpaqhip_method &m = methods[g];
+    if (ids[g].empty()) {                                    // the method's first block: the method itself
+      int rc = ZPAQHIP_OK;
+      if (!m.hdr || (m.pcomp_len && !m.pcomp) || m.pcomp_len > 65535) rc = refuse(err);
+      else rc = parse_method(m.args, flags, M[g], err);
+      if (rc) {
+        if (err) err->block = (int32_t)i;
+        return rc;
+      }
+    }
+    if (const int rc = check_blocks(M[g], (const uint8_t *)d_in, in_off + i, 1, err)) {
+      if (err) err->block = (int32_t)i;
+      return rc;
+    }
+    ids[g].push_back(i);
+  }
+
+  CtxView v = ctx_view(ctx);
+  const hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : v.stream;
+  DevSink sink;
+  std::vector<GatherItem> items(n_blocks);
+  zpaqhip_stats st{};
+  for (size_t g = 0; g < n_methods; ++g) {
+    const size_t ng = ids[g].size();
+    if (!ng) continue;
+    std::vector<uint64_t> len_off(ng + 1, 0), src_off(ng), at(ng + 1);
+    std::vector<const char *> names(ng, nullptr);
+    for (size_t j = 0; j < ng; ++j) {
+      const size_t i = ids[g][j];
+      src_off[j] = in_off[i];
+      len_off[j + 1] = len_off[j] + (in_off[i + 1] - in_off[i]);
+      if (filenames) names[j] = filenames[i];
+    }
+    const zpaqhip_method &m = methods[g];
+    DevPre P(M[g], (const uint8_t *)d_in, len_off.data(), true, src_off.data());
+    const DeviceEnds dev{stream, &sink};
+    size_t end = 0;
+    const int rc = compress_impl(ctx, m.hdr, m.hdr_len, m.pcomp, m.pcomp_len, (const uint8_t *)d_in, len_off.data(), ng, nullptr,
+                                 nullptr, filenames ? names.data() : nullptr, nullptr, 0, &end, at.data(), opts, &P, err, &dev);
+    if (rc) {
+      if (err && err->block >= 0 && (size_t)err->block < ng) err->block = (int32_t)ids[g][err->block];
+      return rc;
+    }
+    for (size_t j = 0; j < ng; ++j) items[ids[g][j]] = {at[j], at[j + 1] - at[j]};
+    const zpaqhip_stats &s = *v.stats;
+    st.kernel_ms += s.kernel_ms;
+    st.init_ms += s.init_ms;
+    st.launches += s.launches;
+    st.in_bytes += s.in_bytes;
+    st.kernel_kind = std::max(st.kernel_kind, s.kernel_kind);
+    st.concurrent = std::max(st.concurrent, s.concurrent);
+  }
+
+  FrameTable T;
+  std::vector<uint64_t> pos(n_blocks + 1);
+  const uint64_t need = build_gather_table(items, out_cap, T, pos.data());
+  if (block_off) std::copy(pos.begin(), pos.begin() + n_blocks, block_off);
+  float ms = 0;
+  if (const int rc = gather(v, stream, T, sink.base(), (uint8_t *)d_out, &ms, &st.launches, err)) return rc;
+  st.kernel_ms += ms;
+  st.blocks = n_blocks;
+  st.model_bytes = sink.cap;
+  st.e8_wave_segs = (uint32_t)(ms * 1000.0f + 0.5f);
+  return finish_call(v, st, need, n_blocks, block_off, out_cap, out_len, err);
 }

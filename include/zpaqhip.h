@@ -59,7 +59,8 @@ typedef enum zpaqhip_status {
   ZPAQHIP_E_HIP = -24,           /* HIP runtime error (message in zpaqhip_err) */
   ZPAQHIP_E_ARG = -25,           /* bad argument / table too small */
   ZPAQHIP_E_BUDGET = -26,        /* ZPAQL instruction budget exhausted (runaway program guard) */
-  ZPAQHIP_E_CALLBACK = -27       /* read/write callback failed */
+  ZPAQHIP_E_CALLBACK = -27,      /* read/write callback failed */
+  ZPAQHIP_E_VERIFY = -28         /* "Pre/post-processor test failed"  LibZPAQ.cs:320 */
 } zpaqhip_status;
 
 typedef struct zpaqhip_err {
@@ -352,7 +353,10 @@ typedef struct zpaqhip_compress_opts {
                                zpaqhip_lzsa_blocks); no effect on any other method; bit4 (zpaqhip_compress_method_blocks only): a
                                level 1 / 2 method with args[5] - args[0] < 21 is parsed by the reference's hash-table search
                                (see zpaqhip_lzht_blocks); no effect on any other method; bits 3 and 4 may be given together;
-                               NULL opts = 3 */
+                               bit5 (value 32, every compressing call): verify (Compressor.setVerify, Compressor.cs:118-121): each
+                               batch's coded sequences run through the block's own post-processor on the device before the
+                               encoders see them, and a block that does not come back as its plaintext fails the call (see
+                               zpaqhip_verify_blocks); NULL opts = 3 */
   uint32_t kernel;          /* 0 auto: single-CM models of the `a<<= K  *d=a  halt` shape (K >= 9) on the window-parallel
                                encoder, the rest on the generic one; 1 every block on the generic encoder (cross-check);
                                2 as 0, but models that fit the lane-per-component kernel (ICM / ISSE / MATCH / MIX chains of at
@@ -524,6 +528,48 @@ int zpaqhip_compress_mixed_blocks_device(zpaqhip_ctx *ctx, const zpaqhip_method 
                                          const char *const *filenames, void *d_out, size_t out_cap, size_t *out_len,
                                          uint64_t *block_off, const zpaqhip_compress_opts *opts, void *hip_stream,
                                          zpaqhip_err *err);
+
+/* ---- the pre/post-processor test (Compressor.setVerify, Compressor.cs:118-121; endSegmentChecksum, :251-281) --------------
+ * zpaqhip_verify_blocks is endSegmentChecksum(&size) for a set of blocks: block i's pre-processed bytes in[in_off[i],
+ * in_off[i+1]) are post-processed on the GPU exactly as PostProcessor.write would after the decoder (the selector for
+ * `pcomp`, the program fed byte by byte, run(-1) at the end of the segment, with H and M of the sizes `hdr` gives: only ph
+ * and pm of the header matter), and results[i] tells how many bytes came out, their SHA-1 and, with `orig`, the offset of
+ * the first byte that differs from orig[orig_off[i], orig_off[i+1]) (the shorter length when one is a prefix of the other).
+ * status is ZPAQHIP_OK, ZPAQHIP_E_VERIFY when the plaintext is given and differs, or the post-processor's own error
+ * (ZPAQHIP_E_ZPAQL, ZPAQHIP_E_PP_*, ZPAQHIP_E_BUDGET); out_len and sha1 then describe what it wrote before it stopped.
+ * `pcomp` NULL / 0 = PASS: size and SHA-1 of the bytes themselves.  The reference's programs (lazy2, lzpre, bwtrle; the
+ * first two with E8E9 too) run on the wave-wide post-processors of the decoder (zh_store.hip), one workgroup per block;
+ * every other program on its translation or on the ZPAQL VM, one lane per block.  The post-processed bytes stay in device
+ * memory that the call owns; only the records cross the bus (and, in the host form, the arguments).  The call returns
+ * ZPAQHIP_OK when it ran, whatever the records say.  zpaqhip_last_stats: kernel_ms = the pass (post-processors, SHA-1,
+ * compare), launches = its launches, blocks, in_bytes = pre-processed bytes, out_bytes = bytes post-processed.
+ *
+ * The compressing calls run the same pass with bit5 of zpaqhip_compress_opts.flags, in the batch loop between pre-processing
+ * and the encoders (zpaqhip_compress_blocks[_device]: over `in` as given, against `orig`, or against `in` itself without
+ * one).  A failing block ends the call with its record's status and err->block = the lowest failing index of that batch
+ * (zpaqhip_compress_mixed_blocks_device: of the first group that fails, in the order the call takes the groups), *out_len = 0
+ * and the contents of out unspecified: a verified call delivers all blocks or none.  With every block passing the stream
+ * is byte for byte the one without the bit; kernel_ms and launches also count the pass. */
+typedef struct zpaqhip_verify_result {
+  int32_t status;        /* ZPAQHIP_OK, ZPAQHIP_E_VERIFY, or the post-processor's own error */
+  uint32_t reserved;
+  uint64_t out_len;      /* bytes the post-processor wrote */
+  uint64_t first_diff;   /* UINT64_MAX: equal, or no plaintext given */
+  uint8_t sha1[20];      /* of those bytes */
+  uint32_t reserved2;
+} zpaqhip_verify_result; /* 48 bytes */
+
+int zpaqhip_verify_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
+                          const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
+                          const uint8_t *orig, const uint64_t *orig_off, zpaqhip_verify_result *results, zpaqhip_err *err);
+
+/* The same with `d_in` and `d_orig` (optional) in device memory on the context's device; the offsets and the records stay
+ * host memory.  No alignment is asked of either; both are read where they lie.  `hip_stream` as for
+ * zpaqhip_compress_blocks_device. */
+int zpaqhip_verify_blocks_device(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
+                                 const void *d_in, const uint64_t *in_off, size_t n_blocks,
+                                 const void *d_orig, const uint64_t *orig_off, zpaqhip_verify_result *results,
+                                 void *hip_stream, zpaqhip_err *err);
 
 /* ---- the data analysis of LibZPAQ.compressBlock's numeric levels 5..9 (LibZPAQ.cs:242-255) -------------------------------
  * The histogram of repetition gaps of each block p = in[in_off[i], in_off[i+1]): with pt[256] and r[4096] all zero,

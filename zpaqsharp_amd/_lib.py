@@ -57,6 +57,12 @@ class CompressOpts(C.Structure):
                 ("batch_blocks", C.c_uint64), ("slot_bytes", C.c_uint64), ("reserved", C.c_uint64 * 2)]
 
 
+class VerifyResult(C.Structure):
+    """zpaqhip_verify_result: what the post-processor made of one block's pre-processed bytes."""
+    _fields_ = [("status", C.c_int32), ("reserved", C.c_uint32), ("out_len", C.c_uint64), ("first_diff", C.c_uint64),
+                ("sha1", C.c_uint8 * 20), ("reserved2", C.c_uint32)]
+
+
 class Method(C.Structure):
     """zpaqhip_method: one entry of the method list of zpaqhip_compress_mixed_blocks_device."""
     _fields_ = [("args", C.c_int32 * 9), ("reserved", C.c_uint32), ("hdr", C.c_void_p), ("hdr_len", C.c_size_t),
@@ -75,7 +81,7 @@ SYMBOLS = ("zpaqhip_version", "zpaqhip_strerror", "zpaqhip_device_count", "zpaqh
            "zpaqhip_gap_hist_blocks", "zpaqhip_lzsa_blocks", "zpaqhip_lzht_blocks", "zpaqhip_enc_chain_plan",
            "zpaqhip_dec_chain_plan", "zpaqhip_compress_blocks_device", "zpaqhip_compress_method_blocks_device",
            "zpaqhip_scan_device", "zpaqhip_decompress_device", "zpaqhip_compress_mixed_blocks_device",
-           "zpaqhip_gap_hist_blocks_device")
+           "zpaqhip_gap_hist_blocks_device", "zpaqhip_verify_blocks", "zpaqhip_verify_blocks_device")
 
 _lib = None
 
@@ -138,6 +144,8 @@ def load():
                                                        C.POINTER(CompressOpts), vp, errp]
     L.zpaqhip_gap_hist_blocks.argtypes = [vp, vp, vp, sz, vp, errp]
     L.zpaqhip_gap_hist_blocks_device.argtypes = L.zpaqhip_gap_hist_blocks.argtypes[:-1] + [vp, errp]
+    L.zpaqhip_verify_blocks.argtypes = [vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, C.POINTER(VerifyResult), errp]
+    L.zpaqhip_verify_blocks_device.argtypes = L.zpaqhip_verify_blocks.argtypes[:-1] + [vp, errp]
     L.zpaqhip_enc_chain_plan.argtypes = [vp, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), errp]
     L.zpaqhip_dec_chain_plan.argtypes = [vp, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), errp]
     _lib = L

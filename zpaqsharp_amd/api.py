@@ -12,7 +12,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import Block, CompressOpts, Err, Opts, SegResult, Segment, Stats, UINT64_MAX
+from ._lib import Block, CompressOpts, Err, Opts, SegResult, Segment, Stats, UINT64_MAX, VerifyResult
 
 
 class ZpaqError(RuntimeError):
@@ -178,6 +178,12 @@ KERNEL_STORE_E8 = 10
 KERNEL_MODEL_E8 = 11
 
 
+def compress_flags(sha1: bool = True, tag: bool = True, bwt: bool = False, sa: bool = False, ht: bool = False,
+                   verify: bool = False) -> int:
+    """zpaqhip_compress_opts.flags from the keywords of the compressing calls (bit 5, value 32: verify)."""
+    return (1 if sha1 else 0) | (2 if tag else 0) | (4 if bwt else 0) | (8 if sa else 0) | (16 if ht else 0) | (32 if verify else 0)
+
+
 def make_opts(verify_sha1: bool = False, max_concurrent: int = 0, kernel: int = 0, zpaql_budget: int = 0,
               batch_blocks: int = 0, queue_blocks: int = 0, dec_waves: int = 0) -> Opts:
     """zpaqhip_opts from keywords (include/zpaqhip.h describes each): every decode entry point below takes them as **opt.
@@ -245,7 +251,7 @@ class Context:
         return sq, st, dt, dt2k, ns
 
     def compress_blocks(self, model, blocks, *, pre=None, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 0,
-                        batch_blocks: int = 0, slot_bytes: int = 0, enc_waves: int = 0) -> bytes:
+                        batch_blocks: int = 0, slot_bytes: int = 0, enc_waves: int = 0, verify: bool = False) -> bytes:
         """Compressor.startBlock .. endBlock for each block (LibZPAQ.cs:296-323 framing, one segment per block), coded on
         the GPU: the same bytes the CPU stream writer (synth.compress_block) produces.  `model` is a models name or a
         zpaql.Model.  A `+e8e9` model codes the forward E8E9 transform of each block; a `+lz77` model needs `pre`, the
@@ -255,7 +261,10 @@ class Context:
         components and 4 mixers: min, mid, max, the method models) on the lane-per-component encoder
         (stats().kernel_kind == 3).  `enc_waves`: that encoder's waves (blocks in flight) per compute unit: 0 as many as
         the model's LDS plan (enc_chain_plan), the blocks and device memory allow, up to four; 1 one; 2 to 4 a cap; more is
-        an error.  The bytes never depend on it; stats().concurrent tells the blocks in flight of the largest launch."""
+        an error.  The bytes never depend on it; stats().concurrent tells the blocks in flight of the largest launch.
+        `verify` (every compressing call has it): Compressor.setVerify, the coded sequence of each block runs through the
+        block's own post-processor on the GPU before it is coded (verify_blocks), and a block that does not come back as
+        its plaintext raises ZpaqError(-28, block) or the post-processor's own error; the bytes do not depend on it."""
         from . import e8e9, models
         m = models.get(model) if isinstance(model, str) else model
         plain = [_as_u8(b) for b in blocks]
@@ -268,7 +277,7 @@ class Context:
             coded, orig = [e8e9.forward(b) for b in plain], plain
         elif m.pcomp_cmd.startswith("lz77"):
             raise ValueError("a +lz77 model needs the pre-processed blocks (pre=)")
-        flags = (1 if sha1 else 0) | (2 if tag else 0)
+        flags = compress_flags(sha1, tag, verify=verify)
         return self._compress(m.header, m.pcomp or b"", coded, orig, filenames, flags, kernel, batch_blocks, slot_bytes,
                               enc_waves=enc_waves)[0]
 
@@ -341,7 +350,7 @@ class Context:
 
     def compress_method(self, method: str, blocks, *, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 0,
                         batch_blocks: int = 0, slot_bytes: int = 0, bwt: bool = False, sa: bool = False, ht: bool = False,
-                        enc_waves: int = 0) -> bytes:
+                        enc_waves: int = 0, verify: bool = False) -> bytes:
         """LibZPAQ.compressBlock(method) for each block (LibZPAQ.cs:296-323, one segment per block) on the GPU: the bytes
         tools.methods.compress_block writes.  Levels 0, 1 and 2 with or without E8E9, and with `bwt=True` level 3; the
         model of an n >= 1 method codes the pre-processed bytes on the encoders of compress_blocks (kernel, batch_blocks,
@@ -352,10 +361,11 @@ class Context:
         parse (lzsa_blocks; the bytes of tools.methods.compress_block(..., sa=True)); no effect on any other method.
         `ht=True`: one with args[5] - args[0] < 21 gets the reference's hash-table parse (lzht_blocks, with its refusals;
         the bytes of tools.methods.compress_block(..., ht=True)); no effect on any other method.  Both may be given."""
-        return self._compress_method(method, blocks, filenames, sha1, tag, kernel, batch_blocks, slot_bytes, bwt, sa, ht, enc_waves)[0]
+        return self._compress_method(method, blocks, filenames, sha1, tag, kernel, batch_blocks, slot_bytes, bwt, sa, ht, enc_waves,
+                                     verify)[0]
 
     def _compress_method(self, method: str, blocks, filenames, sha1: bool, tag: bool, kernel: int, batch_blocks: int,
-                         slot_bytes: int, bwt: bool, sa: bool = False, ht: bool = False, enc_waves: int = 0):
+                         slot_bytes: int, bwt: bool, sa: bool = False, ht: bool = False, enc_waves: int = 0, verify: bool = False):
         """compress_method: (stream bytes, block offsets)."""
         from . import method as mth
         args = mth.parse_args(method)[1]
@@ -364,7 +374,7 @@ class Context:
         model, _ = mth.model_of(method)
         cap = sum(mth.pre_bound(args, p.size) for p in plain) + len(plain) * (len(model.header) + 2 * len(model.pcomp) + 4096) + 4096
         return self._compress(model.header, model.pcomp or b"", plain, None, filenames,
-                              (1 if sha1 else 0) | (2 if tag else 0) | (4 if bwt else 0) | (8 if sa else 0) | (16 if ht else 0), kernel, batch_blocks, slot_bytes, out_cap=cap,
+                              compress_flags(sha1, tag, bwt, sa, ht, verify), kernel, batch_blocks, slot_bytes, out_cap=cap,
                               args=args, enc_waves=enc_waves)[:2]
 
     def gap_hist_blocks(self, blocks) -> np.ndarray:
@@ -387,7 +397,8 @@ class Context:
         return hist
 
     def compress_level(self, level: str, blocks, *, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 2,
-                       batch_blocks: int = 0, slot_bytes: int = 0, sa: bool = False, ht: bool = False, enc_waves: int = 0) -> bytes:
+                       batch_blocks: int = 0, slot_bytes: int = 0, sa: bool = False, ht: bool = False, enc_waves: int = 0,
+                       verify: bool = False) -> bytes:
         """LibZPAQ.compressBlock with a numeric method "LB,R,t" (LibZPAQ.cs:124-323) for each block: `level` is expanded per
         block by method.expand_level (the block's length gives the x<N> argument; at levels 5..9 its gap histogram, taken by
         gap_hist_blocks, gives the periodic models), the blocks are grouped by the string they got, each group goes through
@@ -414,8 +425,13 @@ class Context:
             groups.setdefault(m, []).append(i)
         parts = [b""] * len(plain)
         for m, ids in groups.items():
-            out, off = self._compress_method(m, [plain[i] for i in ids], None if filenames is None else [filenames[i] for i in ids],
-                                             sha1, tag, kernel, batch_blocks, slot_bytes, True, sa, ht, enc_waves)
+            try:
+                out, off = self._compress_method(m, [plain[i] for i in ids], None if filenames is None else [filenames[i] for i in ids],
+                                                 sha1, tag, kernel, batch_blocks, slot_bytes, True, sa, ht, enc_waves, verify)
+            except ZpaqError as e:                         # (the block's index in the call, not in its group)
+                if 0 <= e.block < len(ids):
+                    raise ZpaqError(e.code, ids[e.block], e.segment, e.msg) from None
+                raise
             for j, i in enumerate(ids):
                 parts[i] = out[int(off[j]):int(off[j + 1])]
         self.level_methods = expanded
@@ -469,7 +485,7 @@ class Context:
     def compress_blocks_device(self, model, d_in: int, in_off: Sequence[int], d_out: int, out_cap: int, *, d_orig: int = 0,
                                orig_off: Optional[Sequence[int]] = None, filenames=None, sha1: bool = True, tag: bool = True,
                                kernel: int = 0, batch_blocks: int = 0, slot_bytes: int = 0, enc_waves: int = 0,
-                               hip_stream: int = 0, raise_on_error: bool = True):
+                               hip_stream: int = 0, raise_on_error: bool = True, verify: bool = False):
         """zpaqhip_compress_blocks_device: compress_blocks on device buffers (pointers as ints; the caller holds the memory,
         e.g. torch tensors' .data_ptr()).  Block i codes the bytes d_in + in_off[i] .. d_in + in_off[i + 1] as they are (no
         E8E9 here: a `+e8e9` or `+lz77` model takes its pre-processed bytes in d_in and, for the size comment and SHA-1, the
@@ -478,14 +494,14 @@ class Context:
         bytes needed and the blocks that fit in whole written; any other status raises unless raise_on_error is False."""
         from . import models
         m = models.get(model) if isinstance(model, str) else model
-        flags = (1 if sha1 else 0) | (2 if tag else 0)
+        flags = compress_flags(sha1, tag, verify=verify)
         return self._compress_device(m.header, m.pcomp or b"", None, d_in, in_off, d_orig, orig_off, filenames, flags, kernel,
                                      batch_blocks, slot_bytes, enc_waves, d_out, out_cap, hip_stream, raise_on_error)
 
     def compress_method_device(self, method: str, d_in: int, in_off: Sequence[int], d_out: int, out_cap: int, *, filenames=None,
                                sha1: bool = True, tag: bool = True, kernel: int = 0, batch_blocks: int = 0, slot_bytes: int = 0,
                                bwt: bool = False, sa: bool = False, ht: bool = False, enc_waves: int = 0, hip_stream: int = 0,
-                               raise_on_error: bool = True):
+                               raise_on_error: bool = True, verify: bool = False):
         """zpaqhip_compress_method_blocks_device: compress_method on device buffers, in the style of compress_blocks_device:
         the plaintext of block i at d_in + in_off[i], the stream to d_out, (rc, out_len, block_off) back.  The method's
         refusals (ValueError before the device is touched) and the options are compress_method's."""
@@ -494,7 +510,7 @@ class Context:
         off = [int(x) for x in in_off]
         mth.check_blocks(args, [b - a for a, b in zip(off, off[1:])], bwt=bwt, sa=sa, ht=ht)
         model, _ = mth.model_of(method)
-        flags = (1 if sha1 else 0) | (2 if tag else 0) | (4 if bwt else 0) | (8 if sa else 0) | (16 if ht else 0)
+        flags = compress_flags(sha1, tag, bwt, sa, ht, verify)
         return self._compress_device(model.header, model.pcomp or b"", args, d_in, off, 0, None, filenames, flags, kernel,
                                      batch_blocks, slot_bytes, enc_waves, d_out, out_cap, hip_stream, raise_on_error)
 
@@ -533,6 +549,74 @@ class Context:
             _raise(err, rc)
         return rc, got.value, boffs
 
+    @staticmethod
+    def _verify_model(model_or_method):
+        """(header, pcomp) of a models name, a zpaql.Model or a method string (`x...` / a numeric level is not one)."""
+        from . import method as mth, models
+        if isinstance(model_or_method, str):
+            if model_or_method[:1] == "x":
+                m = mth.model_of(model_or_method)[0]
+            else:
+                m = models.get(model_or_method)
+        else:
+            m = model_or_method
+        return m.header, m.pcomp or b""
+
+    @staticmethod
+    def _verify_records(rec, n):
+        return [{"status": int(rec[i].status), "out_len": int(rec[i].out_len), "first_diff": int(rec[i].first_diff),
+                 "sha1": bytes(rec[i].sha1)} for i in range(n)]
+
+    def verify_blocks(self, model_or_method, pre, orig=None) -> List[dict]:
+        """zpaqhip_verify_blocks: Compressor.endSegmentChecksum for a set of blocks.  `pre[i]` are the pre-processed bytes of
+        block i (what preprocess_blocks / bwt_blocks / lzsa_blocks / lzht_blocks give, or a caller's own); they run through
+        the post-processor of `model_or_method` (a models name, a zpaql.Model or a method string) on the GPU as they would
+        after the decoder.  One dict per block: `status` (0, -28 when `orig` is given and differs, or the post-processor's
+        own error), `out_len` and `sha1` of what it wrote, `first_diff` (the first offset at which that differs from
+        orig[i]; 2**64 - 1 when equal or without `orig`)."""
+        header, pcomp = self._verify_model(model_or_method)
+        coded = [_as_u8(p) for p in pre]
+        n = len(coded)
+        if orig is not None and len(orig) != n:
+            raise ValueError("orig needs one entry per block")
+        cbuf, coffs = _cat(coded)
+        obuf, ooffs = _cat([_as_u8(b) for b in orig]) if orig is not None else (None, None)
+        hdr = _as_u8(header)
+        pc = _as_u8(pcomp) if pcomp else None
+        rec = (VerifyResult * max(1, n))()
+        err = Err()
+        rc = self._L.zpaqhip_verify_blocks(self._h, hdr.ctypes.data, hdr.size, pc.ctypes.data if pc is not None else None,
+                                           pc.size if pc is not None else 0, cbuf.ctypes.data, coffs.ctypes.data, n,
+                                           obuf.ctypes.data if obuf is not None else None,
+                                           ooffs.ctypes.data if ooffs is not None else None, rec, C.byref(err))
+        if rc:
+            _raise(err, rc)
+        return self._verify_records(rec, n)
+
+    def verify_blocks_device(self, model_or_method, d_in: int, in_off: Sequence[int], *, d_orig: int = 0,
+                             orig_off: Optional[Sequence[int]] = None, hip_stream: int = 0) -> List[dict]:
+        """zpaqhip_verify_blocks_device: verify_blocks on device buffers (pointers as ints): the pre-processed bytes of block i
+        at d_in + in_off[i], its plaintext (optional) at d_orig + orig_off[i]; only the records come back."""
+        header, pcomp = self._verify_model(model_or_method)
+        coffs = np.ascontiguousarray(in_off, dtype=np.uint64)
+        n = max(0, coffs.size - 1)
+        ooffs = np.ascontiguousarray(orig_off, dtype=np.uint64) if orig_off is not None else None
+        if ooffs is not None and ooffs.size != coffs.size:
+            raise ValueError("orig_off needs one entry per entry of in_off")
+        if (ooffs is None) != (not d_orig):
+            raise ValueError("d_orig and orig_off go together")
+        hdr = _as_u8(header)
+        pc = _as_u8(pcomp) if pcomp else None
+        rec = (VerifyResult * max(1, n))()
+        err = Err()
+        rc = self._L.zpaqhip_verify_blocks_device(self._h, hdr.ctypes.data, hdr.size, pc.ctypes.data if pc is not None else None,
+                                                  pc.size if pc is not None else 0, d_in or None, coffs.ctypes.data, n,
+                                                  d_orig or None, ooffs.ctypes.data if ooffs is not None else None, rec,
+                                                  hip_stream or None, C.byref(err))
+        if rc:
+            _raise(err, rc)
+        return self._verify_records(rec, n)
+
     def gap_hist_blocks_device(self, d_in: int, in_off: Sequence[int], hip_stream: int = 0) -> np.ndarray:
         """zpaqhip_gap_hist_blocks_device: gap_hist_blocks of blocks in device memory (block i at d_in + in_off[i], read where
         it is, any alignment): the same array, and all that crosses the bus."""
@@ -554,7 +638,7 @@ class Context:
     def compress_mixed_device(self, methods: List[str], method_of: Sequence[int], d_in: int, in_off: Sequence[int], d_out: int,
                               out_cap: int, *, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 0,
                               batch_blocks: int = 0, slot_bytes: int = 0, bwt: bool = False, sa: bool = False, ht: bool = False,
-                              enc_waves: int = 0, hip_stream: int = 0, raise_on_error: bool = True):
+                              enc_waves: int = 0, hip_stream: int = 0, raise_on_error: bool = True, verify: bool = False):
         """zpaqhip_compress_mixed_blocks_device: compress_method_device with a method per block: block i takes
         methods[method_of[i]], and the stream in d_out has the blocks in input order, each the bytes compress_method writes
         for it.  (rc, out_len, block_off) as compress_method_device.  Every method that a block takes is checked against
@@ -591,7 +675,7 @@ class Context:
             names = (C.c_char_p * max(1, n))(*[(f.encode() if isinstance(f, str) else f) for f in filenames])
         o = CompressOpts()
         o.struct_size = C.sizeof(CompressOpts)
-        o.flags = (1 if sha1 else 0) | (2 if tag else 0) | (4 if bwt else 0) | (8 if sa else 0) | (16 if ht else 0)
+        o.flags = compress_flags(sha1, tag, bwt, sa, ht, verify)
         o.kernel, o.batch_blocks, o.slot_bytes, o.enc_waves = kernel, batch_blocks, slot_bytes, enc_waves
         boffs = np.zeros(n + 1, np.uint64)
         err, got = Err(), C.c_size_t(0)
@@ -605,7 +689,7 @@ class Context:
     def compress_level_device(self, level: str, d_in: int, in_off: Sequence[int], d_out: int, out_cap: int, *, filenames=None,
                               sha1: bool = True, tag: bool = True, kernel: int = 2, batch_blocks: int = 0, slot_bytes: int = 0,
                               sa: bool = False, ht: bool = False, enc_waves: int = 0, hip_stream: int = 0,
-                              raise_on_error: bool = True):
+                              raise_on_error: bool = True, verify: bool = False):
         """compress_level on device buffers, in the style of compress_method_device: the plaintext of block i at d_in +
         in_off[i], the stream of compress_level(level, ...) to d_out, (rc, out_len, block_off) back.  At levels 5..9 the
         histogram is taken where the blocks are (gap_hist_blocks_device); method.expand_level runs per block on the host,
@@ -628,7 +712,7 @@ class Context:
         which = [index.setdefault(m, len(index)) for m in expanded]
         r = self.compress_mixed_device(list(index), which, d_in, off, d_out, out_cap, filenames=filenames, sha1=sha1, tag=tag,
                                        kernel=kernel, batch_blocks=batch_blocks, slot_bytes=slot_bytes, bwt=True, sa=sa, ht=ht,
-                                       enc_waves=enc_waves, hip_stream=hip_stream, raise_on_error=raise_on_error)
+                                       enc_waves=enc_waves, hip_stream=hip_stream, raise_on_error=raise_on_error, verify=verify)
         self.level_methods = expanded
         self.level_ms = {"analysis": (t1 - t0) * 1e3, "encode": (time.perf_counter() - t1) * 1e3}
         return r

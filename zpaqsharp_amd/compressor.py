@@ -8,7 +8,9 @@ encoder choice of both (2: ICM / ISSE / MIX chain models on the lane-per-compone
 waves per compute unit (0 automatic, 1 to 4; Context.compress_blocks).  `sa=True` gives the LZ77
 methods with args[5] - args[0] >= 21 the reference's suffix-array parse (Context.compress_method), with `method` and `level`;
 `ht=True` gives those with args[5] - args[0] < 21 its hash-table parse (args[3] = args[6] = 0 and the other limits of
-Context.lzht_blocks).
+Context.lzht_blocks).  `verify=True` is Compressor.setVerify: every block's coded sequence goes through its own
+post-processor on the GPU before it is coded, and a block that does not come back as its plaintext raises ZpaqError(-28)
+(Context.compress_blocks).
 
 With `level`, a numeric method "LB,R,t" (level, block size digits, redundancy, type), this is LibZPAQ.compress as the
 reference's callers use it (LibZPAQ.cs:84-108): the block size is (2^20 << B) - 4096 unless `block_size` is given, and
@@ -25,7 +27,7 @@ from .decompresser import Reader, Writer
 
 def compress(reader: Reader, writer: Writer, model="l1", block_size: Optional[int] = None, context: Optional[api.Context] = None,
              batch_blocks: int = 64, method: Optional[str] = None, bwt: bool = False, kernel: Optional[int] = None,
-             level: Optional[str] = None, sa: bool = False, ht: bool = False, enc_waves: int = 0) -> None:
+             level: Optional[str] = None, sa: bool = False, ht: bool = False, enc_waves: int = 0, verify: bool = False) -> None:
     if level is not None:
         from . import method as mth
         if method is not None:
@@ -49,11 +51,11 @@ def compress(reader: Reader, writer: Writer, model="l1", block_size: Optional[in
             if blocks:
                 if level is not None:
                     writer.write(ctx.compress_level(level, blocks, kernel=2 if kernel is None else kernel, sa=sa, ht=ht,
-                                                      enc_waves=enc_waves))
+                                                      enc_waves=enc_waves, verify=verify))
                 else:
-                    writer.write(ctx.compress_blocks(model, blocks, kernel=kernel or 0, enc_waves=enc_waves) if method is None
+                    writer.write(ctx.compress_blocks(model, blocks, kernel=kernel or 0, enc_waves=enc_waves, verify=verify) if method is None
                                  else ctx.compress_method(method, blocks, bwt=bwt, kernel=kernel or 0, sa=sa, ht=ht,
-                                                          enc_waves=enc_waves))
+                                                          enc_waves=enc_waves, verify=verify))
                 blocks.clear()
 
         # A Reader may return fewer bytes than asked before its end (Reader.cs:14-25): only an empty read ends the input,

@@ -19,6 +19,7 @@
 #include "zh_compress.h"
 #include "zh_ctx_view.h"
 #include "zh_enc.h"
+#include "zh_verify.h"
 
 extern "C" hipError_t zh_launch_enc_generic(const ZhEncLaunch *L, uint32_t grid, hipStream_t stream);
 extern "C" hipError_t zh_launch_enc_chain(const ZhEncLaunch *L, uint32_t grid, hipStream_t stream);
@@ -163,6 +164,7 @@ struct Call {
   hipStream_t user_stream = nullptr;
   DevSink *sink = nullptr;                // the device form appends to it instead of writing to `out`
   uint32_t pack_launches = 0;             // zh_frame.hip's launches, of staging and of framing
+  uint32_t verify_launches = 0;           // the verify pass's (opts.flags bit 5)
   ZhModel M;
   std::vector<uint8_t> code, sel, dev_prefix;   // the selector prefix; what of it goes in front of the bytes on the device
   bool store = false;                     // n = 0: no encoder, the store layout of the pre-processed bytes (a level 2 block)
@@ -180,14 +182,16 @@ struct Call {
   ChainPlan chain;                        // ... with this many waves at most
 
   bool want_sha() const { return (o.flags & 1) != 0; }
+  bool want_verify() const { return (o.flags & kFlagVerify) != 0; }
   uint64_t in_len(size_t i) const { return in_off[i + 1] - in_off[i]; }
   uint64_t plain_len(size_t i) const { return orig ? orig_off[i + 1] - orig_off[i] : in_len(i); }
   uint64_t coded_len(size_t i) const { return dev_prefix.size() + (pre ? pre->bound(i) : in_len(i)); }   // (an upper bound with pre)
   uint64_t slot_cap(uint64_t n) const { return o.slot_bytes ? o.slot_bytes : auto_slot(n); }
   uint64_t block_cost(size_t i) const {
-    if (store) return pre->bound(i) + pre->scratch(i);
+    const uint64_t vc = want_verify() ? 2 * plain_len(i) + (store ? pre->bound(i) : 0) : 0;   // post-processed bytes, plaintext, staged copy
+    if (store) return pre->bound(i) + pre->scratch(i) + vc;
     const uint64_t n = coded_len(i);
-    uint64_t c = n + slot_cap(n) + 64 + (orig && want_sha() ? plain_len(i) : 0) + (pre ? pre->scratch(i) : 0);
+    uint64_t c = n + slot_cap(n) + 64 + (orig && want_sha() ? plain_len(i) : 0) + (pre ? pre->scratch(i) : 0) + vc;
     if (route_encode(M, o, n) == EncKernel::Cm) c += 24 * n + 4 * (ZH_ENC_CM_KEYS + 1);
     return c;
   }
@@ -196,6 +200,7 @@ struct Call {
   int plan(Batch &B, size_t b0) const;
   int stage(Batch &B);
   int digests(Batch &B) const;
+  int verify(Batch &B);
   int encode(const Batch &B, EncRun &r);
   int encode_batch(Batch &B);
   int retry(Batch &B);
@@ -308,6 +313,53 @@ int Call::digests(Batch &B) const {
   HIPCHK(d_orig.alloc(total));
   HIPCHK(hipMemcpy(d_orig.p, h_orig.data(), total, hipMemcpyHostToDevice));
   return sha1_segments(v, d_orig.as<uint8_t>(), seg, B.digest, err);
+}
+
+// opts.flags bit 5 (Compressor.setVerify): the batch's coded sequences through the block's own post-processor, against the
+// plaintext the size comment and SHA-1 describe; the lowest failing block ends the call
+int Call::verify(Batch &B) {
+  if (!want_verify()) return ZPAQHIP_OK;
+  const size_t nb = B.nb(), np = dev_prefix.size();
+  VerifyIn vin;
+  DevMem d_stage, d_orig;
+  if (store) {                            // (the store layout keeps the selector on the host: a copy with it in front)
+    if (const int rc = verify_stage(v, sel, B.d_in.as<uint8_t>(), B.boff, B.blen, d_stage, vin, &verify_launches, err)) return rc;
+  } else {
+    vin.d_in = B.d_in.as<uint8_t>();
+    vin.off = B.boff;
+    vin.len = B.blen;
+  }
+  vin.poff.resize(nb);
+  vin.plen.resize(nb);
+  for (size_t j = 0; j < nb; ++j) vin.plen[j] = plain_len(B.b0 + j);
+  if (pre) {
+    vin.d_plain = B.pre.plain;
+    for (size_t j = 0; j < nb; ++j) vin.poff[j] = in_off[B.b0 + j] - in_off[B.b0];
+  } else if (!orig) {                     // the coded bytes behind the prefix are what the segment describes
+    vin.d_plain = B.d_in.as<uint8_t>();
+    for (size_t j = 0; j < nb; ++j) vin.poff[j] = B.boff[j] + np;
+  } else if (dev_in) {
+    vin.d_plain = orig;
+    for (size_t j = 0; j < nb; ++j) vin.poff[j] = orig_off[B.b0 + j];
+  } else {
+    const uint64_t base = orig_off[B.b0], bytes = orig_off[B.b1] - base;
+    HIPCHK(d_orig.alloc(bytes + 16));
+    if (bytes) HIPCHK(hipMemcpy(d_orig.p, orig + base, bytes, hipMemcpyHostToDevice));
+    vin.d_plain = d_orig.as<uint8_t>();
+    for (size_t j = 0; j < nb; ++j) vin.poff[j] = orig_off[B.b0 + j] - base;
+  }
+  std::vector<zpaqhip_verify_result> rec;
+  uint64_t wrote = 0;
+  if (const int rc = verify_pass(v, M.ph, M.pm, vin, budget / 4, rec, &st.kernel_ms, &verify_launches, &wrote, err)) {
+    if (err && err->block >= 0) err->block += (int32_t)B.b0;
+    return rc;
+  }
+  for (size_t j = 0; j < nb; ++j)
+    if (rec[j].status) {
+      set_err(err, rec[j].status, (int)(B.b0 + j), -1);
+      return rec[j].status;
+    }
+  return ZPAQHIP_OK;
 }
 
 // allocate what r's blocks need, upload their descriptors, launch the encoders, fetch and check the results
@@ -626,7 +678,7 @@ int zh::compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, cons
   if ((rc = c.open(ctx))) return rc;
   for (size_t b0 = 0; b0 < n_blocks;) {
     Batch B;
-    if ((rc = c.plan(B, b0)) || (rc = c.stage(B)) || (rc = c.digests(B))) return rc;
+    if ((rc = c.plan(B, b0)) || (rc = c.stage(B)) || (rc = c.digests(B)) || (rc = c.verify(B))) return rc;
     if (!c.store && ((rc = c.encode_batch(B)) || (rc = c.retry(B)))) return rc;
     if ((rc = c.frame(B))) return rc;
     b0 = B.b1;
@@ -634,7 +686,7 @@ int zh::compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, cons
   // A known wart, kept for zpaqhip_last_stats' sake: the store layout counts the pre-processing launches, the encoders' path
   // counts its own only.
   if (c.store) c.st.launches = pre->launches;
-  c.st.launches += c.pack_launches;
+  c.st.launches += c.pack_launches + c.verify_launches;
   c.st.kernel_kind = c.store ? 0 : c.any_chain ? 3 : c.any_cm ? 2 : 1;
   if (c.sink) c.sink->used = c.pos;
   return finish_call(c.v, c.st, c.pos, n_blocks, block_off, c.sink ? ~(size_t)0 : out_cap, out_len, err);

@@ -46,6 +46,7 @@ const char *status_message(int code) {
     case ZPAQHIP_E_ARG: return "bad argument";
     case ZPAQHIP_E_BUDGET: return "ZPAQL instruction budget exhausted";
     case ZPAQHIP_E_CALLBACK: return "read/write callback failed";
+    case ZPAQHIP_E_VERIFY: return "Pre/post-processor test failed";
     case ZH_E_SKIPPED: return "segment skipped after an earlier error in its block";
     default: return "unknown status";
   }

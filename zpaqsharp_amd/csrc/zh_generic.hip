@@ -12,6 +12,11 @@
 // min / mid / max models) and zh_chain.hip (any chain of <= 64 components) hold
 // the lane-parallel kernels the host routes recognised models to.  Nothing here
 // runs on the CPU.
+//
+// zh_verify_vm.hip includes this file with ZH_RAW_INPUT: the same kernel under
+// another name for n = 0 models whose segment is the decoded bytes themselves
+// (ZhSegDesc::in_len of them) instead of the store layout's chunks.  Without the
+// macro nothing here changes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -165,6 +170,9 @@ __device__ int decode_byte(Pred &P, Coder &d, Src &in, uint64_t budget) {
     }
     return c - 256;
   }
+#ifdef ZH_RAW_INPUT
+  return src_get(in);                                  // -1 at the segment's end (in.end)
+#endif
   if (d.curr == 0) {
     for (int i = 0; i < 4; ++i) d.curr = d.curr << 8 | (uint32_t)src_get(in);
     if (d.curr == 0) return -1;
@@ -175,7 +183,12 @@ __device__ int decode_byte(Pred &P, Coder &d, Src &in, uint64_t budget) {
 
 }  // namespace
 
-extern "C" __global__ __launch_bounds__(64) void zh_decode_generic(ZhLaunch L) {
+#ifndef ZH_RAW_INPUT
+#define ZH_GENERIC_KERNEL zh_decode_generic
+#define ZH_GENERIC_LAUNCH zh_launch_generic
+#endif
+
+extern "C" __global__ __launch_bounds__(64) void ZH_GENERIC_KERNEL(ZhLaunch L) {
   __shared__ GenLds S;
   const uint32_t lane = threadIdx.x;
 
@@ -255,6 +268,9 @@ extern "C" __global__ __launch_bounds__(64) void zh_decode_generic(ZhLaunch L) {
         // Decoder.get() reads the caller's Reader, which does not stop at the segment end
         // (Decoder.cs:112-122): only the end of the stream is EOF.
         in.p = L.in + sd.in_off; in.end = L.in + L.in_total;
+#ifdef ZH_RAW_INPUT
+        in.end = in.p + sd.in_len;
+#endif
         const uint64_t start = out.len;
         int status = 0;
         for (;;) {                                     // Decompresser.decompress(-1), Decompresser.cs:121-153
@@ -272,7 +288,7 @@ extern "C" __global__ __launch_bounds__(64) void zh_decode_generic(ZhLaunch L) {
   }
 }
 
-extern "C" hipError_t zh_launch_generic(const ZhLaunch *L, uint32_t grid, hipStream_t stream) {
-  hipLaunchKernelGGL(zh_decode_generic, dim3(grid), dim3(64), 0, stream, *L);
+extern "C" hipError_t ZH_GENERIC_LAUNCH(const ZhLaunch *L, uint32_t grid, hipStream_t stream) {
+  hipLaunchKernelGGL(ZH_GENERIC_KERNEL, dim3(grid), dim3(64), 0, stream, *L);
   return hipGetLastError();
 }

@@ -28,6 +28,10 @@
 // parsers without `out`: the flusher moves the ring to M only, and at the end of a segment, with everything flushed, the
 // parser wave runs the program's loop over M[0 .. d) as zh_e8e9_wave.h's schedule (e8_pass), which writes the Writer and
 // M.  A segment that writes more than |M| bytes is handed back: the program's loop then runs with wrapped indices.
+//
+// zh_verify_lz.hip includes this file with ZH_RAW_INPUT: the same kernel under another name whose segment is the decoded
+// bytes themselves (selector, then pre-processed bytes, ZhSegDesc::in_len of them) instead of the store layout's chunks.
+// Without the macro nothing here changes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -111,6 +115,13 @@ __device__ __forceinline__ int rd_byte(Rd &r, StoreLds &S, uint32_t lane) {
 // the header or the chunk runs past the stream (Decoder.get would return -1 in the middle: left to the generic kernel)
 __device__ __forceinline__ int rd_chunk(Rd &r, StoreLds &S, uint32_t lane) {
   if (r.left) return 0;
+#ifdef ZH_RAW_INPUT
+  // no chunks: what is left of the segment (r.in.total is its end) is one run of payload, taken 2^31 - 1 bytes at a time
+  const uint64_t rest = uni64(r.in.total - in_pos(r.in));
+  if (rest == 0) return kEos;
+  r.left = rest < 0x7FFFFFFFull ? (uint32_t)rest : 0x7FFFFFFFu;
+  return 0;
+#endif
   uint32_t v = 0;
   for (int i = 0; i < 4; ++i) {
     const int c = rd_byte(r, S, lane);
@@ -669,7 +680,12 @@ typedef BwtLdsT<4096u> BwtLds;
 static_assert(sizeof(BwtLds) <= kRing, "the inverse BWT's tables live in the ring");
 }  // namespace
 
-extern "C" __global__ __launch_bounds__(128) void zh_decode_store(ZhLaunch L) {
+#ifndef ZH_RAW_INPUT
+#define ZH_STORE_KERNEL zh_decode_store
+#define ZH_STORE_LAUNCH zh_launch_store
+#endif
+
+extern "C" __global__ __launch_bounds__(128) void ZH_STORE_KERNEL(ZhLaunch L) {
   __shared__ StoreLds S;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = uni(threadIdx.x >> 6);
@@ -744,6 +760,9 @@ extern "C" __global__ __launch_bounds__(128) void zh_decode_store(ZhLaunch L) {
       const uint64_t seg_off = uni64(L.segs[si].in_off);
       Rd r;
       r.in.stream = L.in; r.in.total = L.in_total; r.in.cbase = 0; r.in.k = 0; r.in.avail = 0; r.in.cur = 0;
+#ifdef ZH_RAW_INPUT
+      r.in.total = seg_off + uni64(L.segs[si].in_len);
+#endif
       r.left = 0; r.kdisc = 0;
       rd_seek(r, S, seg_off, lane);
       seg_base = wp;                                     // (the flusher is idle: everything before was flushed at the last segment's end)
@@ -904,7 +923,7 @@ extern "C" __global__ __launch_bounds__(128) void zh_decode_store(ZhLaunch L) {
   st_put0(&S.cmd, cmd_seq << 2 | kCmdExit);
 }
 
-extern "C" hipError_t zh_launch_store(const ZhLaunch *L, uint32_t grid, hipStream_t stream) {
-  hipLaunchKernelGGL(zh_decode_store, dim3(grid), dim3(128), 0, stream, *L);    // parser wave + flusher wave
+extern "C" hipError_t ZH_STORE_LAUNCH(const ZhLaunch *L, uint32_t grid, hipStream_t stream) {
+  hipLaunchKernelGGL(ZH_STORE_KERNEL, dim3(grid), dim3(128), 0, stream, *L);    // parser wave + flusher wave
   return hipGetLastError();
 }

@@ -1,5 +1,5 @@
-// A stand-alone drive of zh_stream_plan.h: the rules of the whole-stream pipeline and of zpaqhip_decompress_multi without a
-// GPU.  tests/test_stream_plan.py builds it with -fsanitize=address,undefined next to zh_framing.cpp (scan_stream,
+// A stand-alone drive of zh_stream_plan.h: the rules of the whole-stream pipeline, of zpaqhip_decompress_multi and of
+// zpaqhip_decompress_device without a GPU.  tests/test_stream_plan.py builds it with -fsanitize=address,undefined next to zh_framing.cpp (scan_stream,
 // build_model), writes the cases to a file, runs it and compares what it prints with expectations of its own.  Where the
 // driver in zh_api.cpp enqueues a copy from a device buffer, this program does a memcpy from a heap buffer of exactly the
 // planned size into a heap buffer of exactly the caller's capacity, so a copy that leaves either is an ASan report.
@@ -12,6 +12,11 @@
 //   deliver NAME FORM CAP UPTO PARTIAL TOTAL0 BLK0 N  (REAL SLOT FIX PLACE PLACE_CAP)...     FORM = mem | writer | placed
 //   queue NAME N_DEV ALL_CM1 N  COST...
 //   places NAME OUT_CAP DAMAGED N  (HINT REAL)...            DAMAGED = -1: none
+//   device NAME OUT_CAP BUDGET NO_STAGING DAMAGED DAMAGED_AT SHA_BAD N  (HINT REAL NSEG)...
+//       the whole sequence of zpaqhip_decompress_device.  NO_STAGING = 1: the staging buffer cannot be reserved; DAMAGED: a
+//       segment (stream index, -1: none) that fails from its block's DAMAGED_AT-th decode on; SHA_BAD: a segment whose
+//       checksum differs
+//   modelcut NAME PATH
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -307,6 +312,170 @@ static void do_places() {
   hex("out", out.get(), std::min(out_len, out_cap));
 }
 
+// ---- zpaqhip_decompress_device, played with heap buffers in place of device buffers
+struct Heap {                             // exactly n bytes: an access outside them is an ASan report
+  std::unique_ptr<uint8_t[]> p;
+  size_t n = 0;
+  void reserve(size_t bytes) { p.reset(new uint8_t[bytes]); n = bytes; memset(p.get(), 0xEE, bytes); }
+};
+
+// What decode_launch + decode_finish leave of blocks `ids` decoded to base + off[i] with room cap[i], as the kernels' segment
+// epilogue reports it (seg_done / seg_skipped, zh_dev.h) and decode_finish copies it: a segment's out_off = the block's
+// offset + the bytes of the block before it, its out_len what it produced, both counted past the room; bytes are written
+// only inside the room; status ZPAQHIP_E_OUTPUT_FULL when the block's bytes up to and with the segment exceed the room,
+// which does not stop the block; any other error does, and the segments behind it are ZH_E_SKIPPED with out_len 0.
+// (decode_finish's ZH_E_STOPPED and in_used rules do not come up: every segment here ends where its coded data ends.)
+struct FakeDecoder {
+  long damaged, damaged_at;
+  std::vector<uint64_t> seg_len;          // plaintext of every segment
+  std::vector<int> decodes;               // per block
+  void run(DevPlan &pl, const DevDecode &d, Heap &base) {
+    for (size_t j = 0; j < d.ids.size(); ++j) {
+      const size_t b = d.ids[j];
+      const zpaqhip_block &B = pl.blocks[b];
+      ++decodes[b];
+      uint64_t produced = 0;
+      bool failed = false;
+      for (uint32_t i = 0; i < B.n_seg; ++i) {
+        const size_t s = B.first_seg + i;
+        zpaqhip_seg_result &r = pl.res[s];
+        r = zpaqhip_seg_result{};
+        r.out_off = d.off[j] + produced;
+        if (failed) { r.status = ZH_E_SKIPPED; continue; }
+        const bool bad = (long)s == damaged && decodes[b] >= damaged_at;
+        const uint64_t n = bad ? seg_len[s] / 2 : seg_len[s];
+        for (uint64_t q = produced; q < produced + n && q < d.cap[j]; ++q) {
+          if (d.off[j] + q >= base.n) { printf("decoder writes outside its buffer\n"); exit(1); }
+          base.p[d.off[j] + q] = plain(b, (size_t)q);
+        }
+        produced += n;
+        r.out_len = n;
+        r.status = bad ? ZPAQHIP_E_CORRUPT : produced > d.cap[j] ? ZPAQHIP_E_OUTPUT_FULL : ZPAQHIP_OK;
+        failed = bad;
+      }
+    }
+    note_decoded(pl, d.ids);
+  }
+};
+
+static void run_entries(const std::vector<ZhFrameEntry> &tab, Heap &dst, const Heap &d_out, const Heap &staging, const Heap &fix) {
+  for (const ZhFrameEntry &e : tab) {
+    const Heap &src = e.src == ZH_FRAME_SRC_INPUT ? d_out : e.src == ZH_FRAME_SRC_FIRST ? staging : fix;
+    memcpy(dst.p.get() + e.dst_off, src.p.get() + e.src_off, (size_t)e.body_len);
+  }
+}
+
+static void do_device() {
+  const std::string name = word();
+  const uint64_t out_cap = u64(), budget = u64();
+  const bool no_staging = u64() != 0;
+  const long damaged = i64(), damaged_at = i64(), sha_bad = i64();
+  const size_t nb = (size_t)u64();
+  DevPlan p;
+  p.blocks.resize(nb);
+  std::vector<uint64_t> seg_len;
+  for (size_t b = 0; b < nb; ++b) {
+    zpaqhip_block &B = p.blocks[b];
+    memset(&B, 0, sizeof B);
+    B.usize_hint = u64();
+    const uint64_t real = u64();
+    B.first_seg = (uint32_t)seg_len.size(); B.n_seg = (uint32_t)u64();
+    for (uint32_t i = 0; i < B.n_seg; ++i) {
+      zpaqhip_segment g;
+      memset(&g, 0, sizeof g);
+      g.block = (uint32_t)b; g.flags = 1; g.data_len = 40;
+      p.segs.push_back(g);
+      seg_len.push_back(i + 1 < B.n_seg ? real / B.n_seg : real - real / B.n_seg * (B.n_seg - 1));
+    }
+  }
+  p.cut(nb);
+  FakeDecoder dec{damaged, damaged_at, seg_len, std::vector<int>(nb, 0)};
+  Heap d_out, staging, fix;
+  d_out.reserve((size_t)out_cap);
+  staging.reserve(0); fix.reserve(0);
+
+  // ---- the driver's sequence (zpaqhip_decompress_device, zh_api.cpp)
+  dec.run(p, plan_direct(p, out_cap), d_out);
+  if (p.bad.limit > p.k) {
+    const std::vector<zpaqhip_block> rest(p.blocks.begin() + (ptrdiff_t)p.k, p.blocks.end());
+    std::vector<uint64_t> cap, off;
+    uint64_t bytes = plan_slots(rest, p.segs, budget, cap, off);
+    if (no_staging) { count_only_slots(cap, off); bytes = 0; }
+    staging.reserve((size_t)bytes);
+    dec.run(p, plan_staged(p, cap, off), staging);
+  }
+  const size_t k = p.k;
+  const DevSecond second = plan_device_second(p);
+  fix.reserve((size_t)second.fix_bytes);
+  run_entries(second.move, fix, d_out, staging, fix);
+  dec.run(p, second.redo, fix);
+  const Heap *base[3] = {&d_out, &staging, &fix};
+  for (DevWhere w : {DevWhere::kOut, DevWhere::kStaging, DevWhere::kFix}) {
+    const Sha1Table t = device_sha1_table(p, w);
+    for (size_t j = 0; j < t.which.size(); ++j) {         // the digest kernel reads these bytes: they are the segment's
+      const size_t s = t.which[j], b = p.segs[s].block;
+      uint64_t before = 0;
+      for (size_t s2 = p.blocks[b].first_seg; s2 < s; ++s2) before += seg_len[s2];
+      for (uint64_t q = 0; q < t.pairs[2 * j + 1]; ++q)
+        if (base[(int)w]->p[t.pairs[2 * j] + q] != plain(b, (size_t)(before + q))) { printf("checksum table: segment %zu is not at its offset\n", s); exit(1); }
+      if (t.pairs[2 * j + 1] != seg_len[s]) { printf("checksum table: segment %zu has the wrong length\n", s); exit(1); }
+      if ((long)s == sha_bad) p.res[s].status = ZPAQHIP_E_SHA1;
+    }
+  }
+  lowest_failed_block(p.blocks, p.res, p.bad);
+  const DevGather g = plan_gather(p, out_cap);
+  run_entries(g.entries, d_out, d_out, staging, fix);
+  const size_t n_res = device_result_count(p);
+  std::vector<zpaqhip_seg_result> results(p.segs.size());
+  for (zpaqhip_seg_result &r : results) r.status = 12345;  // (not written)
+  device_results(p, g, results.data());
+  const int rc = p.bad.rc ? p.bad.rc : g.out_len() > out_cap ? ZPAQHIP_E_OUTPUT_FULL : ZPAQHIP_OK;
+
+  printf("device %s rc=%d block=%d seg=%d out_len=%llu n_res=%zu k=%zu staging=%zu fix=%llu moves=%zu\n", name.c_str(), rc,
+         p.bad.rc ? p.bad.err.block : -1, p.bad.rc ? p.bad.err.segment : -1, (unsigned long long)g.out_len(), n_res, k, staging.n,
+         (unsigned long long)second.fix_bytes, second.move.size());
+  list("decodes", std::vector<uint64_t>(dec.decodes.begin(), dec.decodes.end()));
+  std::vector<uint64_t> off, len;
+  for (size_t s = 0; s < n_res; ++s) { off.push_back(results[s].out_off); len.push_back(results[s].out_len); }
+  printf("res_status=");
+  for (size_t s = 0; s < n_res; ++s) printf("%s%d", s ? "," : "", results[s].status);
+  printf("\n");
+  list("res_off", off);
+  list("res_len", len);
+  for (size_t s = n_res; s < results.size(); ++s)
+    if (results[s].status != 12345) { printf("a record behind n_res was written\n"); exit(1); }
+  hex("out", d_out.p.get(), (size_t)out_cap);
+}
+
+// The model cut through an accessor that hands out a copy of one header at a time (the device form's), against the batch's
+static void do_modelcut() {
+  const std::string name = word(), path = word();
+  std::ifstream file(path, std::ios::binary);
+  if (!file) { fprintf(stderr, "%s: cannot open %s\n", name.c_str(), path.c_str()); exit(2); }
+  const std::vector<uint8_t> data((std::istreambuf_iterator<char>(file)), std::istreambuf_iterator<char>());
+  Source src;
+  src.mem = data.data(); src.mem_len = data.size();
+  Batch bt;
+  zpaqhip_err err{};
+  if (next_batch(src, bt, 0, 0, 0, 0, &err)) { printf("error\n"); return; }
+  ScanOut so;
+  zpaqhip_err e2{};
+  (void)scan_stream(data.data(), data.size(), so, &e2, batch_limit(0, 0));
+  ModelCut cut;
+  std::unique_ptr<uint8_t[]> hdr;
+  size_t fetched = 0;
+  const int rc = first_bad_model(so.blocks, [&](size_t b, const uint8_t *&h) {
+    hdr.reset(new uint8_t[so.blocks[b].hdr_len]);
+    memcpy(hdr.get(), data.data() + so.blocks[b].hdr_off, so.blocks[b].hdr_len);
+    h = hdr.get();
+    ++fetched;
+    return ZPAQHIP_OK;
+  }, cut);
+  printf("modelcut %s\n", name.c_str());
+  printf("batch nb=%zu rc=%d block=%d seg=%d msg=%s\n", bt.so.blocks.size(), bt.rc_after, bt.err_after.block, bt.err_after.segment, bt.err_after.msg);
+  printf("accessor nb=%zu rc=%d block=%d seg=%d msg=%s call=%d fetched=%zu\n", cut.nb, cut.rc, cut.err.block, cut.err.segment, cut.err.msg, rc, fetched);
+}
+
 int main(int argc, char **argv) {
   std::ifstream file;
   if (argc > 1) file.open(argv[1]);
@@ -320,6 +489,8 @@ int main(int argc, char **argv) {
     else if (w == "deliver") do_deliver();
     else if (w == "queue") do_queue();
     else if (w == "places") do_places();
+    else if (w == "device") do_device();
+    else if (w == "modelcut") do_modelcut();
     else { fprintf(stderr, "case file: unknown case '%s'\n", w.c_str()); return 2; }
   }
   return 0;

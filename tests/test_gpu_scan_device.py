@@ -179,6 +179,27 @@ def test_decompress_device_wrong_size_comments(ctx, texts):
         assert check_whole(ctx, s, tail_clean=False) == d[0] + d[4] + d[5] + d[6] + d[1] + d[2]
 
 
+def test_decompress_device_wrong_size_comments_and_output_too_small(ctx, texts):
+    """Moves and second decodes under clipping: the wrong-size streams above with out_cap one byte short of the total, one
+    byte into the block behind the wrong one, and 0.  The total is counted, nothing is written outside d_out[0, out_cap)
+    (device_decompress checks the guards)."""
+    d = texts
+    small, large = b"100", b"99999"
+    streams = [
+        (plain_block("l1", d[0]) + plain_block("mid", d[4], comment=small) + plain_block("l1", d[5]) + plain_block("l1", d[2], comment=b"")
+         + plain_block("mid", d[6]), [d[0], d[4], d[5], d[2], d[6]]),
+        (plain_block("l1", d[0]) + plain_block("mid", d[4], comment=large) + plain_block("l1", d[5]) + plain_block("min", d[6]),
+         [d[0], d[4], d[5], d[6]]),
+        (plain_block("l1", d[0]) + plain_block("mid", d[4], comment=small) + plain_block("l1", d[5]) + plain_block("mid", d[6], comment=large)
+         + plain_block("l1", d[1]) + plain_block("l1", d[2]), [d[0], d[4], d[5], d[6], d[1], d[2]]),
+    ]
+    for s, parts in streams:
+        total = sum(len(x) for x in parts)
+        for cap in (total - 1, len(parts[0]) + len(parts[1]) + 1, 0):
+            rc, n, got = device_decompress(ctx, s, cap)
+            assert rc == OUT_FULL and n == total, (len(parts), cap)
+
+
 def test_decompress_device_output_too_small(ctx, texts):
     for comment in (None, b""):
         s = b"".join(plain_block(m, d, comment=comment) for m, d in zip(["l1", "mid", "l1", "mid"], texts))

@@ -1,5 +1,6 @@
 """zh_stream_plan.h — the rules of the whole-stream pipeline (batches, staging slots, the second pass, the first failure, what is
-delivered where) and of zpaqhip_decompress_multi (queue, slots, outcome, settle_places) — driven on the host in a stand-alone
+delivered where), of zpaqhip_decompress_multi (queue, slots, outcome, settle_places) and of zpaqhip_decompress_device (direct
+and staged placing, moves, the second decode, the gather, the result records) — driven on the host in a stand-alone
 C++ program built with -fsanitize=address,undefined (tests/native/stream_plan_main.cpp).  The program copies with memcpy between
 heap buffers of exactly the planned sizes, so a rule that would write past a caller's out_cap is an ASan report here, not a heap
 overrun in a GPU run.  No GPU, and no Python under a sanitizer."""
@@ -18,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "zpaqsharp_amd", "csrc")
 NONE = (1 << 64) - 1                                      # no size in the comment
 KIB, MIB = 1 << 10, 1 << 20
-E_HM_TOO_BIG, E_OUTPUT_FULL, E_CORRUPT, E_SKIPPED = -6, -20, -1, -100
+E_HM_TOO_BIG, E_OUTPUT_FULL, E_CORRUPT, E_SKIPPED, E_SHA1 = -6, -20, -1, -100, -21
 BATCH_BLOCKS = (1, 2, 3, 7, 8, 0)
 READS = (0, 97, 777)                                      # the memory source, callback sources with short reads
 
@@ -119,7 +120,7 @@ def run(tmp_path_factory):
         got = {}
         for line in r.stdout.split("\n")[:-1]:
             head = line.split(" ")
-            if head[0] in ("slots", "batches", "second", "deliver", "queue", "places") and len(head) >= 2 and "=" not in head[1]:
+            if head[0] in ("slots", "batches", "second", "deliver", "queue", "places", "device", "modelcut") and len(head) >= 2 and "=" not in head[1]:
                 cur = got.setdefault(head[1], [line])
             elif head[0] == "limit":
                 got[" ".join(head[:3])] = [line]
@@ -320,3 +321,187 @@ def test_settle_places(run):
     assert got["damaged-5"][3] == "rc=0 out_len=%d moved=1" % front and bytes.fromhex(got["damaged-5"][4][4:]) == whole[:front]
     assert got["short"][3] == "rc=%d out_len=%d moved=0" % (E_OUTPUT_FULL, out_len)
     assert got["exact"][3] == "rc=0 out_len=160 moved=0" and bytes.fromhex(got["exact"][4][4:]) == plain(0, 100) + plain(1, 60)
+
+
+# ---- zpaqhip_decompress_device: the whole sequence over heap buffers of exactly out_cap, the planned staging bytes and
+# fix_bytes.  A case: blocks as (size hint or NONE, plaintext size, segments), out_cap, the staging budget, an optional
+# damaged segment (failing from its block's n-th decode on) and an optional segment whose checksum differs.  What is
+# expected is worked out here from the case alone.
+PLENTY = 1 << 30
+HINTS = {
+    "right": [(300, 300, 1), (0, 0, 1), (250, 250, 2), (411, 411, 1), (120, 120, 1)],
+    "absent": [(NONE, 300, 1), (NONE, 0, 1), (NONE, 250, 2), (NONE, 411, 1), (NONE, 120, 1)],
+    "middle": [(300, 300, 1), (250, 250, 2), (NONE, 411, 1), (120, 120, 1), (77, 77, 1)],          # k = 2
+    "implausible": [(300, 300, 1), ((1 << 40) + 1, 250, 1), (120, 120, 1)],
+    "small": [(300, 300, 1), (100, 250, 2), (411, 411, 1), (120, 120, 1)],
+    "large": [(300, 300, 1), (999, 250, 2), (411, 411, 1), (120, 120, 1)],
+    "small-large": [(300, 300, 1), (100, 250, 1), (411, 411, 1), (999, 120, 1), (77, 77, 1), (200, 200, 2)],
+    # too large by one byte: blocks 2 and 3 are whole, one byte behind their final places, and overlap them
+    "large-by-one": [(300, 300, 1), (251, 250, 1), (411, 411, 2), (120, 120, 1)],
+    "zeros": [(0, 0, 1), (0, 200, 1), (300, 300, 1), (0, 0, 1), (50, 50, 1)],
+    "staged-wrong": [(300, 300, 1), (NONE, 250, 1), (100, 411, 2), (999, 120, 1)],               # wrong hints behind k: slots only
+}
+
+
+def _plausible(h):
+    return h != NONE and h <= 1 << 40
+
+
+class DevCase:
+    def __init__(self, name, blocks, out_cap, budget=PLENTY, no_staging=0, damaged=-1, damaged_at=1, sha_bad=-1, rooms=None):
+        self.name, self.blocks, self.out_cap = name, blocks, out_cap
+        self.line = "device %s %d %d %d %d %d %d %d %s" % (name, out_cap, budget, no_staging, damaged, damaged_at, sha_bad, len(blocks),
+                                                         "  ".join("%s %d %d" % (_tok(h), r, n) for h, r, n in blocks))
+        nb = len(blocks)
+        self.seg_block = [b for b, (_, _, n) in enumerate(blocks) for _ in range(n)]
+        self.seg_len = [r // n if i + 1 < n else r - r // n * (n - 1) for _, r, n in blocks for i in range(n)]
+        self.first_seg = [self.seg_block.index(b) for b in range(nb)]
+        k = next((b for b, (h, _, _) in enumerate(blocks) if not _plausible(h)), nb)
+        place = [sum(h for h, _, _ in blocks[:b]) for b in range(k)]
+        room = [max(0, min(blocks[b][0], out_cap - place[b])) for b in range(k)]
+        # behind k: the slot rule (the hint when plausible and within the budget, else the provisional 64 KiB of these small
+        # blocks); `rooms` where the budget drops slots, nothing where the reservation fails
+        room += rooms if rooms is not None else [0 if no_staging else (h if _plausible(h) and h <= budget else 64 * KIB) for h, _, _ in blocks[k:]]
+        dblock = self.seg_block[damaged] if damaged >= 0 else nb
+        count, limit, self.code, self.bad_seg = [0] * nb, nb, 0, -1
+
+        def fail(b, code, seg):
+            nonlocal limit
+            if b < limit:
+                limit, self.code, self.bad_seg = b, code, seg
+        for b in range(k):
+            count[b] = 1
+        if damaged_at == 1 and dblock < k:
+            fail(dblock, E_CORRUPT, damaged)
+        if limit > k:                                     # the staged blocks are decoded only when something of them can be delivered
+            for b in range(k, nb):
+                count[b] = 1
+            if damaged_at == 1:
+                fail(dblock, E_CORRUPT, damaged)
+        for b in range(limit):
+            count[b] += blocks[b][1] > room[b]
+        if damaged_at == 2 and dblock < limit and count[dblock] == 2:
+            fail(dblock, E_CORRUPT, damaged)
+        if sha_bad >= 0:
+            fail(self.seg_block[sha_bad], E_SHA1, sha_bad)
+        self.k, self.count, self.limit = k, count, limit
+        self.want = b"".join(plain(b, blocks[b][1]) for b in range(limit))
+        self.total = len(self.want)
+        self.n_res = self.first_seg[limit] + blocks[limit][2] if limit < nb else len(self.seg_len)
+        # a hint that promised more than its block holds (a block that failed, or lies behind one that did, holds nothing):
+        # blocks behind it were decoded further out in d_out, and what they left behind the delivered bytes stays
+        self.tail_clean = limit == nb and all(h <= r for h, r, _ in blocks[:k])
+
+    def check(self, lines):
+        head = dict(kv.split("=") for kv in lines[0].split(" ")[2:])
+        out = bytes.fromhex(lines[-1].split("=", 1)[1])
+        assert len(out) == self.out_cap
+        assert int(head["out_len"]) == self.total, self.name
+        assert int(head["k"]) == self.k, self.name
+        decodes = _ints(lines[1])
+        assert max(decodes) <= 2 and decodes == self.count, (self.name, decodes, self.count)
+        if self.code:
+            assert (int(head["rc"]), int(head["block"]), int(head["seg"])) == (self.code, self.limit, self.bad_seg), self.name
+        else:
+            assert int(head["rc"]) == (E_OUTPUT_FULL if self.total > self.out_cap else 0) and head["block"] == "-1", self.name
+        assert int(head["n_res"]) == self.n_res, self.name
+        # the records of the delivered blocks: stream-order offsets
+        n_ok = self.first_seg[self.limit] if self.limit < len(self.blocks) else self.n_res
+        assert _ints(lines[3])[:n_ok] == [sum(self.seg_len[:s]) for s in range(n_ok)], self.name
+        assert _ints(lines[4])[:n_ok] == self.seg_len[:n_ok] and _ints(lines[2])[:n_ok] == [0] * n_ok, self.name
+        if self.total <= self.out_cap:
+            assert out[:self.total] == self.want, self.name
+            assert not self.tail_clean or out[self.total:] == b"\xee" * (self.out_cap - self.total), self.name
+        else:                                             # (more than the header promises; every case here gets the exact prefix)
+            assert out == self.want[:self.out_cap], self.name
+        return head
+
+
+def _caps(blocks):
+    """total + 5, total, total - 1, 0, and one byte into and one byte short of the end of every block."""
+    real = [r for _, r, _ in blocks]
+    start = [sum(real[:b]) for b in range(len(real) + 1)]
+    return sorted({start[-1] + 5, start[-1], start[-1] - 1, 0} | {start[b] + 1 for b in range(len(real))} | {max(0, start[b + 1] - 1) for b in range(len(real))})
+
+
+def _run_device(run, cases):
+    got = run([c.line for c in cases])
+    return {c.name: c.check(got[c.name]) for c in cases}
+
+
+def test_device_form_hints_and_out_cap(run):
+    """Every hint set (all right, none, present then absent, implausible, too small, too large, both, too large by one byte,
+    zero-length blocks and a hint of 0 on a non-empty block) at every out_cap position: above, at and below the total, one
+    byte into and one byte short of the end of every block (directly placed, moved, staged, redone), and 0."""
+    cases = [DevCase("%s-%d" % (n, cap), bl, cap) for n, bl in HINTS.items() for cap in _caps(bl)]
+    heads = _run_device(run, cases)
+    total = {n: sum(r for _, r, _ in bl) for n, bl in HINTS.items()}
+    for n in ("right", "absent", "middle", "implausible"):                  # nothing wrong: nothing moved, nothing decoded twice
+        h = heads["%s-%d" % (n, total[n] + 5)]
+        assert (h["fix"], h["moves"]) == ("0", "0"), n
+    assert [heads["%s-%d" % (n, total[n])]["k"] for n in ("right", "absent", "middle", "implausible")] == ["5", "0", "2", "1"]
+    assert heads["small-%d" % total["small"]]["moves"] == "2" and heads["small-%d" % total["small"]]["fix"] == str(250 + 411 + 120)
+    by_one = heads["large-by-one-%d" % (total["large-by-one"] + 5)]
+    assert by_one["moves"] == "2" and by_one["fix"] == "531"
+    by_one = heads["large-by-one-%d" % total["large-by-one"]]               # the last block, one byte further out, is clipped: decoded again
+    assert by_one["moves"] == "1" and by_one["fix"] == "531"
+    assert heads["small-large-%d" % total["small-large"]]["moves"] == "2"   # blocks 2 and 3; 4 and 5 were placed behind out_cap: decoded again
+    assert heads["zeros-%d" % total["zeros"]]["moves"] == "2"               # block 3 is empty: it "moves" without an entry
+
+
+def test_device_form_staging_budget(run):
+    bl = [(NONE, 200, 1), (300, 300, 2), (500, 500, 1)]
+    cases = []
+    for cap in _caps(bl):
+        # 65536 + 300 + 500 is over the budget: the largest slot becomes count-only, its block is decoded a second time
+        cases.append(DevCase("short-%d" % cap, bl, cap, budget=66000, rooms=[0, 300, 500]))
+        cases.append(DevCase("hint-over-%d" % cap, bl, cap, budget=400, rooms=[0, 300, 0]))   # 500 > budget: a provisional slot, dropped too
+    for n in ("absent", "middle", "small", "staged-wrong"):
+        cases += [DevCase("none-%s-%d" % (n, cap), HINTS[n], cap, no_staging=1) for cap in _caps(HINTS[n])]
+    heads = _run_device(run, cases)
+    assert heads["short-1005"]["staging"] == "800" and heads["short-1005"]["fix"] == "200"
+    assert heads["hint-over-1005"]["staging"] == "300" and heads["hint-over-1005"]["fix"] == "700"
+    assert heads["none-absent-1086"]["staging"] == "0" and heads["none-absent-1086"]["fix"] == "1081"
+
+
+def test_device_form_damage_and_results(run):
+    """Whole blocks in front of the lowest failed block are delivered; out_len is their sum; error block, segment and the number
+    of result records as zpaqhip_decompress_device gives them."""
+    cases = []
+    for cap in (2000, 551, 300, 0):
+        cases += [
+            DevCase("direct-%d" % cap, HINTS["right"], cap, damaged=3),                     # second segment of block 2
+            DevCase("direct-first-%d" % cap, HINTS["right"], cap, damaged=0),
+            DevCase("staged-%d" % cap, HINTS["middle"], cap, damaged=3),                    # block 2, the first staged one
+            DevCase("staged-last-%d" % cap, HINTS["middle"], cap, damaged=5),
+            DevCase("direct-of-middle-%d" % cap, HINTS["middle"], cap, damaged=2),          # in front of k: nothing is staged at all
+            DevCase("second-decode-%d" % cap, HINTS["small"], cap, damaged=2, damaged_at=2),      # block 1 outgrew its hint
+            DevCase("second-decode-staged-%d" % cap, HINTS["staged-wrong"], cap, damaged=3, damaged_at=2),
+            DevCase("never-seen-%d" % cap, HINTS["right"], 2000 + cap, damaged=3, damaged_at=2),  # decoded once: no damage shows
+            DevCase("sha-direct-%d" % cap, HINTS["right"], cap, sha_bad=4),
+            DevCase("sha-moved-%d" % cap, HINTS["large"], cap, sha_bad=3),                  # block 2, moved out of the way
+            DevCase("sha-redone-%d" % cap, HINTS["small"], cap, sha_bad=1),
+            DevCase("sha-staged-%d" % cap, HINTS["middle"], cap, sha_bad=4),
+            DevCase("sha-behind-damage-%d" % cap, HINTS["small-large"], cap, damaged=4, sha_bad=2),
+        ]
+    heads = _run_device(run, cases)
+    assert (heads["direct-2000"]["rc"], heads["direct-2000"]["out_len"], heads["direct-2000"]["n_res"]) == (str(E_CORRUPT), "300", "4")
+    assert (heads["sha-moved-2000"]["rc"], heads["sha-moved-2000"]["block"], heads["sha-moved-2000"]["out_len"]) == (str(E_SHA1), "2", "550")
+    assert heads["direct-of-middle-2000"]["staging"] == "0"
+    # a two-segment block among moved blocks: every record is the stream-order offset (DevCase.check), here spelled out
+    got = run([DevCase("two-seg-moved", HINTS["large-by-one"], 1081).line])["two-seg-moved"]
+    assert got[3] == "res_off=0,300,550,755,961" and got[4] == "res_len=300,250,205,206,120"
+
+
+def test_model_cut_is_the_same_through_an_accessor(run):
+    """first_bad_model over a function that hands out one header at a time (the device form copies each from the GPU) against
+    cut_at_bad_model over the batch's bytes: the same cut, code, block and message."""
+    _, _, streams = _streams()
+    for sname in ("bad-model", "whole"):
+        (run.tmp / (sname + ".zpaq")).write_bytes(streams[sname][0])
+    got = run(["modelcut %s %s" % (n, run.tmp / (n + ".zpaq")) for n in ("bad-model", "whole")])
+    batch, acc = got["bad-model"][1], got["bad-model"][2]
+    assert batch.startswith("batch nb=3 rc=%d block=3 seg=-1 msg=" % E_HM_TOO_BIG) and len(batch.split("msg=")[1]) > 3
+    assert acc.startswith("accessor" + batch[5:]) and acc.endswith(" call=0 fetched=4")
+    assert got["whole"][1].startswith("batch nb=7 rc=0 ") and got["whole"][2].startswith("accessor nb=7 rc=0 ")
+    assert got["whole"][2].endswith(" call=0 fetched=7")

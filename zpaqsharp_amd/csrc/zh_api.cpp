@@ -578,62 +578,59 @@ extern "C" int zpaqhip_decode_blocks_device(zpaqhip_ctx *c, const void *d_in, co
 // ---------------------------------------------------------------------------
 namespace {
 
-// Staging buffer of a batch: plan_slots (zh_stream_plan.h) within a quarter of the free memory.
-int plan_staging(zpaqhip_ctx *c, Batch &bt, zpaqhip_err *err) {
-  bt.real.assign(bt.so.blocks.size(), 0);
+// Staging slots of `blocks` in out2[slot]: plan_slots (zh_stream_plan.h) within a quarter of the free memory, to which
+// `reusable` counts (the staging buffers the caller is free to grow).
+int plan_staging(zpaqhip_ctx *c, int slot, size_t reusable, const std::vector<zpaqhip_block> &blocks, const std::vector<zpaqhip_segment> &segs,
+                 std::vector<uint64_t> &cap, std::vector<uint64_t> &off, zpaqhip_err *err) {
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  free_b += c->out2[0].cap + c->out2[1].cap;
+  free_b += reusable;
   const uint64_t budget = free_b / 4 / std::max(1u, c->mem_share);   // per staging buffer; the arena needs the rest
-  const uint64_t pos = plan_slots(bt.so.blocks, bt.so.segs, budget, bt.cap, bt.off);
-  if (c->out2[bt.slot].reserve((size_t)pos + 16) != hipSuccess) {   // not even that: everything count-only, exact second pass
+  const uint64_t pos = plan_slots(blocks, segs, budget, cap, off);
+  if (c->out2[slot].reserve((size_t)pos + 16) != hipSuccess) {      // not even that: everything count-only, exact second pass
     (void)hipGetLastError();
-    std::fill(bt.cap.begin(), bt.cap.end(), 0ull);
-    std::fill(bt.off.begin(), bt.off.end(), 0ull);
-    HIPCHK(c->out2[bt.slot].reserve(16));
+    count_only_slots(cap, off);
+    HIPCHK(c->out2[slot].reserve(16));
   }
   return ZPAQHIP_OK;
 }
 
-// SHA-1 of every decoded segment of a batch that stores one, computed ON THE DEVICE over the staging buffers
-// (zh_sha1_dev.hip) while the plaintext is still there; bad[s] = 1 where the digest differs from the stored one
-// (Decompresser.cs:183-191).
-int sha1_mismatches(zpaqhip_ctx *c, const Batch &bt, std::vector<int> &bad, zpaqhip_err *err) {
-  const size_t ns = bt.so.segs.size();
-  bad.assign(ns, 0);
-  // two passes: segments in the staging buffer, segments in the second-pass buffer
+// SHA-1 of the table's segments (offsets from `base`), computed ON THE DEVICE (zh_sha1_dev.hip) on `stream` while the
+// plaintext is still there; the segments whose digest differs from the stored one (Decompresser.cs:183-191) are added to `bad`.
+int sha1_check(zpaqhip_ctx *c, hipStream_t stream, const uint8_t *base, const Sha1Table &t, const zpaqhip_segment *segs,
+               std::vector<uint32_t> &bad, zpaqhip_err *err) {
+  if (t.which.empty()) return ZPAQHIP_OK;
+  const size_t tab_bytes = t.pairs.size() * 8, dig_bytes = t.which.size() * 20;
+  HIPCHK(c->sdesc.reserve(tab_bytes + dig_bytes + 64));          // the descriptors of the finished decode are not needed any more
+  uint8_t *d_tab = (uint8_t *)c->sdesc.p, *d_dig = d_tab + ((tab_bytes + 15) & ~(size_t)15);
+  HIPCHK(hipMemcpyAsync(d_tab, t.pairs.data(), tab_bytes, hipMemcpyHostToDevice, stream));
+  HIPCHK(zh_launch_sha1(base, (const uint64_t *)d_tab, (uint32_t)t.which.size(), (uint32_t *)d_dig, stream));
+  std::vector<uint32_t> dig(t.which.size() * 5);
+  HIPCHK(hipMemcpyAsync(dig.data(), d_dig, dig_bytes, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  for (size_t k = 0; k < t.which.size(); ++k) {
+    uint8_t d[20];
+    for (int i = 0; i < 5; ++i) {
+      const uint32_t v = dig[5 * k + i];
+      d[4 * i] = (uint8_t)(v >> 24); d[4 * i + 1] = (uint8_t)(v >> 16); d[4 * i + 2] = (uint8_t)(v >> 8); d[4 * i + 3] = (uint8_t)v;
+    }
+    if (memcmp(d, segs[t.which[k]].sha1, 20) != 0) bad.push_back(t.which[k]);
+  }
+  return ZPAQHIP_OK;
+}
+
+// ... of every decoded segment of a batch that stores one: first those in the staging buffer, then those in the
+// second-pass buffer
+int sha1_mismatches(zpaqhip_ctx *c, const Batch &bt, std::vector<uint32_t> &bad, zpaqhip_err *err) {
   for (int where = 0; where < 2; ++where) {
-    std::vector<uint64_t> tab;
-    std::vector<uint32_t> which;
+    Sha1Table t;
     for (size_t b = 0; b < bt.so.blocks.size(); ++b) {
       if ((int)(bt.off[b] >> 63) != where) continue;
       const zpaqhip_block &B = bt.so.blocks[b];
-      for (uint32_t i = 0; i < B.n_seg; ++i) {
-        const size_t s = B.first_seg + i;
-        if (!(bt.so.segs[s].flags & 1) || bt.res[s].status != ZPAQHIP_OK) continue;
-        tab.push_back(bt.res[s].out_off);
-        tab.push_back(bt.res[s].out_len);
-        which.push_back((uint32_t)s);
-      }
+      for (uint32_t i = 0; i < B.n_seg; ++i) t.add(bt.so.segs[B.first_seg + i], bt.res[B.first_seg + i], B.first_seg + i, bt.res[B.first_seg + i].out_off);
     }
-    if (which.empty()) continue;
     const uint8_t *base = where ? (const uint8_t *)c->out_fix[bt.slot].p : (const uint8_t *)c->out2[bt.slot].p;
-    const size_t tab_bytes = tab.size() * 8, dig_bytes = which.size() * 20;
-    HIPCHK(c->sdesc.reserve(tab_bytes + dig_bytes + 64));        // the descriptors of the finished decode are not needed any more
-    uint8_t *d_tab = (uint8_t *)c->sdesc.p, *d_dig = d_tab + ((tab_bytes + 15) & ~(size_t)15);
-    HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(zh_launch_sha1(base, (const uint64_t *)d_tab, (uint32_t)which.size(), (uint32_t *)d_dig, c->stream));
-    std::vector<uint32_t> dig(which.size() * 5);
-    HIPCHK(hipMemcpyAsync(dig.data(), d_dig, dig_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (size_t k = 0; k < which.size(); ++k) {
-      uint8_t d[20];
-      for (int i = 0; i < 5; ++i) {
-        const uint32_t v = dig[5 * k + i];
-        d[4 * i] = (uint8_t)(v >> 24); d[4 * i + 1] = (uint8_t)(v >> 16); d[4 * i + 2] = (uint8_t)(v >> 8); d[4 * i + 3] = (uint8_t)v;
-      }
-      bad[which[k]] = memcmp(d, bt.so.segs[which[k]].sha1, 20) != 0;
-    }
+    if (int rc = sha1_check(c, c->stream, base, t, bt.so.segs.data(), bad, err)) return rc;
   }
   return ZPAQHIP_OK;
 }
@@ -792,6 +789,7 @@ int run_pipeline_impl(zpaqhip_ctx *c, Source &src, Sinkk &sink, const zpaqhip_op
   // launch: the batch's kernels enqueued behind its upload, writing to its staging buffer
   auto launch = [&](Batch &B) -> int {
     B.res.assign(B.so.segs.size(), zpaqhip_seg_result{});
+    B.real.assign(B.so.blocks.size(), 0);
     HIPCHK(hipStreamWaitEvent(c->stream, c->ev_in[B.slot], 0));
     return decode_launch(c, c->in2[B.slot].p, B.h, B.len, B.so.blocks.data(), B.so.blocks.size(), B.so.segs.data(),
                          B.so.segs.size(), nullptr, 0, c->out2[B.slot].p, B.off.data(), B.cap.data(), opts, c->stream, P, err);
@@ -805,11 +803,10 @@ int run_pipeline_impl(zpaqhip_ctx *c, Source &src, Sinkk &sink, const zpaqhip_op
     rc = settle_batch(c, B, opts, acc, err);
     if (rc) { rebase_err(err, B); return rc; }
     if (opts.verify_sha1) {
-      std::vector<int> bad;
+      std::vector<uint32_t> bad;
       rc = sha1_mismatches(c, B, bad, err);
       if (rc) return rc;
-      for (size_t s2 = 0; s2 < bad.size(); ++s2)
-        if (bad[s2] && B.res[s2].status == ZPAQHIP_OK) B.res[s2].status = ZPAQHIP_E_SHA1;
+      for (uint32_t s2 : bad) B.res[s2].status = ZPAQHIP_E_SHA1;
     }
     return ZPAQHIP_OK;
   };
@@ -823,7 +820,7 @@ int run_pipeline_impl(zpaqhip_ctx *c, Source &src, Sinkk &sink, const zpaqhip_op
   for (int cur = 0;; cur ^= 1) {
     Batch &B = bt[cur], &prev = bt[cur ^ 1];
     const bool have = !B.so.blocks.empty();
-    if (have && (rc = plan_staging(c, B, err))) return rc;
+    if (have && (rc = plan_staging(c, B.slot, c->out2[0].cap + c->out2[1].cap, B.so.blocks, B.so.segs, B.cap, B.off, err))) return rc;
     if (have && (rc = launch(B))) {                      // (device memory, HIP): what is already decoded is delivered first
       rebase_err(err, B);
       if (have_prev) { zpaqhip_err e3{}; (void)drain_batch(c, prev, prev.so.blocks.size(), 0, sink, &e3); (void)hipStreamSynchronize(c->s_out); }
@@ -1202,14 +1199,14 @@ struct DevScan {
 
 // The kernels of a timed phase are enqueued by `enqueue`; waits for them
 template <class F>
-int timed_phase(zpaqhip_ctx *c, hipStream_t stream, DevScan &S, zpaqhip_err *err, F enqueue) {
+int timed_phase(zpaqhip_ctx *c, hipStream_t stream, float &total_ms, zpaqhip_err *err, F enqueue) {
   HIPCHK(hipEventRecord(c->ev0, stream));
   if (int rc = enqueue()) return rc;
   HIPCHK(hipEventRecord(c->ev1, stream));
   HIPCHK(hipStreamSynchronize(stream));
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  S.ms += ms;
+  total_ms += ms;
   return ZPAQHIP_OK;
 }
 
@@ -1222,7 +1219,7 @@ int scan_device_chain(zpaqhip_ctx *c, const uint8_t *d_in, size_t n, hipStream_t
   uint64_t *d_cnt = (uint64_t *)c->scan_cnt.p, *d_total = d_cnt + 3 * np;
   ZhScanResult *d_res = (ZhScanResult *)(d_total + 8);
   uint64_t total[3] = {0, 0, 0};
-  int rc = timed_phase(c, stream, S, err, [&]() -> int {
+  int rc = timed_phase(c, stream, S.ms, err, [&]() -> int {
     HIPCHK(zh_launch_scan_count(d_in, n, d_cnt, d_total, stream));
     HIPCHK(hipMemcpyAsync(total, d_total, sizeof total, hipMemcpyDeviceToHost, stream));
     return ZPAQHIP_OK;
@@ -1238,7 +1235,7 @@ int scan_device_chain(zpaqhip_ctx *c, const uint8_t *d_in, size_t n, hipStream_t
   for (int pass = 0; pass < 2; ++pass) {                // (a second time only for more blocks than tag hits and a few: bare "zPQ" blocks)
     const uint64_t cap = pass ? S.R.n_blocks : n_tag + 64;
     HIPCHK(c->scan_blk.reserve((size_t)cap * sizeof(zpaqhip_block) + 16));
-    rc = timed_phase(c, stream, S, err, [&]() -> int {
+    rc = timed_phase(c, stream, S.ms, err, [&]() -> int {
       if (!pass) {
         HIPCHK(zh_launch_scan_fill(d_in, n, d_cnt, d_tag, d_tag + n_tag, d_tag + n_tag + n_run, n_tag, n_run, stream));
         HIPCHK(zh_launch_scan_parse(d_in, n, &S.L, (ZhScanRec *)c->scan_rec.p, stream));
@@ -1261,7 +1258,7 @@ int scan_device_tables(zpaqhip_ctx *c, const uint8_t *d_in, size_t n, hipStream_
   const uint64_t nb = S.R.n_blocks, ns = S.R.n_segs;
   if (!nb) return ZPAQHIP_OK;
   HIPCHK(c->scan_seg.reserve((size_t)ns * sizeof(zpaqhip_segment) + 16));
-  return timed_phase(c, stream, S, err, [&]() -> int {
+  return timed_phase(c, stream, S.ms, err, [&]() -> int {
     HIPCHK(zh_launch_scan_segments(d_in, n, &S.L, (const zpaqhip_block *)c->scan_blk.p, nb, (zpaqhip_segment *)c->scan_seg.p, ns, stream));
     ++S.launches;
     HIPCHK(hipMemcpyAsync(blocks, c->scan_blk.p, (size_t)nb * sizeof(zpaqhip_block), hipMemcpyDeviceToHost, stream));
@@ -1272,6 +1269,32 @@ int scan_device_tables(zpaqhip_ctx *c, const uint8_t *d_in, size_t n, hipStream_
 
 void scan_device_err(const DevScan &S, zpaqhip_err *e) {
   set_err(e, S.R.status, S.R.err_block, S.R.err_seg, zh_scan_message(S.R.msg));
+}
+
+// zh_frame.hip over entries without head and tail: bodies from staging (FIRST), the second-pass buffer (REDO) or d_out
+// (INPUT), copied to `dst`
+int pack_bodies(zpaqhip_ctx *c, hipStream_t stream, const std::vector<ZhFrameEntry> &tab, const uint8_t *d_out, uint8_t *dst, float &ms,
+                uint32_t &launches, zpaqhip_err *err) {
+  if (tab.empty()) return ZPAQHIP_OK;
+  const size_t tb = tab.size() * sizeof(ZhFrameEntry);
+  HIPCHK(c->pack_tab.reserve(tb + 32));
+  HIPCHK(hipMemcpyAsync(c->pack_tab.p, tab.data(), tb, hipMemcpyHostToDevice, stream));
+  ZhFrameLaunch L;
+  memset(&L, 0, sizeof L);
+  L.table = (const ZhFrameEntry *)c->pack_tab.p;
+  L.blob = (const uint8_t *)c->pack_tab.p + tb;
+  L.src[ZH_FRAME_SRC_FIRST] = (const uint8_t *)c->out2[0].p;
+  L.src[ZH_FRAME_SRC_REDO] = (const uint8_t *)c->out_fix[0].p;
+  L.src[ZH_FRAME_SRC_INPUT] = d_out;
+  L.out = dst;
+  L.n = (uint32_t)tab.size();
+  uint64_t longest = 0;
+  for (const ZhFrameEntry &e : tab) longest = std::max(longest, e.body_len);
+  L.pieces = (uint32_t)std::max<uint64_t>(1, (longest + ZH_FRAME_PIECE - 1) / ZH_FRAME_PIECE);
+  return timed_phase(c, stream, ms, err, [&]() -> int {
+    HIPCHK(zh_launch_frame_pack(&L, stream, &launches));
+    return ZPAQHIP_OK;
+  });
 }
 
 bool device_stream_ok(const void *d_in, size_t in_len) { return (d_in || !in_len) && ((uintptr_t)d_in & 3u) == 0; }
@@ -1320,245 +1343,101 @@ extern "C" int zpaqhip_decompress_device(zpaqhip_ctx *c, const void *d_in, size_
   *out_len = 0;
   if (n_results) *n_results = 0;
 
-  // ---- the tables
+  // ---- scan: the tables, and what ends the stream behind the last good block
   DevScan S;
   if (int rc = scan_device_chain(c, in, in_len, stream, S, err)) return rc;
-  std::vector<zpaqhip_block> blocks((size_t)S.R.n_blocks);
-  std::vector<zpaqhip_segment> segs((size_t)S.R.n_segs);
-  if (int rc = scan_device_tables(c, in, in_len, stream, S, blocks.data(), segs.data(), err)) return rc;
-  int after_rc = S.R.status;                            // what ends the stream behind the last good block
+  DevPlan p;
+  p.blocks.resize((size_t)S.R.n_blocks);
+  p.segs.resize((size_t)S.R.n_segs);
+  if (int rc = scan_device_tables(c, in, in_len, stream, S, p.blocks.data(), p.segs.data(), err)) return rc;
+  int after_rc = S.R.status;
   zpaqhip_err after_err{};
   if (after_rc) scan_device_err(S, &after_err);
   zpaqhip_stats acc{};
   acc.kernel_ms = acc.init_ms = S.ms;
   acc.launches = S.launches;
-  size_t nb = blocks.size();
-  {
-    // a header the scan accepts can still be refused when the model is built: the stream ends in front of the first such
-    // block, with its error (cut_at_bad_model, zh_stream_plan.h)
-    std::map<std::string, int> seen;
-    std::vector<uint8_t> hdr, code;
-    for (size_t b = 0; b < nb; ++b) {
-      hdr.resize(blocks[b].hdr_len);
-      HIPCHK(hipMemcpyAsync(hdr.data(), in + blocks[b].hdr_off, hdr.size(), hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      std::string key((const char *)hdr.data(), hdr.size());
-      auto it = seen.find(key);
-      if (it != seen.end() && !it->second) continue;
-      ZhModel m;
-      zpaqhip_err e2{};
-      code.clear();
-      const int mrc = build_model(hdr.data(), hdr.size(), m, code, &e2);
-      seen[key] = mrc;
-      if (!mrc) continue;
-      e2.block = (int32_t)b; e2.segment = -1;
-      after_rc = mrc; after_err = e2; nb = b;
-      break;
-    }
-  }
-  const size_t ns = nb ? blocks[nb - 1].first_seg + blocks[nb - 1].n_seg : 0;
 
-  // ---- first decode: the blocks in front of the first one without a plausible size straight to their place (what lies
-  // behind out_cap counted, not written), the rest to staging slots
-  std::vector<zpaqhip_seg_result> res(segs.size());
-  std::vector<uint64_t> place(nb + 1, 0), cap(nb, 0), real(nb, 0), at(nb, 0);   // at: where the block lies in its buffer
-  enum Where : uint8_t { kPlace, kStaged, kMoved, kFix };
-  std::vector<uint8_t> where(nb, kPlace);
-  size_t k = 0;
-  while (k < nb && plausible_hint(blocks[k].usize_hint)) { place[k + 1] = place[k] + blocks[k].usize_hint; ++k; }
-  size_t limit = nb;                                    // the first block with a data error: nothing from it on is delivered
-  int bad_rc = ZPAQHIP_OK;
-  zpaqhip_err bad_err{};
+  // ---- cut in front of the first block whose model is refused.  (One copy and one wait per header, as ever: fetching
+  // all headers in one copy is a change of speed, not of shape, and is left to a change of its own.)
+  ModelCut cut;
+  std::vector<uint8_t> hdr;
+  const int cut_rc = first_bad_model(p.blocks, [&](size_t b, const uint8_t *&h) -> int {
+    hdr.resize(p.blocks[b].hdr_len);
+    HIPCHK(hipMemcpyAsync(hdr.data(), in + p.blocks[b].hdr_off, hdr.size(), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    h = hdr.data();
+    return ZPAQHIP_OK;
+  }, cut);
+  if (cut_rc) return cut_rc;
+  if (cut.rc) { after_rc = cut.rc; after_err = cut.err; }
+  p.cut(cut.nb);
+
   bool first_time = true;
-  // decodes blocks `ids` to base + off[i], at most cp[i] bytes; notes their plaintext sizes and the first failure
-  auto decode = [&](const std::vector<uint32_t> &ids, void *base, const std::vector<uint64_t> &off, const std::vector<uint64_t> &cp) -> int {
-    if (ids.empty()) return ZPAQHIP_OK;
+  auto decode = [&](const DevDecode &d, void *to) -> int {
+    if (d.ids.empty()) return ZPAQHIP_OK;
     zh_pending P;
     zpaqhip_err e2{};
-    int rc = decode_launch(c, in, nullptr, in_len, blocks.data(), nb, segs.data(), ns, ids.data(), ids.size(), base, off.data(),
-                           cp.data(), opts, stream, P, &e2);
-    if (!rc) rc = decode_finish(c, P, res.data(), &e2);
+    int rc = decode_launch(c, in, nullptr, in_len, p.blocks.data(), p.blocks.size(), p.segs.data(), p.segs.size(), d.ids.data(), d.ids.size(),
+                           to, d.off.data(), d.cap.data(), opts, stream, P, &e2);
+    if (!rc) rc = decode_finish(c, P, p.res.data(), &e2);
     add_kernel_stats(acc, c->stats);
     if (first_time) add_block_stats(acc, c->stats);
     if (rc && !data_error(rc)) { if (err) *err = e2; return rc; }
-    for (uint32_t b : ids) {
-      real[b] = 0;
-      for (uint32_t i = 0; i < blocks[b].n_seg; ++i) real[b] += res[blocks[b].first_seg + i].out_len;
-    }
+    note_decoded(p, d.ids);
     return ZPAQHIP_OK;
   };
-  auto note_failures = [&]() {                          // the lowest block with a segment that failed
-    for (size_t b = 0; b < limit; ++b)
-      for (uint32_t i = 0; i < blocks[b].n_seg; ++i) {
-        const int st = res[blocks[b].first_seg + i].status;
-        if (st == ZPAQHIP_OK || st == ZPAQHIP_E_OUTPUT_FULL) continue;
-        limit = b;
-        bad_rc = st == ZH_E_SKIPPED ? ZPAQHIP_E_CORRUPT : st;
-        set_err(&bad_err, bad_rc, (int)b, (int)(blocks[b].first_seg + i));
-        return;
-      }
+  float pack_ms = 0;
+  uint32_t pack_launches = 0;
+  auto pack = [&](const std::vector<ZhFrameEntry> &tab, void *to) {
+    return pack_bodies(c, stream, tab, (const uint8_t *)d_out, (uint8_t *)to, pack_ms, pack_launches, err);
   };
-  std::vector<uint32_t> ids;
-  std::vector<uint64_t> off, cp;
-  for (size_t b = 0; b < k; ++b) {
-    ids.push_back((uint32_t)b);
-    off.push_back(place[b]);
-    cap[b] = place[b] >= out_cap ? 0 : std::min<uint64_t>(blocks[b].usize_hint, out_cap - place[b]);
-    cp.push_back(cap[b]);
-    at[b] = place[b];
-  }
-  if (int rc = decode(ids, d_out, off, cp)) return rc;
-  note_failures();
-  if (limit > k) {                                      // staging for the rest
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    free_b += c->out2[0].cap;
-    std::vector<zpaqhip_block> rest(blocks.begin() + (ptrdiff_t)k, blocks.begin() + (ptrdiff_t)nb);
-    std::vector<uint64_t> rcap, roff;
-    const uint64_t bytes = plan_slots(rest, segs, free_b / 4 / std::max(1u, c->mem_share), rcap, roff);
-    if (c->out2[0].reserve((size_t)bytes + 16) != hipSuccess) {   // not even that: everything count-only, exact second pass
-      (void)hipGetLastError();
-      std::fill(rcap.begin(), rcap.end(), 0ull);
-      std::fill(roff.begin(), roff.end(), 0ull);
-      HIPCHK(c->out2[0].reserve(16));
-    }
-    ids.clear();
-    for (size_t b = k; b < nb; ++b) { ids.push_back((uint32_t)b); cap[b] = rcap[b - k]; at[b] = roff[b - k]; where[b] = kStaged; }
-    if (int rc = decode(ids, c->out2[0].p, roff, rcap)) return rc;
-    note_failures();
+
+  // ---- first decode: straight to d_out what has a place there, the rest to staging
+  if (int rc = decode(plan_direct(p, out_cap), d_out)) return rc;
+  if (p.bad.limit > p.k) {
+    const std::vector<zpaqhip_block> rest(p.blocks.begin() + (ptrdiff_t)p.k, p.blocks.end());
+    std::vector<uint64_t> cap, off;
+    if (int rc = plan_staging(c, 0, c->out2[0].cap, rest, p.segs, cap, off, err)) return rc;
+    if (int rc = decode(plan_staged(p, cap, off), c->out2[0].p)) return rc;
   }
   first_time = false;
 
-  // ---- a size comment that was wrong: the first such block keeps its place when it is shorter, everything behind it moves
-  size_t wrong = k;
-  for (size_t b = 0; b < k && b < limit; ++b)
-    if (real[b] != blocks[b].usize_hint) { wrong = b; break; }
-  // second decode, with the exact size, of every block that outgrew its slot (a block is decoded twice at most)
-  ids.clear(); off.clear(); cp.clear();
-  uint64_t fix_bytes = 0;
-  std::vector<ZhFrameEntry> move;                        // blocks decoded to a wrong place that are whole: out of the way first
-  for (size_t b = 0; b < limit; ++b) {
-    if (real[b] > cap[b]) {
-      ids.push_back((uint32_t)b); off.push_back(fix_bytes); cp.push_back(real[b]);
-      where[b] = kFix; at[b] = fix_bytes; cap[b] = real[b];
-    } else if (b < k && b > wrong) {
-      ZhFrameEntry e{};
-      e.dst_off = fix_bytes; e.src_off = place[b]; e.body_len = real[b]; e.src = ZH_FRAME_SRC_INPUT;
-      if (real[b]) move.push_back(e);
-      where[b] = kMoved; at[b] = fix_bytes;
-    } else continue;
-    fix_bytes += real[b];
-  }
-  float pack_ms = 0;
-  uint32_t pack_launches = 0;
-  // zh_frame.hip over entries without head and tail: bodies from staging (FIRST), the second-pass buffer (REDO) or d_out (INPUT)
-  auto pack = [&](const std::vector<ZhFrameEntry> &tab, uint8_t *dst) -> int {
-    if (tab.empty()) return ZPAQHIP_OK;
-    const size_t tb = tab.size() * sizeof(ZhFrameEntry);
-    HIPCHK(c->pack_tab.reserve(tb + 32));
-    HIPCHK(hipMemcpyAsync(c->pack_tab.p, tab.data(), tb, hipMemcpyHostToDevice, stream));
-    ZhFrameLaunch L;
-    memset(&L, 0, sizeof L);
-    L.table = (const ZhFrameEntry *)c->pack_tab.p;
-    L.blob = (const uint8_t *)c->pack_tab.p + tb;
-    L.src[ZH_FRAME_SRC_FIRST] = (const uint8_t *)c->out2[0].p;
-    L.src[ZH_FRAME_SRC_REDO] = (const uint8_t *)c->out_fix[0].p;
-    L.src[ZH_FRAME_SRC_INPUT] = (const uint8_t *)d_out;
-    L.out = dst;
-    L.n = (uint32_t)tab.size();
-    uint64_t longest = 0;
-    for (const ZhFrameEntry &e : tab) longest = std::max(longest, e.body_len);
-    L.pieces = (uint32_t)std::max<uint64_t>(1, (longest + ZH_FRAME_PIECE - 1) / ZH_FRAME_PIECE);
-    HIPCHK(hipEventRecord(c->ev0, stream));
-    HIPCHK(zh_launch_frame_pack(&L, stream, &pack_launches));
-    HIPCHK(hipEventRecord(c->ev1, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    pack_ms += ms;
-    return ZPAQHIP_OK;
-  };
-  if (fix_bytes) HIPCHK(c->out_fix[0].reserve((size_t)fix_bytes + 16));
-  if (int rc = pack(move, (uint8_t *)c->out_fix[0].p)) return rc;
-  if (int rc = decode(ids, c->out_fix[0].p, off, cp)) return rc;
-  note_failures();
+  // ---- second decode: whole blocks in a wrong place out of the way, then what outgrew its room with its exact size
+  const DevSecond second = plan_device_second(p);
+  if (second.fix_bytes) HIPCHK(c->out_fix[0].reserve((size_t)second.fix_bytes + 16));
+  if (int rc = pack(second.move, c->out_fix[0].p)) return rc;
+  if (int rc = decode(second.redo, c->out_fix[0].p)) return rc;
 
   // ---- checksums, on the device, where the plaintext lies
-  auto base_of = [&](size_t b) -> const uint8_t * {
-    return where[b] == kPlace ? (const uint8_t *)d_out : where[b] == kStaged ? (const uint8_t *)c->out2[0].p : (const uint8_t *)c->out_fix[0].p;
-  };
-  // a moved block's results still speak of its first place
-  auto seg_at = [&](size_t b, size_t s) { return where[b] == kMoved ? at[b] + (res[s].out_off - place[b]) : res[s].out_off; };
   if (opts.verify_sha1) {
-    for (int w = 0; w < 3; ++w) {                       // d_out, staging, second-pass buffer
-      std::vector<uint64_t> tab;
-      std::vector<uint32_t> which;
-      const uint8_t *base = nullptr;
-      for (size_t b = 0; b < limit; ++b) {
-        if ((where[b] == kPlace ? 0 : where[b] == kStaged ? 1 : 2) != w) continue;
-        base = base_of(b);
-        for (uint32_t i = 0; i < blocks[b].n_seg; ++i) {
-          const size_t s = blocks[b].first_seg + i;
-          if (!(segs[s].flags & 1) || res[s].status != ZPAQHIP_OK) continue;
-          tab.push_back(seg_at(b, s)); tab.push_back(res[s].out_len); which.push_back((uint32_t)s);
-        }
-      }
-      if (which.empty()) continue;
-      const size_t tab_bytes = tab.size() * 8, dig_bytes = which.size() * 20;
-      HIPCHK(c->sdesc.reserve(tab_bytes + dig_bytes + 64));
-      uint8_t *d_tab = (uint8_t *)c->sdesc.p, *d_dig = d_tab + ((tab_bytes + 15) & ~(size_t)15);
-      HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, stream));
-      HIPCHK(zh_launch_sha1(base, (const uint64_t *)d_tab, (uint32_t)which.size(), (uint32_t *)d_dig, stream));
-      std::vector<uint32_t> dig(which.size() * 5);
-      HIPCHK(hipMemcpyAsync(dig.data(), d_dig, dig_bytes, hipMemcpyDeviceToHost, stream));
-      HIPCHK(hipStreamSynchronize(stream));
-      for (size_t j = 0; j < which.size(); ++j) {
-        uint8_t d[20];
-        for (int i = 0; i < 5; ++i) {
-          const uint32_t v = dig[5 * j + i];
-          d[4 * i] = (uint8_t)(v >> 24); d[4 * i + 1] = (uint8_t)(v >> 16); d[4 * i + 2] = (uint8_t)(v >> 8); d[4 * i + 3] = (uint8_t)v;
-        }
-        if (memcmp(d, segs[which[j]].sha1, 20) != 0) res[which[j]].status = ZPAQHIP_E_SHA1;
-      }
+    const uint8_t *const base[3] = {(const uint8_t *)d_out, (const uint8_t *)c->out2[0].p, (const uint8_t *)c->out_fix[0].p};
+    for (DevWhere w : {DevWhere::kOut, DevWhere::kStaging, DevWhere::kFix}) {
+      std::vector<uint32_t> bad;
+      if (int rc = sha1_check(c, stream, base[(int)w], device_sha1_table(p, w), p.segs.data(), bad, err)) return rc;
+      for (uint32_t s : bad) p.res[s].status = ZPAQHIP_E_SHA1;
     }
-    note_failures();
+    lowest_failed_block(p.blocks, p.res, p.bad);
   }
 
-  // ---- every delivered block that is not in its place yet gathered there in one launch, clipped at out_cap
-  std::vector<uint64_t> dst(limit + 1, 0);
-  for (size_t b = 0; b < limit; ++b) dst[b + 1] = dst[b] + real[b];
-  std::vector<ZhFrameEntry> gather;
-  for (size_t b = 0; b < limit; ++b) {
-    if (where[b] == kPlace || !real[b] || dst[b] >= out_cap) continue;
-    ZhFrameEntry e{};
-    e.dst_off = dst[b]; e.src_off = at[b]; e.body_len = std::min<uint64_t>(real[b], out_cap - dst[b]);
-    e.src = where[b] == kStaged ? ZH_FRAME_SRC_FIRST : ZH_FRAME_SRC_REDO;
-    gather.push_back(e);
-  }
-  if (int rc = pack(gather, (uint8_t *)d_out)) return rc;
-  *out_len = (size_t)dst[limit];
+  // ---- gather: every delivered block that is not in its place yet, in one launch
+  const DevGather g = plan_gather(p, out_cap);
+  if (int rc = pack(g.entries, d_out)) return rc;
+  *out_len = (size_t)g.out_len();
 
-  // ---- per-segment outcomes (optional), out_off in stream order
-  const size_t n_res = limit < nb ? blocks[limit].first_seg + blocks[limit].n_seg : ns;
+  // ---- report
+  const size_t n_res = device_result_count(p);
   if (n_results) *n_results = n_res;
-  memset(&c->stats, 0, sizeof c->stats);
   c->stats = acc;
   c->stats.kernel_ms += pack_ms;
   c->stats.launches += pack_launches;
-  c->stats.out_bytes = dst[limit];
+  c->stats.out_bytes = g.out_len();
   if (results || result_cap) {
     if (n_res > result_cap) { set_err(err, ZPAQHIP_E_ARG, -1, -1, "result table too small"); return ZPAQHIP_E_ARG; }
-    for (size_t b = 0; b < nb && b <= limit; ++b)
-      for (uint32_t i = 0; i < blocks[b].n_seg; ++i) {
-        const size_t s = blocks[b].first_seg + i;
-        zpaqhip_seg_result r = res[s];
-        if (b < limit) r.out_off = dst[b] + (seg_at(b, s) - at[b]);
-        results[s] = r;
-      }
+    device_results(p, g, results);
   }
-  if (bad_rc) { if (err) *err = bad_err; return bad_rc; }
+  if (p.bad.rc) { if (err) *err = p.bad.err; return p.bad.rc; }
   if (after_rc) { if (err) *err = after_err; return after_rc; }
-  if (dst[limit] > out_cap) { set_err(err, ZPAQHIP_E_OUTPUT_FULL, -1, -1); return ZPAQHIP_E_OUTPUT_FULL; }
+  if (g.out_len() > out_cap) { set_err(err, ZPAQHIP_E_OUTPUT_FULL, -1, -1); return ZPAQHIP_E_OUTPUT_FULL; }
   return ZPAQHIP_OK;
 }
 

@@ -1,8 +1,10 @@
 // zh_stream_plan.h — the rules of the whole-stream forms: how a stream is cut into batches, where a batch's blocks are staged,
 // which blocks are decoded a second time, what is delivered where, and how zpaqhip_decompress_multi queues, places and
-// settles its blocks.  Host C++ only (no HIP): zh_api.cpp's pipeline enqueues what these functions decide,
-// tests/native/stream_plan_main.cpp runs them without a GPU.  Every rule here reads untrusted input (a comment's text as a
-// size, a truncated stream, a caller's out_cap) and decides where bytes are written.
+// settles its blocks; and the rules of zpaqhip_decompress_device, the form whose stream and output both lie in device
+// memory: what is decoded straight to its place, what is staged, moved, decoded again and gathered.  Host C++ only (no
+// HIP): zh_api.cpp's drivers enqueue what these functions decide, tests/native/stream_plan_main.cpp runs them without a
+// GPU.  Every rule here reads untrusted input (a comment's text as a size, a truncated stream, a caller's out_cap) and
+// decides where bytes are written.
 #pragma once
 #include <string.h>
 
@@ -12,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "zh_frame.h"
 #include "zh_host.h"
 
 namespace zh {
@@ -67,32 +70,44 @@ struct Batch {
 
 // A header the framing scan accepts can still be refused when the model is built (component limits, table sizes:
 // Predictor.cs:94-167).  The reference raises that at the block's Predictor.init, after everything before the block has
-// been written; so the batch is cut in front of the first such block and the error is reported behind the cut.
-inline void cut_at_bad_model(Batch &bt) {
+// been written; so the stream is cut in front of the first such block and the error is reported behind the cut.
+// `header(b, p)` points p at block b's header bytes (valid until its next call) or returns the error of the call.
+struct ModelCut {
+  size_t nb = 0;                          // the blocks in front of the cut
+  int rc = ZPAQHIP_OK;                    // what build_model says of block nb, with its message; OK: no cut
+  zpaqhip_err err{};
+};
+template <class Header>
+inline int first_bad_model(const std::vector<zpaqhip_block> &blocks, Header header, ModelCut &cut) {
   std::map<std::string, int> seen;
-  for (size_t b = 0; b < bt.so.blocks.size(); ++b) {
-    const zpaqhip_block &B = bt.so.blocks[b];
-    std::string key((const char *)bt.h + B.hdr_off, B.hdr_len);
-    auto it = seen.find(key);
+  for (cut.nb = 0; cut.nb < blocks.size(); ++cut.nb) {
+    const uint32_t len = blocks[cut.nb].hdr_len;
+    const uint8_t *h = nullptr;
+    if (int rc = header(cut.nb, h)) return rc;
+    const std::string key((const char *)h, len);
+    const auto it = seen.find(key);
+    if (it != seen.end() && !it->second) continue;
+    ZhModel m;
+    std::vector<uint8_t> code;
     zpaqhip_err e2{};
-    if (it == seen.end()) {
-      ZhModel m;
-      std::vector<uint8_t> code;
-      it = seen.emplace(key, build_model(bt.h + B.hdr_off, B.hdr_len, m, code, &e2)).first;
-    } else if (it->second) {
-      ZhModel m;
-      std::vector<uint8_t> code;
-      (void)build_model(bt.h + B.hdr_off, B.hdr_len, m, code, &e2);     // (again, for the message)
-    }
-    if (!it->second) continue;
-    e2.block = (int32_t)b; e2.segment = -1;
-    bt.rc_after = it->second; bt.err_after = e2; bt.last = true;
-    bt.so.blocks.resize(b);
-    bt.so.segs.resize(b ? bt.so.blocks.back().first_seg + bt.so.blocks.back().n_seg : 0);
-    bt.so.stopped = false;
-    bt.len = b ? (size_t)bt.so.blocks.back().end_off : 0;
-    return;
+    cut.rc = seen[key] = build_model(h, len, m, code, &e2);             // (a bad header seen before: again, for the message)
+    if (!cut.rc) continue;
+    e2.block = (int32_t)cut.nb; e2.segment = -1;
+    cut.err = e2;
+    break;
   }
+  return ZPAQHIP_OK;
+}
+inline void cut_at_bad_model(Batch &bt) {
+  ModelCut cut;
+  (void)first_bad_model(bt.so.blocks, [&](size_t b, const uint8_t *&p) { p = bt.h + bt.so.blocks[b].hdr_off; return ZPAQHIP_OK; }, cut);
+  if (!cut.rc) return;
+  const size_t b = cut.nb;
+  bt.rc_after = cut.rc; bt.err_after = cut.err; bt.last = true;
+  bt.so.blocks.resize(b);
+  bt.so.segs.resize(b ? bt.so.blocks.back().first_seg + bt.so.blocks.back().n_seg : 0);
+  bt.so.stopped = false;
+  bt.len = b ? (size_t)bt.so.blocks.back().end_off : 0;
 }
 
 // Next batch of whole blocks, or batch.so.blocks.empty() at the end of the stream.  Returns a call-level error only.
@@ -178,6 +193,11 @@ inline uint64_t plan_slots(const std::vector<zpaqhip_block> &blocks, const std::
   for (size_t b = 0; b < nb; ++b) { off[b] = pos; pos += cap[b]; }
   return pos;
 }
+// ... and when not even that can be reserved: every slot count-only, an exact second pass for every block
+inline void count_only_slots(std::vector<uint64_t> &cap, std::vector<uint64_t> &off) {
+  std::fill(cap.begin(), cap.end(), 0ull);
+  std::fill(off.begin(), off.end(), 0ull);
+}
 
 // ---- second pass: plaintext sizes of a decoded batch (bt.real), and the blocks that did not fit their staging slot with
 // their exact layout in a buffer of their own
@@ -230,6 +250,25 @@ inline FirstBad first_failure(const Batch &B) {
     }
   }
   return f;
+}
+// ... and the lowest block below f.limit with a failed segment, for zpaqhip_decompress_device.  Not first_failure: there
+// ZPAQHIP_E_OUTPUT_FULL is a failure and the bytes in front of the failed segment are delivered; here a block that was
+// clipped is decoded again, and whole blocks only are delivered.  Block and segment are the stream's.
+struct FailedBlock {
+  size_t limit = 0;                       // nothing from this block on is delivered
+  int rc = ZPAQHIP_OK;
+  zpaqhip_err err{};
+};
+inline void lowest_failed_block(const std::vector<zpaqhip_block> &blocks, const std::vector<zpaqhip_seg_result> &res, FailedBlock &f) {
+  for (size_t b = 0; b < f.limit; ++b)
+    for (uint32_t i = 0; i < blocks[b].n_seg; ++i) {
+      const int st = res[blocks[b].first_seg + i].status;
+      if (st == ZPAQHIP_OK || st == ZPAQHIP_E_OUTPUT_FULL) continue;
+      f.limit = b;
+      f.rc = st == ZH_E_SKIPPED ? ZPAQHIP_E_CORRUPT : st;
+      set_err(&f.err, f.rc, (int)b, (int)(blocks[b].first_seg + i));
+      return;
+    }
 }
 
 // ---- zpaqhip_decompress_segments: per-segment records in stream order
@@ -414,6 +453,162 @@ inline int settle_places(uint8_t *out, size_t out_cap, size_t limit, const std::
   for (size_t b = 0; b < limit; ++b)
     if (!spill[b].empty()) memcpy(out + new_off[b], spill[b].data(), (size_t)real[b]);
   return ZPAQHIP_OK;
+}
+
+// ---- zpaqhip_decompress_device: stream and plaintext both in device memory, one batch, no copy to the host.  The
+// blocks in front of the first one without a plausible size are decoded straight to d_out, the rest to staging slots; a
+// block that outgrew its room is decoded again with its exact size; one gather puts everything in place.
+enum class DevWhere : uint8_t { kOut, kStaging, kFix };     // the caller's d_out, the staging buffer, the second-pass buffer
+inline uint32_t frame_src(DevWhere w) {                     // ... as zh_frame.hip's entries name them
+  return w == DevWhere::kOut ? ZH_FRAME_SRC_INPUT : w == DevWhere::kStaging ? ZH_FRAME_SRC_FIRST : ZH_FRAME_SRC_REDO;
+}
+// Where a block lies.  (Batch::off | kInFix does not carry this: its one bit tells two buffers apart and here are three, and
+// a moved block's segment records keep speaking of the place it was decoded to.)
+struct DevBlock {
+  DevWhere buf = DevWhere::kOut;
+  uint64_t off = 0;                       // of the block in buf
+  uint64_t rec_off = 0;                   // the offset its segment records count from: off, or for a moved block its first place
+  uint64_t cap = 0, real = 0;             // room it was decoded with / plaintext length
+};
+struct DevDecode {                        // one decode launch: blocks ids[i] to base + off[i], at most cap[i] bytes
+  std::vector<uint32_t> ids;
+  std::vector<uint64_t> off, cap;
+  void add(size_t b, uint64_t o, uint64_t c) { ids.push_back((uint32_t)b); off.push_back(o); cap.push_back(c); }
+};
+struct DevPlan {
+  std::vector<zpaqhip_block> blocks;      // the stream's tables, cut in front of the first block whose model is refused
+  std::vector<zpaqhip_segment> segs;
+  std::vector<zpaqhip_seg_result> res;    // per segment, as the last decode of its block left it
+  std::vector<DevBlock> at;
+  size_t k = 0;                           // blocks [0, k) went straight to d_out
+  FailedBlock bad;
+  void cut(size_t nb) {
+    blocks.resize(nb);
+    segs.resize(nb ? blocks[nb - 1].first_seg + blocks[nb - 1].n_seg : 0);
+    res.assign(segs.size(), zpaqhip_seg_result{});
+    at.assign(nb, DevBlock{});
+    bad.limit = nb;
+  }
+};
+
+// Direct phase: every leading block with a plausible size at the sum of the sizes before it; what lies behind out_cap is
+// counted, not written (capacity clipped at out_cap, 0 at or beyond it).
+inline DevDecode plan_direct(DevPlan &p, uint64_t out_cap) {
+  DevDecode d;
+  uint64_t place = 0;
+  for (p.k = 0; p.k < p.blocks.size() && plausible_hint(p.blocks[p.k].usize_hint); ++p.k) {
+    const uint64_t hint = p.blocks[p.k].usize_hint;
+    DevBlock &B = p.at[p.k];
+    B.buf = DevWhere::kOut; B.off = B.rec_off = place;
+    B.cap = place >= out_cap ? 0 : std::min<uint64_t>(hint, out_cap - place);
+    d.add(p.k, place, B.cap);
+    place += hint;
+  }
+  return d;
+}
+// Staging phase: blocks [k, nb) in the slots plan_slots gave blocks.begin() + k ...
+inline DevDecode plan_staged(DevPlan &p, const std::vector<uint64_t> &cap, const std::vector<uint64_t> &off) {
+  DevDecode d;
+  for (size_t b = p.k; b < p.blocks.size(); ++b) {
+    DevBlock &B = p.at[b];
+    B.buf = DevWhere::kStaging; B.off = B.rec_off = off[b - p.k]; B.cap = cap[b - p.k];
+    d.add(b, B.off, B.cap);
+  }
+  return d;
+}
+// After a decode: the plaintext sizes of its blocks (segments count past the capacity), and the lowest failed block
+inline void note_decoded(DevPlan &p, const std::vector<uint32_t> &ids) {
+  for (uint32_t b : ids) {
+    p.at[b].real = 0;
+    for (uint32_t i = 0; i < p.blocks[b].n_seg; ++i) p.at[b].real += p.res[p.blocks[b].first_seg + i].out_len;
+  }
+  lowest_failed_block(p.blocks, p.res, p.bad);
+}
+
+// After the first decode.  A size comment that was wrong: the first such block keeps its place when it is shorter,
+// every directly placed block behind it is whole but in the wrong place, and is moved out of the way (d_out to the
+// second-pass buffer) before anything is gathered.  Every block that outgrew its room is decoded a second time, with its
+// exact size, into the same buffer (a block is decoded twice at most).
+struct DevSecond {
+  DevDecode redo;
+  std::vector<ZhFrameEntry> move;
+  uint64_t fix_bytes = 0;                 // of the second-pass buffer
+};
+inline DevSecond plan_device_second(DevPlan &p) {
+  DevSecond s;
+  size_t wrong = p.k;
+  for (size_t b = 0; b < p.k && b < p.bad.limit; ++b)
+    if (p.at[b].real != p.blocks[b].usize_hint) { wrong = b; break; }
+  for (size_t b = 0; b < p.bad.limit; ++b) {
+    DevBlock &B = p.at[b];
+    if (B.real > B.cap) {
+      s.redo.add(b, s.fix_bytes, B.real);
+      B.off = B.rec_off = s.fix_bytes; B.cap = B.real;
+    } else if (b < p.k && b > wrong) {
+      ZhFrameEntry e{};
+      e.dst_off = s.fix_bytes; e.src_off = B.off; e.body_len = B.real; e.src = frame_src(DevWhere::kOut);
+      if (B.real) s.move.push_back(e);
+      B.off = s.fix_bytes;
+    } else continue;
+    B.buf = DevWhere::kFix;
+    s.fix_bytes += B.real;
+  }
+  return s;
+}
+
+// Checksums: the (offset, length) pairs of buffer w's segments that store a SHA-1 and decoded without an error
+struct Sha1Table {
+  std::vector<uint64_t> pairs;
+  std::vector<uint32_t> which;            // pair j is segment which[j]
+  void add(const zpaqhip_segment &g, const zpaqhip_seg_result &r, size_t s, uint64_t off) {
+    if (!(g.flags & 1) || r.status != ZPAQHIP_OK) return;
+    pairs.push_back(off); pairs.push_back(r.out_len); which.push_back((uint32_t)s);
+  }
+};
+inline Sha1Table device_sha1_table(const DevPlan &p, DevWhere w) {
+  Sha1Table t;
+  for (size_t b = 0; b < p.bad.limit; ++b) {
+    if (p.at[b].buf != w) continue;
+    for (uint32_t i = 0; i < p.blocks[b].n_seg; ++i) {
+      const size_t s = p.blocks[b].first_seg + i;
+      t.add(p.segs[s], p.res[s], s, p.at[b].off + (p.res[s].out_off - p.at[b].rec_off));
+    }
+  }
+  return t;
+}
+
+// Gather: blocks [0, limit) consecutive from d_out; every one that does not lie there already copied in, clipped at out_cap
+struct DevGather {
+  std::vector<uint64_t> dst;              // final offset of block b; dst[limit] = out_len
+  std::vector<ZhFrameEntry> entries;
+  uint64_t out_len() const { return dst.back(); }
+};
+inline DevGather plan_gather(const DevPlan &p, uint64_t out_cap) {
+  DevGather g;
+  g.dst.assign(p.bad.limit + 1, 0);
+  for (size_t b = 0; b < p.bad.limit; ++b) {
+    const DevBlock &B = p.at[b];
+    g.dst[b + 1] = g.dst[b] + B.real;
+    if (B.buf == DevWhere::kOut || !B.real || g.dst[b] >= out_cap) continue;
+    ZhFrameEntry e{};
+    e.dst_off = g.dst[b]; e.src_off = B.off; e.body_len = std::min<uint64_t>(B.real, out_cap - g.dst[b]); e.src = frame_src(B.buf);
+    g.entries.push_back(e);
+  }
+  return g;
+}
+
+// Result records: those of the delivered blocks with out_off in stream order, and the failed block's as they are
+inline size_t device_result_count(const DevPlan &p) {
+  const size_t l = p.bad.limit;
+  return l < p.blocks.size() ? p.blocks[l].first_seg + p.blocks[l].n_seg : p.segs.size();
+}
+inline void device_results(const DevPlan &p, const DevGather &g, zpaqhip_seg_result *results) {
+  for (size_t b = 0; b < p.blocks.size() && b <= p.bad.limit; ++b)
+    for (uint32_t i = 0; i < p.blocks[b].n_seg; ++i) {
+      const size_t s = p.blocks[b].first_seg + i;
+      results[s] = p.res[s];
+      if (b < p.bad.limit) results[s].out_off = g.dst[b] + (p.res[s].out_off - p.at[b].rec_off);
+    }
 }
 
 // ---- statistics: what the sums of the pipeline, the second pass and the multi-device threads have in common

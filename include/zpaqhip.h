@@ -495,6 +495,38 @@ int zpaqhip_compress_method_blocks_device(zpaqhip_ctx *ctx, const int32_t args[9
                                           size_t *out_len, uint64_t *block_off, const zpaqhip_compress_opts *opts,
                                           void *hip_stream, zpaqhip_err *err);
 
+/* ---- solid blocks: several segments per block (Compressor.startSegment .. endSegment, repeated; Compressor.cs:133-248) ------
+ * zpaqhip_compress_blocks[_device] with one more table: block i holds the segments [seg_first[i], seg_first[i + 1]) of the
+ * call, at least one (seg_first[0] == 0; n_segs = seg_first[n_blocks], below 2^32).  in_off, orig_off (with `orig`) and
+ * filenames are then PER SEGMENT: n_segs + 1 offsets, n_segs names; segment s codes in[in_off[s], in_off[s + 1]), its size
+ * comment and SHA-1 describe orig[orig_off[s], orig_off[s + 1]) (NULL = the coded bytes).  block_off[0..n_blocks] stays per
+ * block.  A block is what Compressor writes for
+ *   startBlock(hdr); for each segment: startSegment(filename, size), postProcess(pcomp) (it acts in the first segment only,
+ *   Compressor.cs:158), compress(its bytes), endSegment(sha1 or none); endBlock()
+ * behind the tag (bit1 of opts.flags): the model, the coder's interval and the post-processor's state carry over from a
+ * segment to the next, which is what packing many small files into one block is for.  The caller sees to it that the
+ * segments' coded bytes are what the post-processor turns into their described bytes one after the other.
+ * opts: bits 0 and 1 of flags, kernel, enc_waves, batch_blocks and slot_bytes with the meaning they have for
+ * zpaqhip_compress_blocks; any other bit of flags (the method opt-ins, verify) gives ZPAQHIP_E_ARG.  A block of one segment
+ * takes the encoder it takes there and comes out byte for byte the same.  A block of several segments never takes the
+ * window-parallel CM encoder: with kernel == 2 a single-CM model's goes to the lane-per-component encoder, else to the
+ * generic one.  ZPAQHIP_E_ARG, before the device is touched, also for a block without a segment, seg_first or offsets that
+ * decrease (err.block tells the block, err.segment the segment within it) and an n == 0 header.  zpaqhip_last_stats,
+ * ZPAQHIP_E_OUTPUT_FULL (whole blocks only) and the device form's contract (pointers, stream, alignment, nothing at or past
+ * d_out + out_cap, no plaintext or coded byte over the bus; per segment a digest, an end offset and a table entry
+ * cross it) are those of zpaqhip_compress_blocks and zpaqhip_compress_blocks_device. */
+int zpaqhip_compress_solid_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
+                                  const uint8_t *in, const uint64_t *in_off, const uint64_t *seg_first, size_t n_blocks,
+                                  const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
+                                  uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
+                                  const zpaqhip_compress_opts *opts, zpaqhip_err *err);
+int zpaqhip_compress_solid_blocks_device(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp,
+                                         size_t pcomp_len, const void *d_in, const uint64_t *in_off, const uint64_t *seg_first,
+                                         size_t n_blocks, const void *d_orig, const uint64_t *orig_off,
+                                         const char *const *filenames, void *d_out, size_t out_cap, size_t *out_len,
+                                         uint64_t *block_off, const zpaqhip_compress_opts *opts, void *hip_stream,
+                                         zpaqhip_err *err);
+
 /* ---- a method per block: what LibZPAQ.compressBlock does with a numeric level (LibZPAQ.cs:84-283), device-resident ----------
  * zpaqhip_compress_method_blocks_device for blocks that do not all take the same method: methods[0, n_methods) is the list
  * (args, hdr and pcomp of each as for zpaqhip_compress_method_blocks; `reserved` must be 0), method_of[i] the entry block i

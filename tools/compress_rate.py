@@ -2,7 +2,7 @@
 
     python3 tools/compress_rate.py [--blocks 256] [--block-size 4194304] [--kinds T,R] [--model l1] [--method M] [--bwt] [--sa | --ht]
                                    [--level L [--analysis-only]] [--kernel 0] [--enc-waves 0] [--rounds 1] [--decode-kernel K] [--no-cpu]
-                                   [--device]
+                                   [--device] [--solid N]
 
 Per kind: plaintext MB/s from wall time, the time of each pass (zpaqhip_last_stats: init_ms = model pass, kernel_ms -
 init_ms = coder pass), and the CPU writer
@@ -43,6 +43,11 @@ pre-processing and the packing kernel and init_ms the pre-processing alone, so p
 form (best of the rounds), pack_GBps = stream bytes / pack_ms, and next to it d2d_GBps, a device-to-device copy of the same
 number of bytes timed with events in the same process.  Behind a model the packing kernel's time is part of a kernel_ms
 thousands of times as long and cannot be read off it: pack_ms is null.
+
+--solid N (with --model): the cost of the encoders' segment loop.  Three forms on the same blocks, ALTERNATED in one process,
+--rounds times each (default 2 here), one JSON line per call: Context.compress_blocks ("blocks"), Context.compress_solid with
+every block as one segment ("solid1": the same bytes, "identical"), and with every block cut into N segments of equal
+length ("solidN": N - 1 more end-of-segment bits and segment frames per block; checked by a round trip).
 """
 import argparse
 import json
@@ -177,6 +182,39 @@ def run_device(ctx, a, kernels):
                               "d2d_GBps": len(want) / 1e6 / d2d}), flush=True)
 
 
+def run_solid(ctx, a, kernels):
+    n = a.solid
+    for kind in a.kinds.split(","):
+        blocks = [synth.plain(kind, i, a.block_size).tobytes() for i in range(a.blocks)]
+        mb = a.blocks * a.block_size / 1e6
+        step = (a.block_size + n - 1) // n
+        cut = [[b[i:i + step] for i in range(0, len(b), step)] for b in blocks]
+        forms = {"blocks": lambda k, w: ctx.compress_blocks(a.model, blocks, kernel=k, enc_waves=w),
+                 "solid1": lambda k, w: ctx.compress_solid(a.model, [[b] for b in blocks], kernel=k, enc_waves=w),
+                 f"solid{n}": lambda k, w: ctx.compress_solid(a.model, cut, kernel=k, enc_waves=w)}
+        for k in kernels:
+            ctx.compress_solid(a.model, cut[:1], kernel=k)                    # warm-up
+        want, checked = {}, set()
+        for rnd in range(a.rounds):
+            for k, w, form in [(k, w, f) for k in kernels for w in a.waves for f in forms]:
+                t = time.perf_counter()
+                got = forms[form](k, w)
+                wall = time.perf_counter() - t
+                st = ctx.stats()
+                row = {"model": a.model, "kind": kind, "blocks": a.blocks, "block_size": a.block_size, "kernel": k, "enc_waves": w,
+                       "form": form, "segments_per_block": 1 if form != f"solid{n}" else len(cut[0]), "round": rnd, "wall_s": wall,
+                       "MBps": mb / wall, "kernel_ms": st.kernel_ms, "kernel_MBps": mb / (st.kernel_ms / 1e3), "launches": st.launches,
+                       "kernel_kind": st.kernel_kind, "in_flight": st.concurrent, "out_bytes": len(got), "ratio": len(got) / (mb * 1e6)}
+                if form == "blocks":
+                    want[k] = got
+                elif form == "solid1":
+                    row["identical"] = got == want[k]
+                elif (k, form) not in checked:
+                    checked.add((k, form))
+                    row["round_trip"] = ctx.decompress(got, verify_sha1=True).tobytes() == b"".join(blocks)
+                print(json.dumps(row), flush=True)
+
+
 def run_level(ctx, a, kernels):
     for kind in a.kinds.split(","):
         blocks = [synth.plain(kind, i, a.block_size) for i in range(a.blocks)]
@@ -235,13 +273,16 @@ def main():
     ap.add_argument("--enc-waves", default="0", help="chain encoder waves per compute unit, comma separated; several are alternated")
     ap.add_argument("--rounds", type=int, default=None, help="runs of each --kernel value (default 1; 2 with --device)")
     ap.add_argument("--device", action="store_true", help="host form against device form (compress_*_device), alternated")
+    ap.add_argument("--solid", type=int, default=0, help="blocks, one-segment solid blocks and N-segment solid blocks, alternated")
     ap.add_argument("--decode-kernel", type=int, default=None, help="also time the decoder with this opts.kernel")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU writer")
     a = ap.parse_args()
     kernels = [int(k) for k in (a.kernel or ("2" if a.level else "0")).split(",")]
     a.waves = [int(w) for w in a.enc_waves.split(",")]
-    a.rounds = a.rounds if a.rounds is not None else 2 if a.device else 1
+    a.rounds = a.rounds if a.rounds is not None else 2 if a.device or a.solid else 1
     with z.Context(0) as ctx:
+        if a.solid:
+            return run_solid(ctx, a, kernels)
         if a.device:
             return run_device(ctx, a, kernels)
         if a.level:

@@ -81,7 +81,8 @@ SYMBOLS = ("zpaqhip_version", "zpaqhip_strerror", "zpaqhip_device_count", "zpaqh
            "zpaqhip_gap_hist_blocks", "zpaqhip_lzsa_blocks", "zpaqhip_lzht_blocks", "zpaqhip_enc_chain_plan",
            "zpaqhip_dec_chain_plan", "zpaqhip_compress_blocks_device", "zpaqhip_compress_method_blocks_device",
            "zpaqhip_scan_device", "zpaqhip_decompress_device", "zpaqhip_compress_mixed_blocks_device",
-           "zpaqhip_gap_hist_blocks_device", "zpaqhip_verify_blocks", "zpaqhip_verify_blocks_device")
+           "zpaqhip_gap_hist_blocks_device", "zpaqhip_verify_blocks", "zpaqhip_verify_blocks_device",
+           "zpaqhip_compress_solid_blocks", "zpaqhip_compress_solid_blocks_device")
 
 _lib = None
 
@@ -137,6 +138,9 @@ def load():
     # the device forms: the host forms' lists with the hip_stream in front of err
     L.zpaqhip_compress_blocks_device.argtypes = L.zpaqhip_compress_blocks.argtypes[:-1] + [vp, errp]
     L.zpaqhip_compress_method_blocks_device.argtypes = L.zpaqhip_compress_method_blocks.argtypes[:-1] + [vp, errp]
+    # the solid forms: seg_first between in_off and n_blocks
+    L.zpaqhip_compress_solid_blocks.argtypes = L.zpaqhip_compress_blocks.argtypes[:7] + [vp] + L.zpaqhip_compress_blocks.argtypes[7:]
+    L.zpaqhip_compress_solid_blocks_device.argtypes = L.zpaqhip_compress_solid_blocks.argtypes[:-1] + [vp, errp]
     L.zpaqhip_scan_device.argtypes = [vp, vp, sz, C.POINTER(Block), sz, C.POINTER(sz), C.POINTER(Segment), sz, C.POINTER(sz), vp, errp]
     L.zpaqhip_decompress_device.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(SegResult), sz, C.POINTER(sz),
                                             C.POINTER(Opts), vp, errp]

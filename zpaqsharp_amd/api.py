@@ -549,6 +549,114 @@ class Context:
             _raise(err, rc)
         return rc, got.value, boffs
 
+    def compress_solid(self, model, blocks, *, pre=None, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 0,
+                       enc_waves: int = 0, batch_blocks: int = 0, slot_bytes: int = 0) -> bytes:
+        """zpaqhip_compress_solid_blocks: compress_blocks with several segments per block (Compressor.startSegment ..
+        endSegment, repeated; the post-processor is sent in a block's first segment only).  `blocks` is a list of lists of
+        byte strings, a block's segments; a block needs at least one, and a segment may be empty.  `pre` (the coded bytes
+        of each segment when they are not the segment itself; size comment and SHA-1 then still describe `blocks`) and
+        `filenames` have the same shape.  Model, coder interval and post-processor state carry over from a segment to the
+        next: many small files share one block's statistics.  Nothing is pre-processed here: a model with a
+        post-processor needs `pre`, and the caller sees to it that the segments' coded bytes, one after the other, are what
+        the post-processor turns into `blocks`.  The options are compress_blocks' (no verify); a block of one segment is
+        coded where compress_blocks codes it, to the same bytes; a block of several segments of a single-CM model goes to
+        the lane-per-component encoder with kernel=2 and to the generic one otherwise."""
+        from . import models
+        m = models.get(model) if isinstance(model, str) else model
+        if pre is None and m.pcomp:
+            raise ValueError("a model with a post-processor needs the pre-processed segments (pre=)")
+        flat, seg_first = self._solid_lists(blocks, "blocks")
+        plain = [_as_u8(b) for b in flat]
+        coded, orig = plain, None
+        if pre is not None:
+            flat, pf = self._solid_lists(pre, "pre")
+            if pf != seg_first:
+                raise ValueError("pre needs the shape of blocks")
+            coded, orig = [_as_u8(p) for p in flat], plain
+        names = self._solid_names(filenames, seg_first)
+        n, ns = len(seg_first) - 1, len(coded)
+        cbuf, coffs = _cat(coded)
+        obuf, ooffs = _cat(orig) if orig is not None else (None, None)
+        sf = np.asarray(seg_first, np.uint64)
+        o = CompressOpts()
+        o.struct_size = C.sizeof(CompressOpts)
+        o.flags, o.kernel, o.batch_blocks, o.slot_bytes, o.enc_waves = compress_flags(sha1, tag), kernel, batch_blocks, slot_bytes, enc_waves
+        hdr = _as_u8(m.header)
+        pc = _as_u8(m.pcomp) if m.pcomp else None
+        boffs = np.zeros(n + 1, np.uint64)
+        out_cap = int(coffs[-1]) + int(coffs[-1]) // 8 + n * (len(m.header) + 4096) + ns * 128 + 4096
+        for _ in range(2):
+            out = np.empty(max(1, out_cap), np.uint8)
+            err, got = Err(), C.c_size_t(0)
+            rc = self._L.zpaqhip_compress_solid_blocks(
+                self._h, hdr.ctypes.data, hdr.size, pc.ctypes.data if pc is not None else None, pc.size if pc is not None else 0,
+                cbuf.ctypes.data, coffs.ctypes.data, sf.ctypes.data, n, obuf.ctypes.data if obuf is not None else None,
+                ooffs.ctypes.data if ooffs is not None else None, names, out.ctypes.data, out_cap, C.byref(got), boffs.ctypes.data,
+                C.byref(o), C.byref(err))
+            if rc == -20 and got.value > out_cap:    # ZPAQHIP_E_OUTPUT_FULL: now the exact size is known
+                out_cap = got.value
+                continue
+            if rc:
+                _raise(err, rc)
+            return out[:got.value].tobytes()
+        _raise(err, rc)
+
+    @staticmethod
+    def _solid_lists(blocks, what: str):
+        """A list of lists flattened: (the segments in order, seg_first)."""
+        flat, seg_first = [], [0]
+        for b in blocks:
+            if isinstance(b, (bytes, bytearray, memoryview, str, np.ndarray)) or len(b) == 0:
+                raise ValueError(f"{what}: every block is a list of at least one segment")
+            flat.extend(b)
+            seg_first.append(len(flat))
+        return flat, seg_first
+
+    @staticmethod
+    def _solid_names(filenames, seg_first):
+        """The per-segment names of a solid call as a C array (None: no names)."""
+        if filenames is None:
+            return None
+        flat, ff = Context._solid_lists(filenames, "filenames") if len(filenames) and not isinstance(filenames[0], (bytes, str)) \
+            else (list(filenames), None)
+        if (ff is not None and ff != list(seg_first)) or len(flat) != seg_first[-1]:
+            raise ValueError("filenames needs one entry per segment")
+        return (C.c_char_p * max(1, len(flat)))(*[(f.encode() if isinstance(f, str) else f) for f in flat])
+
+    def compress_solid_device(self, model, d_in: int, in_off: Sequence[int], seg_first: Sequence[int], d_out: int, out_cap: int, *,
+                              d_orig: int = 0, orig_off: Optional[Sequence[int]] = None, filenames=None, sha1: bool = True,
+                              tag: bool = True, kernel: int = 0, enc_waves: int = 0, batch_blocks: int = 0, slot_bytes: int = 0,
+                              hip_stream: int = 0, raise_on_error: bool = True):
+        """zpaqhip_compress_solid_blocks_device: compress_solid on device buffers, in the style of compress_blocks_device.
+        Segment s codes the bytes d_in + in_off[s] .. d_in + in_off[s + 1]; block i holds the segments seg_first[i] ..
+        seg_first[i + 1]; `filenames` is a flat list, one per segment, or a list of lists in the blocks' shape.  Returns
+        (rc, out_len, block_off) as compress_blocks_device does."""
+        from . import models
+        m = models.get(model) if isinstance(model, str) else model
+        coffs = np.ascontiguousarray(in_off, dtype=np.uint64)
+        sf = np.ascontiguousarray(seg_first, dtype=np.uint64)
+        n = max(0, sf.size - 1)
+        if sf.size == 0 or coffs.size != int(sf[-1]) + 1:
+            raise ValueError("in_off needs one entry per segment and one more")
+        ooffs = np.ascontiguousarray(orig_off, dtype=np.uint64) if orig_off is not None else None
+        if ooffs is not None and ooffs.size != coffs.size:
+            raise ValueError("orig_off needs one entry per entry of in_off")
+        names = self._solid_names(filenames, [int(x) for x in sf])
+        o = CompressOpts()
+        o.struct_size = C.sizeof(CompressOpts)
+        o.flags, o.kernel, o.batch_blocks, o.slot_bytes, o.enc_waves = compress_flags(sha1, tag), kernel, batch_blocks, slot_bytes, enc_waves
+        hdr = _as_u8(m.header)
+        pc = _as_u8(m.pcomp) if m.pcomp else None
+        boffs = np.zeros(n + 1, np.uint64)
+        err, got = Err(), C.c_size_t(0)
+        rc = self._L.zpaqhip_compress_solid_blocks_device(
+            self._h, hdr.ctypes.data, hdr.size, pc.ctypes.data if pc is not None else None, pc.size if pc is not None else 0,
+            d_in or None, coffs.ctypes.data, sf.ctypes.data, n, d_orig or None, ooffs.ctypes.data if ooffs is not None else None,
+            names, d_out or None, out_cap, C.byref(got), boffs.ctypes.data, C.byref(o), hip_stream or None, C.byref(err))
+        if rc and rc != -20 and raise_on_error:
+            _raise(err, rc)
+        return rc, got.value, boffs
+
     @staticmethod
     def _verify_model(model_or_method):
         """(header, pcomp) of a models name, a zpaql.Model or a method string (`x...` / a numeric level is not one)."""

@@ -16,6 +16,9 @@ With `level`, a numeric method "LB,R,t" (level, block size digits, redundancy, t
 reference's callers use it (LibZPAQ.cs:84-108): the block size is (2^20 << B) - 4096 unless `block_size` is given, and
 Context.compress_level picks each block's method (LibZPAQ.cs:124-283), on the lane-per-component encoder unless `kernel`
 says otherwise.
+
+compress_files packs many (name, bytes) pairs into solid blocks instead: several segments per block, one per file, coded by
+Context.compress_solid.
 """
 from __future__ import annotations
 
@@ -74,6 +77,44 @@ def compress(reader: Reader, writer: Writer, model="l1", block_size: Optional[in
         if cur:
             blocks.append(bytes(cur))
         flush()
+    finally:
+        if context is None:
+            ctx.close()
+
+
+def pack_files(sizes, block_size: int):
+    """compress_files' packing rule on a list of file sizes: consecutive files go into one block while their plaintext stays
+    within `block_size` bytes; a file larger than that gets a block of its own.  Returns the blocks as lists of file
+    indices, in order; every file is in exactly one block and no block is empty."""
+    if block_size < 1:
+        raise ValueError("block_size must be positive")
+    blocks, cur, used = [], [], 0
+    for i, n in enumerate(sizes):
+        if cur and used + n > block_size:
+            blocks.append(cur)
+            cur, used = [], 0
+        cur.append(i)
+        used += n
+    if cur:
+        blocks.append(cur)
+    return blocks
+
+
+def compress_files(files, writer: Writer, model="min", block_size: int = 1 << 22, context: Optional[api.Context] = None,
+                   kernel: int = 2, enc_waves: int = 0, batch_blocks: int = 0) -> None:
+    """Many files into solid blocks: `files` is a list of (name, bytes) pairs; pack_files puts them, in order, into blocks of
+    at most `block_size` plaintext bytes, every file a segment with its name, its size comment and its SHA-1, and
+    Context.compress_solid codes the blocks.  A block's model is warm from its second file on and its header is paid once,
+    which is what small files need.  `model` is a models name or a zpaql.Model without a post-processor."""
+    files = [(n, bytes(d)) for n, d in files]
+    groups = pack_files([len(d) for _, d in files], block_size)
+    if not groups:
+        return
+    ctx = context or api.Context(0)
+    try:
+        writer.write(ctx.compress_solid(model, [[files[i][1] for i in g] for g in groups],
+                                        filenames=[[files[i][0] for i in g] for g in groups], kernel=kernel, enc_waves=enc_waves,
+                                        batch_blocks=batch_blocks))
     finally:
         if context is None:
             ctx.close()

@@ -1,5 +1,6 @@
 // zh_compress.cpp — zpaqhip_compress_blocks: Compressor.startBlock / startSegment / postProcess / compress / endSegment /
 // endBlock (Compressor.cs:27-299) for a batch of blocks, one segment each (LibZPAQ.cs:296-323 framing), coded on the GPU;
+// zpaqhip_compress_solid_blocks, the same with several segments per block (startSegment .. endSegment repeated);
 // and what zh_compress.h shares with the method path (zh_pre.cpp).
 //
 // The host validates the header with the decoder's framing code and then, batch by batch (Call's steps below): plans the
@@ -99,11 +100,14 @@ namespace {
 
 // ---- which kernel encodes a block (the encode-side twin of zh_dec_plan.h's route_block): the window-parallel CM encoder for
 // ZH_FAM_CM1 models with opts.kernel 0 or 2, the lane-per-component encoder for the chain families with opts.kernel 2, the
-// generic encoder for everything else (and for a block too long for zh_enc_cm's 28-bit positions)
+// generic encoder for everything else (and for a block too long for zh_enc_cm's 28-bit positions).  A block of several
+// segments (the solid form) never goes to the window-parallel encoder, which codes one segment: its ZH_FAM_CM1 model is a
+// chain of one component, so such a block takes the lane-per-component encoder with opts.kernel 2 and the generic one otherwise.
 enum class EncKernel { Generic, Cm, Chain };
-EncKernel route_encode(const ZhModel &m, const zpaqhip_compress_opts &o, uint64_t coded) {
-  if ((m.kind & 255u) == ZH_FAM_CM1 && (o.kernel == 0 || o.kernel == 2) && coded < ZH_ENC_CM_MAX_N) return EncKernel::Cm;
-  if (o.kernel == 2 && chain_family(m.kind & 255u)) return EncKernel::Chain;
+EncKernel route_encode(const ZhModel &m, const zpaqhip_compress_opts &o, uint64_t coded, uint64_t n_seg) {
+  const bool cm1 = (m.kind & 255u) == ZH_FAM_CM1;
+  if (cm1 && n_seg == 1 && (o.kernel == 0 || o.kernel == 2) && coded < ZH_ENC_CM_MAX_N) return EncKernel::Cm;
+  if (o.kernel == 2 && (chain_family(m.kind & 255u) || (cm1 && n_seg > 1 && m.arena_bytes < (1ull << 32)))) return EncKernel::Chain;
   return EncKernel::Generic;
 }
 
@@ -133,8 +137,10 @@ struct EncRun {
   std::vector<size_t> block;              // one's (a work queue each); desc[k] codes block block[k] of the call
   size_t n_cm = 0, n_chain = 0;
   uint64_t slot_total = 0, scr_total = 0;
+  std::vector<ZhEncSeg> segs;             // desc[k]'s segments are segs[desc[k].seg0 ...], n_seg of them
   std::vector<ZhEncResult> res;
-  DevMem slots, d_desc, d_res, queue, arena, chain_arena, la, lb, bases, P;
+  std::vector<uint64_t> seg_end;          // per entry of segs, from the device
+  DevMem slots, d_desc, d_res, queue, arena, chain_arena, la, lb, bases, P;   // (d_desc: desc, then segs; d_res: res, then seg_end)
 };
 
 struct Batch {                            // blocks [b0, b1) of the call
@@ -143,7 +149,7 @@ struct Batch {                            // blocks [b0, b1) of the call
   uint64_t in_total = 0;
   DevMem d_in;
   PreBatch pre;
-  std::vector<uint32_t> digest;           // five words per block, in block order
+  std::vector<uint32_t> digest;           // five words per block, in block order (the solid form: per segment)
   EncRun first, redo;                     // every block with its own slot; the overflowed ones again with worst-case slots
   std::vector<size_t> slot_of;            // j -> index in `first`
   std::vector<int64_t> redo_of;           // index in `first` -> index in `redo`, or -1
@@ -178,11 +184,18 @@ struct Call {
   zpaqhip_stats st{};
   uint64_t pos = 0;                       // bytes of the stream so far
   bool any_cm = false, any_chain = false;
+  // the solid form: block i holds the segments [seg_first[i], seg_first[i + 1]); seg_in, seg_orig (optional) and filenames
+  // are per segment, in_off and orig_off above the blocks' view of them
+  const uint64_t *seg_first = nullptr, *seg_in = nullptr, *seg_orig = nullptr;
+  DevMem d_model_chain;                   // a ZH_FAM_CM1 model as the lane-per-component encoder takes it
   int cus = 0;                            // compute units: the chain encoder's LDS lets one of its workgroups live on each
   ChainPlan chain;                        // ... with this many waves at most
 
   bool want_sha() const { return (o.flags & 1) != 0; }
   bool want_verify() const { return (o.flags & kFlagVerify) != 0; }
+  size_t seg_lo(size_t i) const { return seg_first ? seg_first[i] : i; }
+  size_t n_seg(size_t i) const { return seg_first ? seg_first[i + 1] - seg_first[i] : 1; }
+  uint64_t seg_plain(size_t s) const { return seg_orig ? seg_orig[s + 1] - seg_orig[s] : seg_in[s + 1] - seg_in[s]; }
   uint64_t in_len(size_t i) const { return in_off[i + 1] - in_off[i]; }
   uint64_t plain_len(size_t i) const { return orig ? orig_off[i + 1] - orig_off[i] : in_len(i); }
   uint64_t coded_len(size_t i) const { return dev_prefix.size() + (pre ? pre->bound(i) : in_len(i)); }   // (an upper bound with pre)
@@ -192,20 +205,22 @@ struct Call {
     if (store) return pre->bound(i) + pre->scratch(i) + vc;
     const uint64_t n = coded_len(i);
     uint64_t c = n + slot_cap(n) + 64 + (orig && want_sha() ? plain_len(i) : 0) + (pre ? pre->scratch(i) : 0) + vc;
-    if (route_encode(M, o, n) == EncKernel::Cm) c += 24 * n + 4 * (ZH_ENC_CM_KEYS + 1);
-    return c;
+    if (route_encode(M, o, n, n_seg(i)) == EncKernel::Cm) c += 24 * n + 4 * (ZH_ENC_CM_KEYS + 1);
+    return c + 24 * n_seg(i);
   }
 
   int open(zpaqhip_ctx *ctx);
   int plan(Batch &B, size_t b0) const;
   int stage(Batch &B);
   int digests(Batch &B) const;
+  int digests_solid(Batch &B) const;
   int verify(Batch &B);
   int encode(const Batch &B, EncRun &r);
   int encode_batch(Batch &B);
   int retry(Batch &B);
   int pack(const FrameTable &T, const Batch &B, uint8_t *d_dst, float *ms);
   int frame(Batch &B);
+  int frame_solid(Batch &B);
 };
 
 // the device, the model for the generic encoder and what the CM encoder needs of it, the budget
@@ -230,6 +245,17 @@ int Call::open(zpaqhip_ctx *ctx) {
   HIPCHK(device_budget(v.mem_share, 0, &budget));
   arena_stride = align_up(M.arena_bytes, 256);
   chain = plan_chain(M);
+  if (seg_first && (M.kind & 255u) == ZH_FAM_CM1) {
+    // a single CM is a chain of one component without ICM / ISSE units; that encoder reads a translated HCOMP's id from
+    // bits 8-15 of the kind, where this family keeps something else: 0 there has it interpret the program
+    ZhModel Mc = M;
+    Mc.kind = ZH_FAM_CHAIN;
+    HIPCHK(d_model_chain.alloc(sizeof(ZhModel)));
+    HIPCHK(hipMemcpy(d_model_chain.p, &Mc, sizeof(ZhModel), hipMemcpyHostToDevice));
+    chain.units = 0;
+    chain.waves = zh_enc_chain_fit(0);
+    chain.lds_bytes = ZH_ENC_CHAIN_TABLES + chain.waves * zh_enc_chain_stride(0);
+  }
   return ZPAQHIP_OK;
 }
 
@@ -289,6 +315,7 @@ int Call::stage(Batch &B) {
 // `orig`, or the coded bytes behind the prefix
 int Call::digests(Batch &B) const {
   if (!want_sha()) return ZPAQHIP_OK;
+  if (seg_first) return digests_solid(B);
   const size_t nb = B.nb(), np = dev_prefix.size();
   std::vector<uint64_t> seg(2 * nb);
   for (size_t j = 0; j < nb; ++j) seg[2 * j + 1] = plain_len(B.b0 + j);
@@ -312,6 +339,29 @@ int Call::digests(Batch &B) const {
   DevMem d_orig;
   HIPCHK(d_orig.alloc(total));
   HIPCHK(hipMemcpy(d_orig.p, h_orig.data(), total, hipMemcpyHostToDevice));
+  return sha1_segments(v, d_orig.as<uint8_t>(), seg, B.digest, err);
+}
+
+// ... and of the solid form: a digest per segment of the batch, over the same bytes
+int Call::digests_solid(Batch &B) const {
+  const size_t sa = seg_first[B.b0], sb = seg_first[B.b1], np = dev_prefix.size();
+  std::vector<uint64_t> seg(2 * (sb - sa));
+  for (size_t s = sa; s < sb; ++s) seg[2 * (s - sa) + 1] = seg_plain(s);
+  if (!orig) {                            // a block's segments lie back to back behind its prefix
+    for (size_t j = 0; j < B.nb(); ++j)
+      for (size_t s = seg_first[B.b0 + j]; s < seg_first[B.b0 + j + 1]; ++s)
+        seg[2 * (s - sa)] = B.boff[j] + np + (seg_in[s] - seg_in[seg_first[B.b0 + j]]);
+    return sha1_segments(v, B.d_in.as<uint8_t>(), seg, B.digest, err);
+  }
+  if (dev_in) {
+    for (size_t s = sa; s < sb; ++s) seg[2 * (s - sa)] = seg_orig[s];
+    return sha1_segments(v, orig, seg, B.digest, err);
+  }
+  const uint64_t base = seg_orig[sa], bytes = seg_orig[sb] - base;
+  for (size_t s = sa; s < sb; ++s) seg[2 * (s - sa)] = seg_orig[s] - base;
+  DevMem d_orig;
+  HIPCHK(d_orig.alloc(bytes + 16));
+  if (bytes) HIPCHK(hipMemcpy(d_orig.p, orig + base, bytes, hipMemcpyHostToDevice));
   return sha1_segments(v, d_orig.as<uint8_t>(), seg, B.digest, err);
 }
 
@@ -366,11 +416,17 @@ int Call::verify(Batch &B) {
 int Call::encode(const Batch &B, EncRun &r) {
   const size_t n = r.desc.size(), n_gen = n - r.n_cm - r.n_chain;
   HIPCHK(r.slots.alloc(r.slot_total));
-  HIPCHK(r.d_desc.alloc(n * sizeof(ZhEncBlock)));
-  HIPCHK(r.d_res.alloc(n * sizeof(ZhEncResult)));
-  HIPCHK(hipMemcpy(r.d_desc.p, r.desc.data(), n * sizeof(ZhEncBlock), hipMemcpyHostToDevice));
+  const size_t desc_b = n * sizeof(ZhEncBlock), segs_b = r.segs.size() * sizeof(ZhEncSeg), res_b = n * sizeof(ZhEncResult);
+  std::vector<uint8_t> up(desc_b + segs_b);
+  memcpy(up.data(), r.desc.data(), desc_b);
+  memcpy(up.data() + desc_b, r.segs.data(), segs_b);
+  HIPCHK(r.d_desc.alloc(up.size()));
+  HIPCHK(r.d_res.alloc(res_b + r.segs.size() * 8));
+  HIPCHK(hipMemcpy(r.d_desc.p, up.data(), up.size(), hipMemcpyHostToDevice));
   ZhEncLaunch L;
   memset(&L, 0, sizeof L);
+  L.segs = reinterpret_cast<const ZhEncSeg *>(r.d_desc.as<uint8_t>() + desc_b);
+  L.seg_end = reinterpret_cast<uint64_t *>(r.d_res.as<uint8_t>() + res_b);
   L.in = B.d_in.as<uint8_t>();
   L.slots = r.slots.as<uint8_t>();
   L.model = d_model.as<ZhModel>();
@@ -426,7 +482,9 @@ int Call::encode(const Batch &B, EncRun &r) {
     L.blocks = r.d_desc.as<ZhEncBlock>() + r.n_cm; L.res = r.d_res.as<ZhEncResult>() + r.n_cm; L.n_blocks = (uint32_t)r.n_chain;
     L.queue = r.queue.as<uint32_t>() + 16; L.arena = r.chain_arena.as<uint8_t>();
     L.waves = chain_waves; L.lds_pool = chain.units * 1024u; L.lds_stride = zh_enc_chain_stride(chain.units);
+    if (d_model_chain.p) L.model = d_model_chain.as<ZhModel>();
     HIPCHK(zh_launch_enc_chain(&L, chain_grid, v.stream));
+    L.model = d_model.as<ZhModel>();
     st.launches += 1;
   }
   if (n_gen) {
@@ -445,8 +503,13 @@ int Call::encode(const Batch &B, EncRun &r) {
     HIPCHK(hipEventElapsedTime(&ms_model, v.ev0, ev_model.e));
     st.init_ms += ms_model;
   }
+  std::vector<uint8_t> down(res_b + r.segs.size() * 8);
+  HIPCHK(hipMemcpy(down.data(), r.d_res.p, down.size(), hipMemcpyDeviceToHost));
   r.res.resize(n);
-  HIPCHK(hipMemcpy(r.res.data(), r.d_res.p, n * sizeof(ZhEncResult), hipMemcpyDeviceToHost));
+  r.seg_end.resize(r.segs.size());
+  memcpy(r.res.data(), down.data(), res_b);
+  memcpy(r.seg_end.data(), down.data() + res_b, r.segs.size() * 8);
+  for (size_t k = 0; k < r.n_cm; ++k) r.seg_end[r.desc[k].seg0] = r.res[k].len;   // zh_enc_cm keeps no such record: one segment
   for (size_t k = 0; k < n; ++k)
     if (r.res[k].status) {
       set_err(err, r.res[k].status, (int)r.block[k], -1);
@@ -459,7 +522,7 @@ int Call::encode(const Batch &B, EncRun &r) {
 int Call::encode_batch(Batch &B) {
   EncRun &r = B.first;
   auto take = [&](EncKernel k) {
-    for (size_t i = B.b0; i < B.b1; ++i) if (route_encode(M, o, B.blen[i - B.b0]) == k) r.block.push_back(i);
+    for (size_t i = B.b0; i < B.b1; ++i) if (route_encode(M, o, B.blen[i - B.b0], n_seg(i)) == k) r.block.push_back(i);
   };
   take(EncKernel::Cm);
   r.n_cm = r.block.size();
@@ -481,6 +544,19 @@ int Call::encode_batch(Batch &B) {
     r.slot_total += align_up(d.slot_cap, 256);
     d.scr_off = r.scr_total;
     if (k < r.n_cm) r.scr_total += align_up(d.n, 4);
+    // its segments: the whole coded sequence, or the solid form's, back to back with the prefix in the first
+    const size_t i = r.block[k], ns = n_seg(i);
+    d.seg0 = (uint32_t)r.segs.size();
+    d.n_seg = (uint32_t)ns;
+    if (!seg_first) r.segs.push_back({d.in_off, d.n});
+    else {
+      uint64_t at = d.in_off;
+      for (size_t s = seg_first[i]; s < seg_first[i + 1]; ++s) {
+        const uint64_t len = seg_in[s + 1] - seg_in[s] + (s == seg_first[i] ? dev_prefix.size() : 0);
+        r.segs.push_back({at, len});
+        at += len;
+      }
+    }
   }
   return encode(B, r);
 }
@@ -498,6 +574,8 @@ int Call::retry(Batch &B) {
       d.slot_cap = worst_slot(d.n);
       d.slot_off = r.slot_total;
       r.slot_total += align_up(d.slot_cap, 256);
+      r.segs.insert(r.segs.end(), B.first.segs.begin() + d.seg0, B.first.segs.begin() + d.seg0 + d.n_seg);
+      d.seg0 = (uint32_t)(r.segs.size() - d.n_seg);
       B.redo_of[k] = (int64_t)r.desc.size();
       r.desc.push_back(d);
       r.block.push_back(B.first.block[k]);
@@ -549,6 +627,7 @@ int Call::pack(const FrameTable &T, const Batch &B, uint8_t *d_dst, float *ms) {
 // framing around each block's coded bytes, in block order: the frame table says what goes where; the host form copies by
 // it, the device form hands it to the packing kernel
 int Call::frame(Batch &B) {
+  if (seg_first) return frame_solid(B);
   std::vector<FrameItem> items;
   items.reserve(B.nb());
   for (size_t j = 0; j < B.nb(); ++j) {
@@ -601,6 +680,50 @@ int Call::frame(Batch &B) {
   return ZPAQHIP_OK;
 }
 
+// ... and of the solid form: an entry per segment, cut out of the block's slot at the ends the encoder recorded (the retry's
+// when the block went again); heads and tails come from the table's blob
+int Call::frame_solid(Batch &B) {
+  std::vector<SolidItem> items(B.nb());
+  const size_t sa = seg_first[B.b0];
+  for (size_t j = 0; j < B.nb(); ++j) {
+    const size_t i = B.b0 + j, k = B.slot_of[j];
+    const int64_t redo = B.redo_of[k];
+    const EncRun &r = redo >= 0 ? B.redo : B.first;
+    const ZhEncBlock &d = r.desc[redo >= 0 ? (size_t)redo : k];
+    SolidItem &it = items[j];
+    it.src = redo >= 0 ? ZH_FRAME_SRC_REDO : ZH_FRAME_SRC_FIRST;
+    it.src_off = d.slot_off;
+    for (size_t s = seg_first[i]; s < seg_first[i + 1]; ++s)
+      it.seg.push_back({filenames ? filenames[s] : nullptr, seg_plain(s), want_sha() ? &B.digest[5 * (s - sa)] : nullptr,
+                        r.seg_end[d.seg0 + (s - seg_first[i])]});
+    st.in_bytes += plain_len(i);
+  }
+  const uint64_t pos0 = pos;
+  FrameTable T;
+  pos = build_solid_frame_table((o.flags & 2) != 0, hdr, hdr_len, items, pos0, out_cap, T, block_off ? block_off + B.b0 : nullptr);
+  if (dev_out) {
+    float ms = 0;
+    const int rc = pack(T, B, out, &ms);
+    st.kernel_ms += ms;
+    return rc;
+  }
+  std::vector<uint8_t> h_src;
+  if (pos0 < out_cap) {
+    h_src.resize(B.first.slot_total);
+    HIPCHK(hipMemcpy(h_src.data(), B.first.slots.p, h_src.size(), hipMemcpyDeviceToHost));
+  }
+  for (const ZhFrameEntry &e : T.entry) {
+    uint8_t *w = out + e.dst_off;
+    memcpy(w, T.blob.data() + e.head_off, e.head_len);
+    w += e.head_len;
+    if (e.src == ZH_FRAME_SRC_REDO) {
+      if (e.body_len) HIPCHK(hipMemcpy(w, B.redo.slots.as<uint8_t>() + e.src_off, e.body_len, hipMemcpyDeviceToHost));
+    } else if (e.body_len) memcpy(w, h_src.data() + e.src_off, e.body_len);
+    memcpy(w + e.body_len, T.blob.data() + e.tail_off, e.tail_len);
+  }
+  return ZPAQHIP_OK;
+}
+
 }  // namespace
 
 extern "C" int zpaqhip_enc_chain_plan(const uint8_t *hdr, size_t hdr_len, uint32_t *waves, uint32_t *lds_bytes, zpaqhip_err *err) {
@@ -637,11 +760,74 @@ extern "C" int zpaqhip_compress_blocks_device(zpaqhip_ctx *ctx, const uint8_t *h
                        filenames, (uint8_t *)d_out, out_cap, out_len, block_off, opts, nullptr, err, &dev);
 }
 
+namespace {
+
+// The solid entry points: the checks of the segment tables, the blocks' view of the per-segment offsets, compress_impl
+int solid_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len, const uint8_t *in,
+               const uint64_t *in_off, const uint64_t *seg_first, size_t n_blocks, const uint8_t *orig, const uint64_t *orig_off,
+               const char *const *filenames, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
+               const zpaqhip_compress_opts *opts, zpaqhip_err *err, const DeviceEnds *dev) {
+  if (!ctx || !hdr || !out_len || (!out && out_cap) || (n_blocks && (!in_off || !seg_first)) || (orig && !orig_off)) {
+    set_err(err, ZPAQHIP_E_ARG, -1, -1);
+    return ZPAQHIP_E_ARG;
+  }
+  *out_len = 0;
+  if (resolve_compress_opts(opts).flags & ~3u) {
+    set_err(err, ZPAQHIP_E_ARG, -1, -1, "solid blocks take bits 0 and 1 of flags only (no method opt-ins, no verify)");
+    return ZPAQHIP_E_ARG;
+  }
+  if (n_blocks && seg_first[0] != 0) {
+    set_err(err, ZPAQHIP_E_ARG, 0, -1, "seg_first[0] must be 0");
+    return ZPAQHIP_E_ARG;
+  }
+  for (size_t i = 0; i < n_blocks; ++i) {
+    if (seg_first[i + 1] <= seg_first[i] || seg_first[i + 1] > 0xFFFFFFFFull) {
+      set_err(err, ZPAQHIP_E_ARG, (int)i, -1, seg_first[i + 1] == seg_first[i] ? "a block needs at least one segment" : "seg_first must not decrease");
+      return ZPAQHIP_E_ARG;
+    }
+    for (uint64_t s = seg_first[i]; s < seg_first[i + 1]; ++s)
+      if (in_off[s + 1] < in_off[s] || (orig && orig_off[s + 1] < orig_off[s])) {
+        set_err(err, ZPAQHIP_E_ARG, (int)i, (int)(s - seg_first[i]), "segment offsets must not decrease");
+        return ZPAQHIP_E_ARG;
+      }
+  }
+  std::vector<uint64_t> b_in(n_blocks + 1, 0), b_orig(orig ? n_blocks + 1 : 0, 0);
+  for (size_t i = 0; i <= n_blocks && n_blocks; ++i) {
+    b_in[i] = in_off[seg_first[i]];
+    if (orig) b_orig[i] = orig_off[seg_first[i]];
+  }
+  const SolidSegs solid{seg_first, in_off, orig ? orig_off : nullptr};
+  return compress_impl(ctx, hdr, hdr_len, pcomp, pcomp_len, in, b_in.data(), n_blocks, orig, orig ? b_orig.data() : nullptr, filenames,
+                       out, out_cap, out_len, block_off, opts, nullptr, err, dev, &solid);
+}
+
+}  // namespace
+
+extern "C" int zpaqhip_compress_solid_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
+                                             const uint8_t *in, const uint64_t *in_off, const uint64_t *seg_first, size_t n_blocks,
+                                             const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
+                                             uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
+                                             const zpaqhip_compress_opts *opts, zpaqhip_err *err) {
+  return solid_impl(ctx, hdr, hdr_len, pcomp, pcomp_len, in, in_off, seg_first, n_blocks, orig, orig_off, filenames, out, out_cap,
+                    out_len, block_off, opts, err, nullptr);
+}
+
+extern "C" int zpaqhip_compress_solid_blocks_device(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp,
+                                                    size_t pcomp_len, const void *d_in, const uint64_t *in_off,
+                                                    const uint64_t *seg_first, size_t n_blocks, const void *d_orig,
+                                                    const uint64_t *orig_off, const char *const *filenames, void *d_out,
+                                                    size_t out_cap, size_t *out_len, uint64_t *block_off,
+                                                    const zpaqhip_compress_opts *opts, void *hip_stream, zpaqhip_err *err) {
+  const DeviceEnds dev{(hipStream_t)hip_stream};
+  return solid_impl(ctx, hdr, hdr_len, pcomp, pcomp_len, (const uint8_t *)d_in, in_off, seg_first, n_blocks, (const uint8_t *)d_orig,
+                    orig_off, filenames, (uint8_t *)d_out, out_cap, out_len, block_off, opts, err, &dev);
+}
+
 int zh::compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
                       const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
                       const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
                       uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
-                      const zpaqhip_compress_opts *opts, DevPre *pre, zpaqhip_err *err, const DeviceEnds *dev) {
+                      const zpaqhip_compress_opts *opts, DevPre *pre, zpaqhip_err *err, const DeviceEnds *dev, const SolidSegs *solid) {
   if (!ctx || !hdr || !out_len || (!out && out_cap) || (n_blocks && !in_off) || (orig && !orig_off) || (pcomp_len && !pcomp) ||
       pcomp_len > 65535) {
     set_err(err, ZPAQHIP_E_ARG, -1, -1);
@@ -658,6 +844,11 @@ int zh::compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, cons
       return ZPAQHIP_E_ARG;
     }
   Call c{hdr, hdr_len, in, in_off, n_blocks, orig, orig_off, filenames, out, out_cap, block_off, pre, err, resolve_compress_opts(opts)};
+  if (solid) {
+    c.seg_first = solid->seg_first;
+    c.seg_in = solid->in_off;
+    c.seg_orig = solid->orig_off;
+  }
   if (dev) {
     c.dev_in = c.dev_out = true;
     c.user_stream = dev->stream;

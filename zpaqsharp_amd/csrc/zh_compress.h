@@ -130,10 +130,16 @@ struct DevSink {
 // With `sink`, `out` and `out_cap` are not used: the stream is appended to the sink at sink->used (block_off counts from
 // there) and nothing is ever too small.
 struct DeviceEnds { hipStream_t stream = nullptr; DevSink *sink = nullptr; };
+// The solid form (zpaqhip_compress_solid_blocks): block i holds the segments [seg_first[i], seg_first[i + 1]), whose coded
+// bytes, described bytes and names the per-segment `in_off`, `orig_off` (NULL without `orig`) and compress_impl's
+// `filenames` give; compress_impl's own in_off / orig_off are then the blocks' view of them (in_off[seg_first[i]]).  Without
+// `pre` and without a sink only.
+struct SolidSegs { const uint64_t *seg_first, *in_off, *orig_off; };
 int compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
                   const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
                   const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
                   uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
-                  const zpaqhip_compress_opts *opts, DevPre *pre, zpaqhip_err *err, const DeviceEnds *dev = nullptr);
+                  const zpaqhip_compress_opts *opts, DevPre *pre, zpaqhip_err *err, const DeviceEnds *dev = nullptr,
+                  const SolidSegs *solid = nullptr);
 
 }  // namespace zh

@@ -4,6 +4,10 @@
 // A block's "coded sequence" is what Encoder.compress sees (Compressor.cs:156-222): the post-processor prefix
 // (PASS: 0; PROG: 1, length lo, length hi, program) followed by the block's bytes.  The host lays the coded sequences of
 // a batch out back to back in one device buffer; each block's coded output goes to its own slot.
+//
+// A block holds one or more segments (Compressor.startSegment .. endSegment, repeated): its coded sequence is then the
+// concatenation of its segments' coded sequences, the prefix being part of the first, and ZhEncLaunch::segs says where each
+// lies.  zh_enc_chain and zh_enc_generic walk that table; zh_enc_cm takes blocks of one segment only and reads in_off / n.
 #pragma once
 #include <stdint.h>
 
@@ -32,6 +36,12 @@ struct ZhEncBlock {
   uint64_t slot_off;       // output slot in ZhEncLaunch::slots
   uint64_t slot_cap;       // slot bytes; the coder counts past it but never writes past it
   uint64_t scr_off;        // zh_enc_cm: first element of this block in the list / P scratch (a coded-byte index)
+  uint32_t seg0, n_seg;    // zh_enc_chain / zh_enc_generic: the block's segments, [seg0, seg0 + n_seg) of ZhEncLaunch::segs (n_seg >= 1)
+};
+
+struct ZhEncSeg {
+  uint64_t in_off;         // the segment's coded sequence in ZhEncLaunch::in
+  uint64_t n;              // its length; 0: the segment codes its end-of-segment bit only
 };
 
 struct ZhEncResult {
@@ -44,6 +54,9 @@ struct ZhEncLaunch {
   const uint8_t *in;
   const ZhEncBlock *blocks;
   ZhEncResult *res;
+  const ZhEncSeg *segs;    // zh_enc_chain / zh_enc_generic: every block's segments, a block's back to back
+  uint64_t *seg_end;       // per entry of segs: the coder's byte count (counted past the slot) right behind the segment's
+                           // end-of-segment bit; the last segment's is ZhEncResult::len
   uint8_t *slots;
   uint32_t n_blocks;
   uint32_t waves;          // zh_enc_chain: encoder waves per workgroup (block size / 64); arena slot (blockIdx * waves + wave)

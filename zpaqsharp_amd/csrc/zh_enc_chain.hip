@@ -156,8 +156,8 @@ extern "C" __global__ __launch_bounds__(256) void zh_enc_chain(ZhEncLaunch L) {
     if (bi >= L.n_blocks) break;                       // every wave leaves here, each at its own time
 
     const ZhEncBlock *bdp = &L.blocks[bi];
-    const uint64_t b_n = uni64(bdp->n);
-    const uint8_t *in = L.in + uni64(bdp->in_off);
+    const uint64_t b_n = uni64(bdp->n);                // all of the block's coded bytes, over its segments
+    const uint32_t seg0 = uni(bdp->seg0), seg1 = uni(seg0 + uni(bdp->n_seg));
 
     // ---- Predictor.init (Predictor.cs:82-171): arena tables by all lanes, component by component.  The same initial
     // state as zh_enc_generic.hip's init_slot, with the ICM / ISSE bit-history tables in LDS (below) instead of the arena.
@@ -388,254 +388,262 @@ extern "C" __global__ __launch_bounds__(256) void zh_enc_chain(ZhEncLaunch L) {
       rows_finish(1u, a0, a1, a2, a3, ah);
     }
 
-    // 64 bytes of the coded sequence per step, a byte per lane; the next 64 are loaded meanwhile
-    uint32_t cv = lane < b_n ? in[lane] : 0u;
-    for (uint64_t base = 0; base < b_n && !status; base += 64) {
-      const uint64_t ni = base + 64 + lane;
-      const uint32_t cnx = ni < b_n ? in[ni] : 0u;
-      const uint64_t left = b_n - base;
-      const uint32_t cnt = uni(left < 64 ? (uint32_t)left : 64u);
-      for (uint32_t l = 0; l < cnt; ++l) {               // Encoder.compress(c), Encoder.cs:39-60: one byte per iteration
-        const uint32_t c = rdlane(cv, l);
-        e.low = uni(e.low); e.high = uni(e.high);
-        encode(e, ob, 0, 0, lane);                       // the EOS flag
-        // the second nibble's rows, at their exact addresses: in flight during the first nibble's four bits
-        uint4 nr0 = make_uint4(0, 0, 0, 0), nr1 = nr0, nr2 = nr0, nr3 = nr0;
-        uint32_t nh0 = 0;
-        const uint32_t c8b = 16u | c >> 4, hmap4b = c8b << 4 | 1u;
-        rows_load(c8b, hmap4b, nr0, nr1, nr2, nr3, nh0);
-        uint32_t c8 = 1, hmap4 = 1;                      // Predictor.cs:20-21
-        for (int bit = 0; bit < 8; ++bit) {
-          c8 = uni(c8); hmap4 = uni(hmap4);
-          const uint32_t y = (c >> (7 - bit)) & 1u;
-          const uint32_t hm15 = hmap4 & 15;
-          // ================= predict, level 0 (Predictor.cs:259-343) =================
-          uint32_t rows[kMaxMix] = {0, 0, 0, 0};
-#pragma unroll
-          for (uint32_t q = 0; q < (uint32_t)kMaxMix; ++q) {      // mixer rows: every input lane loads its own weight
-            if (q >= nmix) break;
-            const uint32_t rowv = ((me.h + (c8 & me.a4)) & (me.c - 1)) * mx_m[q];    // valid in the mixer lane
-            rows[q] = rdlane(rowv, mx_lane[q]);
-            const uint32_t *mrow = reinterpret_cast<const uint32_t *>(slot_mem + mx_off[q]) + (lane - mx_j0[q]);
-            if (me.memb >> q & 1) me.mw[q] = (int)mrow[rows[q]];
-          }
-          uint32_t pv = 0, pns = 0;
-          int pdt = 0;
-          if (is_cm) {
-            me.cxt = (me.h ^ hmap4) & 15;
-            pv = reinterpret_cast<const uint32_t *>(myslot)[me.cxt];
-            me.p = T.t.stretch[pv >> 17];
-            pdt = T.t.dt[pv & 0x3ff];
-          }
-          uint32_t ii_a = 0;
-          {
-            // every lane walks the same three dependent LDS reads (row byte -> table entry -> stretch);
-            // lanes of other types read harmless locations and keep nothing
-            const uint32_t sw = *(lds_u32_p)(slot_off + (hm15 & 12));
-            const uint32_t st = (sw >> ((hm15 & 3) * 8)) & 255;               // the bit history of this context
-            ii_a = ii_tab + (st << ii_sh);
-            const uint32_t w_x = *(lds_u32_p)ii_a, w_y = *(lds_u32_p)(ii_a + 4);
-            const uint32_t nsv = *(lds_u16_p)(ns_off + st * 4);               // next(state, 0) | next(state, 1) << 8
-            const int stv = T.t.stretch[is_icm ? w_x >> 8 : 0];
-            if (is_ii) { me.cxt = st; pns = nsv; pv = w_x; me.w0 = (int)w_x; me.w1 = (int)w_y; }
-            if (is_icm) me.p = stv;
-          }
-          {
-            const uint32_t cbit = (me.mbyte >> (7 - (me.cxt & 7))) & 1;
-            if (is_match) { me.c = me.a ? cbit : me.c; me.p = me.a ? (cbit ? pm1 : pm0) : 0; }
-          }
-          if (me.type == ZH_MIX2) {
-            me.cxt = (me.h + (c8 & me.a4)) & (me.c - 1);
-            me.w0 = reinterpret_cast<const uint16_t *>(slot_mem + me.cmo)[me.cxt];
-          }
-          // ================= predict, dependent levels =================
-          for (uint32_t lv = 1; lv <= depth; ++lv) {
-            const uint32_t desc = rdlane(lvl_desc, lv & 63);
-            const uint32_t one = desc & 127, typ = (desc >> 8) & 15;
-            if (LIKELY(one < 64)) {
-              // a single component at this level: wave-uniform control flow, operands by v_readlane,
-              // every lane computes, only lane `one` keeps the result
-              const int pj = (int)rdlane((uint32_t)me.p, (desc >> 16) & 63);
-              const bool mine = lane == one;
-              if (LIKELY(typ == ZH_ISSE)) {
-                const int v = clamp2k((__mul24(me.w0, pj) + me.w1 * 64) >> 16);
-                me.p = mine ? v : me.p; me.pj = mine ? pj : me.pj;
-              } else if (typ == ZH_MIX2) {
-                const int pk = (int)rdlane((uint32_t)me.p, (desc >> 24) & 63);
-                const int v = (__mul24(me.w0, pj) + __mul24(65536 - me.w0, pk)) >> 16;
-                me.p = mine ? v : me.p; me.pj = mine ? pj : me.pj; me.pk = mine ? pk : me.pk;
-              } else if (typ == ZH_AVG) {
-                const int pk = (int)rdlane((uint32_t)me.p, (desc >> 24) & 63);
-                const int v = (pj * (int)me.a2 + pk * (256 - (int)me.a2)) >> 8;
-                me.p = mine ? v : me.p;
-              } else if (mine) {                       // SSE (Predictor.cs:327-340)
-                me.pj = pj;
-                me.cxt = (me.h + c8) * 32u;
-                int pq = clampk(pj + 992, 0, 1983);
-                const int wt = pq & 63;
-                pq >>= 6;
-                me.cxt += (uint32_t)pq;
-                const uint32_t *cm = reinterpret_cast<const uint32_t *>(slot_mem + me.cmo);
-                const uint32_t e0 = cm[me.cxt & me.cm_mask], e1 = cm[(me.cxt + 1) & me.cm_mask];
-                me.p = T.t.stretch[((e0 >> 10) * (uint32_t)(64 - wt) + (e1 >> 10) * (uint32_t)wt) >> 13];
-                me.cxt += (uint32_t)(wt >> 5);
-                me.w0 = (int)((wt >> 5) ? e1 : e0);    // the entry train() will update
-              }
-            } else if (one == 64) {
-              // several components at this level: every lane gathers its own operands (ds_bpermute)
-              const int pj = __shfl(me.p, (int)(me.type == ZH_AVG ? me.a0 : me.a1));
-              const int pk = __shfl(me.p, (int)(me.type == ZH_AVG ? me.a1 : me.a2));
-              if (me.level == lv) {
-                me.pj = pj; me.pk = pk;
-                switch (me.type) {
-                  case ZH_ISSE: me.p = clamp2k((__mul24(me.w0, pj) + me.w1 * 64) >> 16); break;
-                  case ZH_AVG: me.p = (pj * (int)me.a2 + pk * (256 - (int)me.a2)) >> 8; break;
-                  case ZH_MIX2: me.p = (__mul24(me.w0, pj) + __mul24(65536 - me.w0, pk)) >> 16; break;
-                  case ZH_SSE: {
-                    me.cxt = (me.h + c8) * 32u;
-                    int pq = clampk(pj + 992, 0, 1983);
-                    const int wt = pq & 63;
-                    pq >>= 6;
-                    me.cxt += (uint32_t)pq;
-                    const uint32_t *cm = reinterpret_cast<const uint32_t *>(slot_mem + me.cmo);
-                    const uint32_t e0 = cm[me.cxt & me.cm_mask], e1 = cm[(me.cxt + 1) & me.cm_mask];
-                    me.p = T.t.stretch[((e0 >> 10) * (uint32_t)(64 - wt) + (e1 >> 10) * (uint32_t)wt) >> 13];
-                    me.cxt += (uint32_t)(wt >> 5);
-                    me.w0 = (int)((wt >> 5) ? e1 : e0);
-                    break;
+    // The block's segments (Compressor.startSegment .. endSegment, repeated): the model, the rows in flight, the coder and
+    // the output buffer carry over a boundary; a segment adds its end-of-segment bit and the record of where it ended.
+    // seg0, seg1 and every segment's place and length are wave-uniform, so every lane takes the same trips.
+    for (uint32_t sg = seg0; sg < seg1 && !status; ++sg) {
+      const uint64_t s_n = uni64(L.segs[sg].n);
+      const uint8_t *in = L.in + uni64(L.segs[sg].in_off);
+      // 64 bytes of the coded sequence per step, a byte per lane; the next 64 are loaded meanwhile
+      uint32_t cv = lane < s_n ? in[lane] : 0u;
+      for (uint64_t base = 0; base < s_n && !status; base += 64) {
+        const uint64_t ni = base + 64 + lane;
+        const uint32_t cnx = ni < s_n ? in[ni] : 0u;
+        const uint64_t left = s_n - base;
+        const uint32_t cnt = uni(left < 64 ? (uint32_t)left : 64u);
+        for (uint32_t l = 0; l < cnt; ++l) {               // Encoder.compress(c), Encoder.cs:39-60: one byte per iteration
+          const uint32_t c = rdlane(cv, l);
+          e.low = uni(e.low); e.high = uni(e.high);
+          encode(e, ob, 0, 0, lane);                       // the EOS flag
+          // the second nibble's rows, at their exact addresses: in flight during the first nibble's four bits
+          uint4 nr0 = make_uint4(0, 0, 0, 0), nr1 = nr0, nr2 = nr0, nr3 = nr0;
+          uint32_t nh0 = 0;
+          const uint32_t c8b = 16u | c >> 4, hmap4b = c8b << 4 | 1u;
+          rows_load(c8b, hmap4b, nr0, nr1, nr2, nr3, nh0);
+          uint32_t c8 = 1, hmap4 = 1;                      // Predictor.cs:20-21
+          for (int bit = 0; bit < 8; ++bit) {
+            c8 = uni(c8); hmap4 = uni(hmap4);
+            const uint32_t y = (c >> (7 - bit)) & 1u;
+            const uint32_t hm15 = hmap4 & 15;
+            // ================= predict, level 0 (Predictor.cs:259-343) =================
+            uint32_t rows[kMaxMix] = {0, 0, 0, 0};
+  #pragma unroll
+            for (uint32_t q = 0; q < (uint32_t)kMaxMix; ++q) {      // mixer rows: every input lane loads its own weight
+              if (q >= nmix) break;
+              const uint32_t rowv = ((me.h + (c8 & me.a4)) & (me.c - 1)) * mx_m[q];    // valid in the mixer lane
+              rows[q] = rdlane(rowv, mx_lane[q]);
+              const uint32_t *mrow = reinterpret_cast<const uint32_t *>(slot_mem + mx_off[q]) + (lane - mx_j0[q]);
+              if (me.memb >> q & 1) me.mw[q] = (int)mrow[rows[q]];
+            }
+            uint32_t pv = 0, pns = 0;
+            int pdt = 0;
+            if (is_cm) {
+              me.cxt = (me.h ^ hmap4) & 15;
+              pv = reinterpret_cast<const uint32_t *>(myslot)[me.cxt];
+              me.p = T.t.stretch[pv >> 17];
+              pdt = T.t.dt[pv & 0x3ff];
+            }
+            uint32_t ii_a = 0;
+            {
+              // every lane walks the same three dependent LDS reads (row byte -> table entry -> stretch);
+              // lanes of other types read harmless locations and keep nothing
+              const uint32_t sw = *(lds_u32_p)(slot_off + (hm15 & 12));
+              const uint32_t st = (sw >> ((hm15 & 3) * 8)) & 255;               // the bit history of this context
+              ii_a = ii_tab + (st << ii_sh);
+              const uint32_t w_x = *(lds_u32_p)ii_a, w_y = *(lds_u32_p)(ii_a + 4);
+              const uint32_t nsv = *(lds_u16_p)(ns_off + st * 4);               // next(state, 0) | next(state, 1) << 8
+              const int stv = T.t.stretch[is_icm ? w_x >> 8 : 0];
+              if (is_ii) { me.cxt = st; pns = nsv; pv = w_x; me.w0 = (int)w_x; me.w1 = (int)w_y; }
+              if (is_icm) me.p = stv;
+            }
+            {
+              const uint32_t cbit = (me.mbyte >> (7 - (me.cxt & 7))) & 1;
+              if (is_match) { me.c = me.a ? cbit : me.c; me.p = me.a ? (cbit ? pm1 : pm0) : 0; }
+            }
+            if (me.type == ZH_MIX2) {
+              me.cxt = (me.h + (c8 & me.a4)) & (me.c - 1);
+              me.w0 = reinterpret_cast<const uint16_t *>(slot_mem + me.cmo)[me.cxt];
+            }
+            // ================= predict, dependent levels =================
+            for (uint32_t lv = 1; lv <= depth; ++lv) {
+              const uint32_t desc = rdlane(lvl_desc, lv & 63);
+              const uint32_t one = desc & 127, typ = (desc >> 8) & 15;
+              if (LIKELY(one < 64)) {
+                // a single component at this level: wave-uniform control flow, operands by v_readlane,
+                // every lane computes, only lane `one` keeps the result
+                const int pj = (int)rdlane((uint32_t)me.p, (desc >> 16) & 63);
+                const bool mine = lane == one;
+                if (LIKELY(typ == ZH_ISSE)) {
+                  const int v = clamp2k((__mul24(me.w0, pj) + me.w1 * 64) >> 16);
+                  me.p = mine ? v : me.p; me.pj = mine ? pj : me.pj;
+                } else if (typ == ZH_MIX2) {
+                  const int pk = (int)rdlane((uint32_t)me.p, (desc >> 24) & 63);
+                  const int v = (__mul24(me.w0, pj) + __mul24(65536 - me.w0, pk)) >> 16;
+                  me.p = mine ? v : me.p; me.pj = mine ? pj : me.pj; me.pk = mine ? pk : me.pk;
+                } else if (typ == ZH_AVG) {
+                  const int pk = (int)rdlane((uint32_t)me.p, (desc >> 24) & 63);
+                  const int v = (pj * (int)me.a2 + pk * (256 - (int)me.a2)) >> 8;
+                  me.p = mine ? v : me.p;
+                } else if (mine) {                       // SSE (Predictor.cs:327-340)
+                  me.pj = pj;
+                  me.cxt = (me.h + c8) * 32u;
+                  int pq = clampk(pj + 992, 0, 1983);
+                  const int wt = pq & 63;
+                  pq >>= 6;
+                  me.cxt += (uint32_t)pq;
+                  const uint32_t *cm = reinterpret_cast<const uint32_t *>(slot_mem + me.cmo);
+                  const uint32_t e0 = cm[me.cxt & me.cm_mask], e1 = cm[(me.cxt + 1) & me.cm_mask];
+                  me.p = T.t.stretch[((e0 >> 10) * (uint32_t)(64 - wt) + (e1 >> 10) * (uint32_t)wt) >> 13];
+                  me.cxt += (uint32_t)(wt >> 5);
+                  me.w0 = (int)((wt >> 5) ? e1 : e0);    // the entry train() will update
+                }
+              } else if (one == 64) {
+                // several components at this level: every lane gathers its own operands (ds_bpermute)
+                const int pj = __shfl(me.p, (int)(me.type == ZH_AVG ? me.a0 : me.a1));
+                const int pk = __shfl(me.p, (int)(me.type == ZH_AVG ? me.a1 : me.a2));
+                if (me.level == lv) {
+                  me.pj = pj; me.pk = pk;
+                  switch (me.type) {
+                    case ZH_ISSE: me.p = clamp2k((__mul24(me.w0, pj) + me.w1 * 64) >> 16); break;
+                    case ZH_AVG: me.p = (pj * (int)me.a2 + pk * (256 - (int)me.a2)) >> 8; break;
+                    case ZH_MIX2: me.p = (__mul24(me.w0, pj) + __mul24(65536 - me.w0, pk)) >> 16; break;
+                    case ZH_SSE: {
+                      me.cxt = (me.h + c8) * 32u;
+                      int pq = clampk(pj + 992, 0, 1983);
+                      const int wt = pq & 63;
+                      pq >>= 6;
+                      me.cxt += (uint32_t)pq;
+                      const uint32_t *cm = reinterpret_cast<const uint32_t *>(slot_mem + me.cmo);
+                      const uint32_t e0 = cm[me.cxt & me.cm_mask], e1 = cm[(me.cxt + 1) & me.cm_mask];
+                      me.p = T.t.stretch[((e0 >> 10) * (uint32_t)(64 - wt) + (e1 >> 10) * (uint32_t)wt) >> 13];
+                      me.cxt += (uint32_t)(wt >> 5);
+                      me.w0 = (int)((wt >> 5) ? e1 : e0);
+                      break;
+                    }
+                    default: break;
                   }
-                  default: break;
+                }
+              }
+              const uint32_t mq = (desc >> 12) & 7;
+              if (mq) {                                   // a MIX: wave reduction over its input lanes
+  #pragma unroll
+                for (uint32_t q = 0; q < (uint32_t)kMaxMix; ++q) {
+                  if (q >= nmix) break;
+                  if (mq != 7 ? mq != q + 1 : mx_lv[q] != lv) continue;
+                  const int term = (me.memb >> q & 1) ? __mul24(me.mw[q] >> 8, me.p) : 0;
+                  const int sum = wave_sum(term);
+                  if (lane == mx_lane[q]) me.p = clamp2k(sum >> 8);
                 }
               }
             }
-            const uint32_t mq = (desc >> 12) & 7;
-            if (mq) {                                   // a MIX: wave reduction over its input lanes
-#pragma unroll
-              for (uint32_t q = 0; q < (uint32_t)kMaxMix; ++q) {
-                if (q >= nmix) break;
-                if (mq != 7 ? mq != q + 1 : mx_lv[q] != lv) continue;
-                const int term = (me.memb >> q & 1) ? __mul24(me.mw[q] >> 8, me.p) : 0;
-                const int sum = wave_sum(term);
-                if (lane == mx_lane[q]) me.p = clamp2k(sum >> 8);
+            // ================= code the bit =================
+            const int sqp = (int)T.t.squash[me.p + 2048];          // squash(p[i]) of every lane, one LDS pass
+            const uint32_t pr = rdlane((uint32_t)sqp, n - 1);
+            encode(e, ob, y, (pr * 2 + 1) << 16, lane);
+
+            // ================= update (Predictor.cs:363-461) =================
+            const int ey = (int)y * 32767;
+            const int emix = __mul24(ey - sqp, (int)me.a3) >> 4;   // MIX error term (meaningful in mixer lanes)
+  #pragma unroll
+            for (uint32_t q = 0; q < (uint32_t)kMaxMix; ++q) {      // MIX: error from the mixer lane, weights in the input lanes
+              if (q >= nmix) break;
+              const int eq = (int)rdlane((uint32_t)emix, mx_lane[q]);
+              if (me.memb >> q & 1) {
+                me.mw[q] = clamp512k(me.mw[q] + ((__mul24(eq, me.p) + (1 << 12)) >> 13));
+                reinterpret_cast<uint32_t *>(slot_mem + mx_off[q])[rows[q] + (lane - mx_j0[q])] = (uint32_t)me.mw[q];
               }
             }
-          }
-          // ================= code the bit =================
-          const int sqp = (int)T.t.squash[me.p + 2048];          // squash(p[i]) of every lane, one LDS pass
-          const uint32_t pr = rdlane((uint32_t)sqp, n - 1);
-          encode(e, ob, y, (pr * 2 + 1) << 16, lane);
-
-          // ================= update (Predictor.cs:363-461) =================
-          const int ey = (int)y * 32767;
-          const int emix = __mul24(ey - sqp, (int)me.a3) >> 4;   // MIX error term (meaningful in mixer lanes)
-#pragma unroll
-          for (uint32_t q = 0; q < (uint32_t)kMaxMix; ++q) {      // MIX: error from the mixer lane, weights in the input lanes
-            if (q >= nmix) break;
-            const int eq = (int)rdlane((uint32_t)emix, mx_lane[q]);
-            if (me.memb >> q & 1) {
-              me.mw[q] = clamp512k(me.mw[q] + ((__mul24(eq, me.p) + (1 << 12)) >> 13));
-              reinterpret_cast<uint32_t *>(slot_mem + mx_off[q])[rows[q] + (lane - mx_j0[q])] = (uint32_t)me.mw[q];
+            if (is_cm) {
+              const uint32_t cnt_ = pv & 0x3ff;
+              const int er = ey - (int)(pv >> 17);
+              reinterpret_cast<uint32_t *>(myslot)[me.cxt] = pv + (((uint32_t)er * (uint32_t)pdt) & 0xFFFFFC00u) + (cnt_ < me.limit);
             }
-          }
-          if (is_cm) {
-            const uint32_t cnt_ = pv & 0x3ff;
-            const int er = ey - (int)(pv >> 17);
-            reinterpret_cast<uint32_t *>(myslot)[me.cxt] = pv + (((uint32_t)er * (uint32_t)pdt) & 0xFFFFFC00u) + (cnt_ < me.limit);
-          }
-          if (me.type == ZH_SSE) {
-            const uint32_t v = (uint32_t)me.w0, cnt_ = v & 0x3ff;
-            const int er = ey - (int)(v >> 17);
-            reinterpret_cast<uint32_t *>(slot_mem + me.cmo)[me.cxt & me.cm_mask] =
-                v + (((uint32_t)er * (uint32_t)T.t.dt[cnt_]) & 0xFFFFFC00u) + (cnt_ < me.limit);
-          }
-          {                                              // ICM / ISSE: all lanes, stores of unconcerned lanes go to their dummy cell
-            *(lds_u8_p)(is_ii ? slot_off + hm15 : dummy_off) = (uint8_t)(pns >> (y * 8));   // StateTable.next
-            const int er = ey - sqp;
-            const uint32_t n0 = is_icm ? pv + (uint32_t)((int)(ey - (int)(pv >> 8)) >> 2)
-                                       : (uint32_t)clamp512k(me.w0 + ((__mul24(er, me.pj) + (1 << 12)) >> 13));
-            const uint32_t n1 = (uint32_t)clamp512k(me.w1 + ((er + 16) >> 5));
-            *(lds_u32_p)(is_ii ? ii_a : dummy_off) = n0;
-            *(lds_u32_p)(is_isse ? ii_a + 4 : dummy_off) = n1;
-          }
-          if (is_match) {
-            if (me.c != y) me.a = 0;
-            me.mcur = (me.mcur * 2 + y) & 255;
-            ++me.cxt;                                  // finished at the byte boundary below
-          }
-          if (me.type == ZH_MIX2) {
-            const int er = __mul24(ey - sqp, (int)me.a3) >> 5;
-            int w = me.w0 + ((er * (me.pj - me.pk) + (1 << 12)) >> 13);
-            w = clampk(w, 0, 65535);
-            reinterpret_cast<uint16_t *>(slot_mem + me.cmo)[me.cxt] = (uint16_t)w;
-          }
-          // ---- c8 / hmap4 bookkeeping (Predictor.cs:463-474)
-          c8 = uni(c8 * 2 + y);
-          if (bit == 3) {
-            hmap4 = uni((hmap4 & 0xf) << 5 | y << 4 | 1);
-            row_writeback();                             // the first nibble's row, then the rows requested at the byte's start
-            rows_patch(nr0, nr1, nr2, nr3, nh0);
-            rows_finish(c8, nr0, nr1, nr2, nr3, nh0);
-          } else hmap4 = uni((hmap4 & 0x1f0) | (((hmap4 & 0xf) * 2 + y) & 0xf));
-        }
-
-        // ---- MATCH at the byte boundary (Predictor.cs:391-410)
-        uint32_t need = 0, cmv = 0;
-        if (is_match) {
-          me.cxt = 0;
-          (slot_mem + me.hto)[me.limit & me.ht_mask] = (uint8_t)me.mcur;   // the assembled byte; ht(0)=1 is overwritten like the reference
-          me.mcur = 0;
-          me.limit = (me.limit + 1) & me.ht_mask;
-          uint32_t *cm = reinterpret_cast<uint32_t *>(slot_mem + me.cmo);   // still with the h[i] of the byte just coded
-          cmv = cm[me.h & me.cm_mask];                 // consumed after HCOMP: the load travels meanwhile
-          cm[me.h & me.cm_mask] = me.limit;
-        }
-        // h[] for the next byte: z.run(c), then H(i) (Predictor.cs:465-469)
-        int rc;
-        if (hm_lds) { ZH_ENC_HCOMP_LDS(hnative) }
-        else { ZH_ENC_HCOMP_MEM(hnative) }
-        rc = (int)uni((uint32_t)rc);
-        if (rc) { status = rc; break; }
-        me.h = h_in_lds ? lds_h[lane & hmask] : Hptr[lane & hmask];
-        {                                                // rows of the next byte's first nibble: in flight during MATCH
-          uint4 a0 = make_uint4(0, 0, 0, 0), a1 = a0, a2 = a0, a3 = a0;
-          uint32_t ah = 0;
-          row_writeback();
-          rows_load(1u, 1u, a0, a1, a2, a3, ah);
-          if (is_match) {
-            if (me.a == 0) {
-              me.b = me.limit - cmv;
-              need = (me.b & me.ht_mask) != 0;
-            } else me.a += me.a < 255;
-          }
-          uint64_t nm = __ballot(need != 0);
-          while (nm) {                                   // verify candidates with the whole wave
-            const uint32_t ml = (uint32_t)__builtin_ctzll(nm);
-            nm &= nm - 1;
-            const uint32_t lim = rdlane(me.limit, ml), off = rdlane(me.b, ml), msk = rdlane(me.ht_mask, ml);
-            const uint8_t *hp = slot_mem + rdlane(me.hto, ml);
-            uint32_t len = 0;
-            for (uint32_t tb = 0; tb < 256; tb += 64) {
-              const uint32_t t = tb + lane;
-              const bool eq = t < 255 && hp[(lim - t - 1) & msk] == hp[(lim - t - off - 1) & msk];
-              const uint64_t mism = __ballot(!eq);
-              if (mism) { len += (uint32_t)__builtin_ctzll(mism); break; }
-              len += 64;
+            if (me.type == ZH_SSE) {
+              const uint32_t v = (uint32_t)me.w0, cnt_ = v & 0x3ff;
+              const int er = ey - (int)(v >> 17);
+              reinterpret_cast<uint32_t *>(slot_mem + me.cmo)[me.cxt & me.cm_mask] =
+                  v + (((uint32_t)er * (uint32_t)T.t.dt[cnt_]) & 0xFFFFFC00u) + (cnt_ < me.limit);
             }
-            if (lane == ml) me.a = len > 255 ? 255 : len;
+            {                                              // ICM / ISSE: all lanes, stores of unconcerned lanes go to their dummy cell
+              *(lds_u8_p)(is_ii ? slot_off + hm15 : dummy_off) = (uint8_t)(pns >> (y * 8));   // StateTable.next
+              const int er = ey - sqp;
+              const uint32_t n0 = is_icm ? pv + (uint32_t)((int)(ey - (int)(pv >> 8)) >> 2)
+                                         : (uint32_t)clamp512k(me.w0 + ((__mul24(er, me.pj) + (1 << 12)) >> 13));
+              const uint32_t n1 = (uint32_t)clamp512k(me.w1 + ((er + 16) >> 5));
+              *(lds_u32_p)(is_ii ? ii_a : dummy_off) = n0;
+              *(lds_u32_p)(is_isse ? ii_a + 4 : dummy_off) = n1;
+            }
+            if (is_match) {
+              if (me.c != y) me.a = 0;
+              me.mcur = (me.mcur * 2 + y) & 255;
+              ++me.cxt;                                  // finished at the byte boundary below
+            }
+            if (me.type == ZH_MIX2) {
+              const int er = __mul24(ey - sqp, (int)me.a3) >> 5;
+              int w = me.w0 + ((er * (me.pj - me.pk) + (1 << 12)) >> 13);
+              w = clampk(w, 0, 65535);
+              reinterpret_cast<uint16_t *>(slot_mem + me.cmo)[me.cxt] = (uint16_t)w;
+            }
+            // ---- c8 / hmap4 bookkeeping (Predictor.cs:463-474)
+            c8 = uni(c8 * 2 + y);
+            if (bit == 3) {
+              hmap4 = uni((hmap4 & 0xf) << 5 | y << 4 | 1);
+              row_writeback();                             // the first nibble's row, then the rows requested at the byte's start
+              rows_patch(nr0, nr1, nr2, nr3, nh0);
+              rows_finish(c8, nr0, nr1, nr2, nr3, nh0);
+            } else hmap4 = uni((hmap4 & 0x1f0) | (((hmap4 & 0xf) * 2 + y) & 0xf));
           }
-          if (is_match) me.mbyte = (slot_mem + me.hto)[(me.limit - me.b) & me.ht_mask];
-          {                                              // the two predictions a match of this length can make (Predictor.cs:273-287)
-            const int dk = T.t.dt2k[is_match ? me.a : 0];
-            pm0 = T.t.stretch[dk & 32767];
-            pm1 = T.t.stretch[(-dk) & 32767];
+
+          // ---- MATCH at the byte boundary (Predictor.cs:391-410)
+          uint32_t need = 0, cmv = 0;
+          if (is_match) {
+            me.cxt = 0;
+            (slot_mem + me.hto)[me.limit & me.ht_mask] = (uint8_t)me.mcur;   // the assembled byte; ht(0)=1 is overwritten like the reference
+            me.mcur = 0;
+            me.limit = (me.limit + 1) & me.ht_mask;
+            uint32_t *cm = reinterpret_cast<uint32_t *>(slot_mem + me.cmo);   // still with the h[i] of the byte just coded
+            cmv = cm[me.h & me.cm_mask];                 // consumed after HCOMP: the load travels meanwhile
+            cm[me.h & me.cm_mask] = me.limit;
           }
-          rows_finish(1u, a0, a1, a2, a3, ah);
+          // h[] for the next byte: z.run(c), then H(i) (Predictor.cs:465-469)
+          int rc;
+          if (hm_lds) { ZH_ENC_HCOMP_LDS(hnative) }
+          else { ZH_ENC_HCOMP_MEM(hnative) }
+          rc = (int)uni((uint32_t)rc);
+          if (rc) { status = rc; break; }
+          me.h = h_in_lds ? lds_h[lane & hmask] : Hptr[lane & hmask];
+          {                                                // rows of the next byte's first nibble: in flight during MATCH
+            uint4 a0 = make_uint4(0, 0, 0, 0), a1 = a0, a2 = a0, a3 = a0;
+            uint32_t ah = 0;
+            row_writeback();
+            rows_load(1u, 1u, a0, a1, a2, a3, ah);
+            if (is_match) {
+              if (me.a == 0) {
+                me.b = me.limit - cmv;
+                need = (me.b & me.ht_mask) != 0;
+              } else me.a += me.a < 255;
+            }
+            uint64_t nm = __ballot(need != 0);
+            while (nm) {                                   // verify candidates with the whole wave
+              const uint32_t ml = (uint32_t)__builtin_ctzll(nm);
+              nm &= nm - 1;
+              const uint32_t lim = rdlane(me.limit, ml), off = rdlane(me.b, ml), msk = rdlane(me.ht_mask, ml);
+              const uint8_t *hp = slot_mem + rdlane(me.hto, ml);
+              uint32_t len = 0;
+              for (uint32_t tb = 0; tb < 256; tb += 64) {
+                const uint32_t t = tb + lane;
+                const bool eq = t < 255 && hp[(lim - t - 1) & msk] == hp[(lim - t - off - 1) & msk];
+                const uint64_t mism = __ballot(!eq);
+                if (mism) { len += (uint32_t)__builtin_ctzll(mism); break; }
+                len += 64;
+              }
+              if (lane == ml) me.a = len > 255 ? 255 : len;
+            }
+            if (is_match) me.mbyte = (slot_mem + me.hto)[(me.limit - me.b) & me.ht_mask];
+            {                                              // the two predictions a match of this length can make (Predictor.cs:273-287)
+              const int dk = T.t.dt2k[is_match ? me.a : 0];
+              pm0 = T.t.stretch[dk & 32767];
+              pm1 = T.t.stretch[(-dk) & 32767];
+            }
+            rows_finish(1u, a0, a1, a2, a3, ah);
+          }
         }
+        cv = cnx;
       }
-      cv = cnx;
+      e.low = uni(e.low); e.high = uni(e.high);
+      if (!status) encode(e, ob, 1, 0, lane);              // compress(-1): end of segment
+      if (lane == 0) L.seg_end[sg] = ob.len;
     }
-    e.low = uni(e.low); e.high = uni(e.high);
-    if (!status) encode(e, ob, 1, 0, lane);              // compress(-1): end of segment
     out_flush(ob, lane);
     if (lane == 0) {
       ZhEncResult r;

@@ -159,20 +159,25 @@ extern "C" __global__ __launch_bounds__(64) void zh_enc_generic(ZhEncLaunch L) {
       Sink &out = S.sink;
       out.out = L.slots + bd.slot_off; out.cap = bd.slot_cap; out.len = 0;
       Enc e{1u, 0xFFFFFFFFu};
-      const uint8_t *in = L.in + bd.in_off;
       int status = 0;
-      for (uint64_t i = 0; i < bd.n && !status; ++i) {   // Encoder.compress(c), Encoder.cs:39-60
-        const int c = in[i];
-        encode(e, out, 0, 0);
-        for (int k = 7; k >= 0; --k) {
-          const uint32_t p = (uint32_t)predict(P) * 2 + 1;
-          const int y = c >> k & 1;
-          encode(e, out, y, p);
-          status = update(P, y, L.budget);
-          if (status) break;
+      // the block's segments (Compressor.startSegment .. endSegment, repeated): model, coder and output carry over
+      for (uint32_t s = bd.seg0; s < bd.seg0 + bd.n_seg && !status; ++s) {
+        const ZhEncSeg sg = L.segs[s];
+        const uint8_t *in = L.in + sg.in_off;
+        for (uint64_t i = 0; i < sg.n && !status; ++i) {   // Encoder.compress(c), Encoder.cs:39-60
+          const int c = in[i];
+          encode(e, out, 0, 0);
+          for (int k = 7; k >= 0; --k) {
+            const uint32_t p = (uint32_t)predict(P) * 2 + 1;
+            const int y = c >> k & 1;
+            encode(e, out, y, p);
+            status = update(P, y, L.budget);
+            if (status) break;
+          }
         }
+        if (!status) encode(e, out, 1, 0);              // compress(-1): end of segment
+        L.seg_end[s] = out.len;
       }
-      if (!status) encode(e, out, 1, 0);                // compress(-1): end of segment
       ZhEncResult r;
       r.len = out.len; r.status = status; r.overflow = out.len > out.cap;
       L.res[bi] = r;

@@ -51,6 +51,10 @@ struct BlockFrame {
   std::string head, tail;
   BlockFrame(bool tag, uint8_t level, const uint8_t *hdr, size_t hdr_len, const char *filename, uint64_t plain_len,
              const uint32_t *digest);
+  // One segment of a block that holds several (Compressor.startSegment .. endSegment, repeated): tag and block header go
+  // in front of the `first` segment's head only, the end of block behind the `last` one's tail only.
+  BlockFrame(bool tag, uint8_t level, const uint8_t *hdr, size_t hdr_len, const char *filename, uint64_t plain_len,
+             const uint32_t *digest, bool first, bool last);
 };
 // Encoder.compress without a model (Encoder.cs:39-73): the decoded stream, `sel` then `pre`, in chunks of at most 65 536
 // bytes behind their 4-byte big-endian lengths.
@@ -76,6 +80,27 @@ struct FrameTable {
 // that fit are in.  `sel` non-NULL selects the store layout.  Returns the stream offset behind the batch.
 uint64_t build_frame_table(const std::vector<FrameItem> &items, const std::vector<uint8_t> *sel, uint64_t pos, uint64_t out_cap,
                            FrameTable &T, uint64_t *block_pos);
+
+// The solid form: a block of several segments whose coded bytes lie back to back in one slot.  Segment s of a block has the
+// bytes [seg[s - 1].end, seg[s].end) of the slot (from 0 for the first): `end` is the encoder's count right behind the
+// segment's end-of-segment bit (ZhEncLaunch::seg_end).
+struct SolidSeg {
+  const char *filename;                   // NULL = empty
+  uint64_t plain_len;                     // the size comment
+  const uint32_t *digest;                 // five words, or NULL = no SHA-1
+  uint64_t end;
+};
+struct SolidItem {                        // one block of a batch
+  uint32_t src;                           // where its slot lies
+  uint64_t src_off;
+  std::vector<SolidSeg> seg;              // at least one
+};
+// The frame table of such a batch: an entry per segment, head || body || tail as for build_frame_table, the first
+// segment's head behind the tag and the block header, the last one's tail in front of the end of block (BlockFrame writes
+// them all).  block_pos[j] (optional) is where block j starts; a block's entries are in the table when the WHOLE block
+// fits under out_cap, else none of them is; T.item[e] is the block of entry e.  Returns the stream offset behind the batch.
+uint64_t build_solid_frame_table(bool tag, const uint8_t *hdr, size_t hdr_len, const std::vector<SolidItem> &items, uint64_t pos,
+                                 uint64_t out_cap, FrameTable &T, uint64_t *block_pos);
 
 // The gather table of a mixed call (zpaqhip_compress_mixed_blocks_device): item i is block i of the call, framed already,
 // `len` bytes at `src_off` of the call's scratch stream, where the blocks lie group by group.  The stream has them in input

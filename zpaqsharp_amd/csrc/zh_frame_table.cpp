@@ -14,13 +14,18 @@ std::vector<uint8_t> zh::selector_prefix(const uint8_t *pcomp, size_t pcomp_len)
 }
 
 zh::BlockFrame::BlockFrame(bool tag, uint8_t level, const uint8_t *hdr, size_t hdr_len, const char *filename, uint64_t plain_len,
-                           const uint32_t *digest) : tail(4, '\0') {
+                           const uint32_t *digest) : BlockFrame(tag, level, hdr, hdr_len, filename, plain_len, digest, true, true) {}
+
+zh::BlockFrame::BlockFrame(bool tag, uint8_t level, const uint8_t *hdr, size_t hdr_len, const char *filename, uint64_t plain_len,
+                           const uint32_t *digest, bool first, bool last) : tail(4, '\0') {
   static constexpr uint8_t kTag[13] = {0x37, 0x6b, 0x53, 0x74, 0xa0, 0x31, 0x83, 0xd3, 0x8c, 0xb2, 0x28, 0xb0, 0xd3};   // Compressor.cs:27-43
-  if (tag) head.append((const char *)kTag, 13);
-  head.append("zPQ", 3);
-  head.push_back((char)level);
-  head.push_back(1);
-  head.append((const char *)hdr, hdr_len);
+  if (first) {
+    if (tag) head.append((const char *)kTag, 13);
+    head.append("zPQ", 3);
+    head.push_back((char)level);
+    head.push_back(1);
+    head.append((const char *)hdr, hdr_len);
+  }
   head.push_back(1);
   if (filename) head.append(filename);
   head.push_back(0);
@@ -32,7 +37,7 @@ zh::BlockFrame::BlockFrame(bool tag, uint8_t level, const uint8_t *hdr, size_t h
     for (int w = 0; w < 5; ++w)
       for (int s = 24; s >= 0; s -= 8) tail.push_back((char)(digest[w] >> s));
   } else tail.push_back((char)254);
-  tail.push_back((char)255);
+  if (last) tail.push_back((char)255);
 }
 
 uint64_t zh::store_body_len(uint64_t decoded) { return decoded + 4 * ((decoded + 65535) / 65536); }
@@ -77,6 +82,47 @@ uint64_t zh::build_frame_table(const std::vector<FrameItem> &items, const std::v
       T.entry.push_back(e);
       T.item.push_back(j);
       T.pieces = (uint32_t)std::max<uint64_t>(T.pieces, (decoded + ZH_FRAME_PIECE - 1) / ZH_FRAME_PIECE);
+    }
+    pos += need;
+  }
+  return pos;
+}
+
+uint64_t zh::build_solid_frame_table(bool tag, const uint8_t *hdr, size_t hdr_len, const std::vector<SolidItem> &items, uint64_t pos,
+                                     uint64_t out_cap, FrameTable &T, uint64_t *block_pos) {
+  T = FrameTable();
+  for (size_t j = 0; j < items.size(); ++j) {
+    const SolidItem &it = items[j];
+    const size_t ns = it.seg.size(), e0 = T.entry.size(), blob0 = T.blob.size();
+    uint64_t need = 0, from = 0;
+    for (size_t s = 0; s < ns; ++s) {
+      const SolidSeg &sg = it.seg[s];
+      const BlockFrame f(tag, 1, hdr, hdr_len, sg.filename, sg.plain_len, sg.digest, s == 0, s + 1 == ns);
+      ZhFrameEntry e;
+      memset(&e, 0, sizeof e);
+      e.dst_off = pos + need;
+      e.src = it.src;
+      e.src_off = it.src_off + from;
+      e.body_len = sg.end - from;
+      e.head_off = T.blob.size();
+      e.head_len = (uint32_t)f.head.size();
+      T.blob.insert(T.blob.end(), f.head.begin(), f.head.end());
+      e.tail_off = T.blob.size();
+      e.tail_len = (uint32_t)f.tail.size();
+      T.blob.insert(T.blob.end(), f.tail.begin(), f.tail.end());
+      T.entry.push_back(e);
+      T.item.push_back(j);
+      need += f.head.size() + e.body_len + f.tail.size();
+      from = sg.end;
+    }
+    if (block_pos) block_pos[j] = pos;
+    if (need <= out_cap && pos <= out_cap - need) {
+      for (size_t n = e0; n < T.entry.size(); ++n)
+        T.pieces = (uint32_t)std::max<uint64_t>(T.pieces, (T.entry[n].body_len + ZH_FRAME_PIECE - 1) / ZH_FRAME_PIECE);
+    } else {                              // the whole block or nothing of it
+      T.entry.resize(e0);
+      T.item.resize(e0);
+      T.blob.resize(blob0);
     }
     pos += need;
   }

@@ -15,6 +15,7 @@ import torch
 import oracle
 import zpaqsharp_amd as z
 from tests import lzcodes
+from tests.verify_cases import SUB1, first_diff
 from zpaqsharp_amd import method as mth, synth, zpaql
 
 pytestmark = pytest.mark.gpu
@@ -125,16 +126,10 @@ def _lzpre_positions(feed: bytes):
             i += 2 + c
         else:
             if off is None and i > 200:
-                off = i + (c >> 6)
-            i += 1 + (c >> 6)
+                off = i + 1 + (c >> 6)
+            i += 2 + (c >> 6)                                   # the code byte and (c >> 6) + 1 offset bytes
     assert lit is not None and off is not None
     return lit, off
-
-
-def _first_diff(a: bytes, b: bytes) -> int:
-    n = min(len(a), len(b))
-    d = np.flatnonzero(np.frombuffer(a[:n], np.uint8) != np.frombuffer(b[:n], np.uint8))
-    return int(d[0]) if d.size else (NONE if len(a) == len(b) else n)
 
 
 @pytest.mark.parametrize("what", ["literal", "offset"])
@@ -149,7 +144,7 @@ def test_detection(ctx, what):
     bad[at] ^= 1
     tampered = [pre[0], bytes(bad), pre[2]]
     got = oracle.run_pcomp(model.pcomp, tampered[1], model.header[4], model.header[5], cap=4 * len(blocks[1]) + 4096)
-    want_diff = _first_diff(got, blocks[1])
+    want_diff = first_diff(got, blocks[1])
     assert want_diff != NONE
     rec = ctx.verify_blocks(model, tampered, blocks)
     assert [r["status"] for r in rec] == [0, E_VERIFY, 0]
@@ -180,7 +175,6 @@ def test_detection(ctx, what):
 
 
 # ---- 4. the post-processor's own errors, and a caller's own program ---------------------------------------------------------
-SUB1 = "comp 0 0 0 0 0 hcomp halt pcomp sub1 ; a> 255 if halt endif a-- out halt end"
 THIRD = "comp 0 0 0 0 0 hcomp halt pcomp third ; a> 255 if halt endif b=a d++ a=d a== 3 if a++ endif a=b out halt end"
 
 

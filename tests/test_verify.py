@@ -106,6 +106,26 @@ def test_the_default_is_no_verify():
     assert ctx._L.flags == [("zpaqhip_compress_blocks", 3)]
 
 
+def test_compress_level_names_the_failing_block_of_the_call():
+    """compress_level codes its blocks in groups of one method each; a group's error (a verify failure, say) comes back as a
+    ZpaqError with the block's index in the call and the group's message."""
+    ctx = _fake_ctx()
+    blocks = [np.zeros(10, np.uint8), np.zeros(2_000_000, np.uint8), np.zeros(20, np.uint8), np.zeros(30, np.uint8)]
+    seen = []
+
+    def failing(method, group, *a):
+        seen.append((method, [b.size for b in group]))
+        if len(group) == 3:
+            raise z.ZpaqError(-28, 1, -1, "from the group")
+        return b"", np.zeros(len(group) + 1, np.uint64)
+
+    ctx._compress_method = failing
+    with pytest.raises(z.ZpaqError) as e:
+        ctx.compress_level("1,128,0", blocks, verify=True)
+    assert (e.value.code, e.value.block, e.value.segment, str(e.value)) == (-28, 2, -1, "from the group")
+    assert ([10, 20, 30] in [s for _, s in seen]) and len({m for m, _ in seen}) == len(seen)
+
+
 class _Bytes(Reader):
     def __init__(self, data):
         self.data, self.pos = data, 0

@@ -430,7 +430,7 @@ class Context:
                                                  sha1, tag, kernel, batch_blocks, slot_bytes, True, sa, ht, enc_waves, verify)
             except ZpaqError as e:                         # (the block's index in the call, not in its group)
                 if 0 <= e.block < len(ids):
-                    raise ZpaqError(e.code, ids[e.block], e.segment, e.msg) from None
+                    raise ZpaqError(e.code, ids[e.block], e.segment, str(e)) from None
                 raise
             for j, i in enumerate(ids):
                 parts[i] = out[int(off[j]):int(off[j + 1])]

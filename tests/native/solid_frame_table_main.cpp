@@ -1,5 +1,5 @@
-// A stand-alone check of the solid form of zh_frame.h's frame table (zh_frame_table.cpp's build_solid_frame_table): blocks of
-// several segments whose coded bytes lie back to back in one slot, cut at the ends the encoders record.  The table is played
+// A stand-alone check of zh_frame.h's frame table (zh_frame_table.cpp's build_frame_table) on blocks of several segments,
+// whose coded bytes lie back to back in one slot, cut at the ends the encoders record.  The table is played
 // the way the host copy and zh_frame.hip play it (head || body || tail of every entry at its dst_off) into a buffer of
 // sentinels, against a stream assembled byte by byte from the format alone.  tests/test_solid_frame.py builds it with
 // -fsanitize=address,undefined and runs it; it prints one line per check and exits non-zero at the first that fails.
@@ -36,7 +36,7 @@ struct Batch {
   std::vector<uint8_t> slots;                       // every block's slot, 256-byte aligned, filled with a pattern
   std::vector<uint64_t> slot_off;
   std::vector<std::vector<uint32_t>> digest;        // five words per segment
-  std::vector<SolidItem> items;
+  std::vector<TableBlock> items;
 };
 
 static Batch make_batch(const std::vector<Block> &blocks, bool sha) {
@@ -58,7 +58,7 @@ static Batch make_batch(const std::vector<Block> &blocks, bool sha) {
       for (uint32_t w = 0; w < 5; ++w) B.digest.back().push_back(0x01020304u * (w + 1) + (uint32_t)s * 0x10001u + salt++);
   }
   for (size_t j = 0; j < blocks.size(); ++j) {
-    SolidItem it;
+    TableBlock it;
     it.src = ZH_FRAME_SRC_FIRST;
     it.src_off = B.slot_off[j];
     uint64_t end = 0;
@@ -142,7 +142,7 @@ static void run(const char *what, const std::vector<Block> &blocks, bool sha, bo
   for (uint64_t cap : caps) {
     FrameTable T;
     std::vector<uint64_t> bp(blocks.size(), 77);
-    CHECK(build_solid_frame_table(tag, kHdr, sizeof kHdr, B.items, pos0, cap, T, bp.data()) == pos.back());
+    CHECK(build_frame_table(tag, 1, kHdr, sizeof kHdr, B.items, nullptr, pos0, cap, T, bp.data()) == pos.back());
     CHECK(T.entry.size() == T.item.size() && T.sel_len == 0);
     const uint64_t size = cap == ~0ull ? pos.back() : cap;
     std::vector<uint8_t> out(size + 64, kSentinel);    // (+ 64: what lies behind out_cap must stay as it is)
@@ -169,25 +169,35 @@ static void run(const char *what, const std::vector<Block> &blocks, bool sha, bo
   }
   // without block_pos
   FrameTable T;
-  CHECK(build_solid_frame_table(tag, kHdr, sizeof kHdr, B.items, pos0, ~0ull, T, nullptr) == pos.back());
+  CHECK(build_frame_table(tag, 1, kHdr, sizeof kHdr, B.items, nullptr, pos0, ~0ull, T, nullptr) == pos.back());
   printf("ok %s\n", what);
 }
 
 static Seg seg(const char *name, uint64_t plain, uint64_t coded) { return {name ? name : "", name != nullptr, plain, coded}; }
 
 int main() {
-  // one segment: the same bytes, and the same single entry, as the one-segment table of build_frame_table
+  // one segment: the same bytes, and the single entry of a block framed by hand
   {
     const std::vector<Block> one = {{{seg("file", 1234, 777)}}};
     run("one_segment", one, true, true, 0);
     const Batch B = make_batch(one, true);
-    FrameTable S, F;
-    build_solid_frame_table(true, kHdr, sizeof kHdr, B.items, 5, ~0ull, S, nullptr);
-    std::vector<FrameItem> items;
-    items.push_back({BlockFrame(true, 1, kHdr, sizeof kHdr, "file", 1234, &B.digest[0][0]), ZH_FRAME_SRC_FIRST, B.slot_off[0], 777});
-    build_frame_table(items, nullptr, 5, ~0ull, F, nullptr);
-    CHECK(S.entry.size() == 1 && F.entry.size() == 1 && S.blob == F.blob && S.pieces == F.pieces);
-    CHECK(memcmp(&S.entry[0], &F.entry[0], sizeof(ZhFrameEntry)) == 0);
+    FrameTable S;
+    build_frame_table(true, 1, kHdr, sizeof kHdr, B.items, nullptr, 5, ~0ull, S, nullptr);
+    const BlockFrame f(true, 1, kHdr, sizeof kHdr, "file", 1234, &B.digest[0][0], true, true);
+    ZhFrameEntry want;
+    memset(&want, 0, sizeof want);
+    want.dst_off = 5;
+    want.src = ZH_FRAME_SRC_FIRST;
+    want.src_off = B.slot_off[0];
+    want.body_len = 777;
+    want.head_off = 0;
+    want.head_len = (uint32_t)f.head.size();
+    want.tail_off = f.head.size();
+    want.tail_len = (uint32_t)f.tail.size();
+    const std::string blob = f.head + f.tail;
+    CHECK(S.entry.size() == 1 && S.item.size() == 1 && S.item[0] == 0 && S.pieces == 1 && S.sel_len == 0);
+    CHECK(S.blob == std::vector<uint8_t>(blob.begin(), blob.end()));
+    CHECK(memcmp(&S.entry[0], &want, sizeof(ZhFrameEntry)) == 0);
     puts("ok one_segment_is_the_block_form");
   }
   run("empty_first_segment", {{{seg("", 0, 1), seg("b", 500, 300)}}}, true, true, 0);
@@ -208,6 +218,26 @@ int main() {
   run("no_sha1", {{{seg("a", 100, 64), seg("b", 200, 65)}}, {{seg("c", 300, 255), seg("d", 1, 256), seg("e", 2, 257)}}}, false, true, 0);
   run("no_tag_later_batch", {{{seg("a", 100, 64)}}, {{seg("c", 300, 255), seg("d", 1, 1)}}, {{seg("e", 2, 3)}}}, true, false, 100000);
   run("pieces", {{{seg("a", 1, 10), seg("b", 200000, 70000), seg("c", 3, 4)}}}, true, true, 0, 2);
+  // a block of three segments whose first two would fit under out_cap but whose third does not: none of its entries is in
+  // the table, the block behind it is out as well, and block_pos and the end are the unbounded ones
+  {
+    const std::vector<Block> blocks = {{{seg("a", 10, 20)}}, {{seg("b", 100, 64), seg("c", 200, 65), seg("d", 300, 66)}}, {{seg("e", 1, 2)}}};
+    const Batch B = make_batch(blocks, true);
+    FrameTable full, T;
+    std::vector<uint64_t> pos(3), bp(3, 77);
+    const uint64_t end = build_frame_table(true, 1, kHdr, sizeof kHdr, B.items, nullptr, 9, ~0ull, full, pos.data());
+    CHECK(full.entry.size() == 5 && full.item[1] == 1 && full.item[3] == 1);
+    const ZhFrameEntry &third = full.entry[3];
+    for (uint64_t cap : {third.dst_off, third.dst_off + third.head_len + third.body_len, pos[2] - 1}) {
+      CHECK(full.entry[2].dst_off + full.entry[2].head_len + full.entry[2].body_len + full.entry[2].tail_len <= cap);   // two fit
+      CHECK(build_frame_table(true, 1, kHdr, sizeof kHdr, B.items, nullptr, 9, cap, T, bp.data()) == end && bp == pos);
+      CHECK(T.entry.size() == 1 && T.item.size() == 1 && T.item[0] == 0);
+      CHECK(memcmp(&T.entry[0], &full.entry[0], sizeof(ZhFrameEntry)) == 0);
+      CHECK(T.blob.size() == T.entry[0].tail_off + T.entry[0].tail_len);      // and nothing of the block stays in the blob
+    }
+    CHECK(build_frame_table(true, 1, kHdr, sizeof kHdr, B.items, nullptr, 9, pos[2], T, bp.data()) == end && T.entry.size() == 4);
+    puts("ok third_segment_does_not_fit");
+  }
   printf("ok %d checks\n", n_checks);
   return 0;
 }

@@ -172,3 +172,63 @@ def test_seeded_random_sweep_matches_the_cpu_writer(ctx):
     for model, blocks in draws.items():
         got = ctx.compress_blocks(model, blocks)
         assert got == _want(model, blocks), model
+
+
+E_VERIFY = -28
+
+
+@pytest.fixture(scope="module")
+def five_blocks():
+    """Plaintext of 0, 1, 15, 4 097 and 70 000 bytes with x86-like calls, its forward E8E9 transform, and the stream the
+    oracle's Compressor writes for l1+e8e9 from the two."""
+    m = models.get("l1+e8e9")
+    plain = [util.x86ish(n, seed=50 + i) if n > 15 else util.text(n, seed=50 + i) for i, n in enumerate((0, 1, 15, 4097, 70000))]
+    pre = [oracle.e8e9(b) for b in plain]
+    assert pre[3] != plain[3] and pre[4] != plain[4]
+    want = []
+    for b, p in zip(plain, pre):
+        c = oracle.Compressor(16 * (len(p) + len(m.pcomp) + 8) + len(m.header) + 4096)
+        c.write_tag()
+        c.start_block(m.header)
+        c.start_segment(b"", str(len(b)).encode())
+        c.post_process(m.pcomp)
+        c.compress(p)
+        c.end_segment(oracle.sha1(b))
+        c.end_block()
+        want.append(c.getvalue())
+    return plain, pre, b"".join(want)
+
+
+def test_host_orig_serves_sha1_and_verify_in_every_batch(ctx, five_blocks):
+    """`pre=` puts `orig` on the host: SHA-1 and verify of a batch read one upload of its range of it, and the batches
+    behind the first start at non-zero offsets of it."""
+    plain, pre, want = five_blocks
+    got = ctx.compress_blocks("l1+e8e9", plain, pre=pre, sha1=True, verify=True, batch_blocks=2)
+    assert got == want
+    assert ctx.decompress(got, verify_sha1=True).tobytes() == b"".join(plain)
+    bad = list(pre)
+    bad[3] = bad[3][:2000] + bytes([bad[3][2000] ^ 0x55]) + bad[3][2001:]
+    with pytest.raises(api.ZpaqError) as e:
+        ctx.compress_blocks("l1+e8e9", plain, pre=bad, sha1=True, verify=True, batch_blocks=2)
+    assert (e.value.code, e.value.block) == (E_VERIFY, 3)
+
+
+def test_device_orig_at_an_odd_base_gives_the_same_bytes(ctx, five_blocks):
+    import torch
+    plain, pre, want = five_blocks
+
+    def offs(parts):
+        return np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.uint64)
+
+    def dev(parts, shift):
+        buf = np.frombuffer(b"".join(parts), np.uint8).copy()
+        t = torch.full((shift + buf.size + 32,), 0x5A, dtype=torch.uint8, device="cuda")
+        t[shift:shift + buf.size].copy_(torch.from_numpy(buf))
+        return t
+
+    tin, torig = dev(pre, 0), dev(plain, 3)
+    tout = torch.zeros(len(want) + 16, dtype=torch.uint8, device="cuda")
+    rc, n, off = ctx.compress_blocks_device("l1+e8e9", tin.data_ptr(), offs(pre), tout.data_ptr(), len(want), d_orig=torig.data_ptr() + 3,
+                                            orig_off=offs(plain), sha1=True, verify=True, batch_blocks=2)
+    assert (rc, n) == (0, len(want))
+    assert tout.cpu().numpy()[:n].tobytes() == want

@@ -231,3 +231,33 @@ def test_compress_files_packs_small_files_into_solid_blocks(ctx):
     apart = ctx.compress_blocks("min", [d for _, d in files], filenames=[n for n, _ in files], kernel=2)
     print(f"solid {len(solid)} bytes, one file per block {len(apart)} bytes, plaintext {pos} bytes")
     assert len(solid) < len(apart)
+
+
+SEG_TABLE_CASES = [("min", 1), ("min", 2), ("l1", 2)]
+
+
+@pytest.fixture(scope="module")
+def later_batches():
+    """Three blocks whose second and third start at non-zero offsets of every per-segment array: an empty one, one of three
+    segments (1 byte, none, 4 097 bytes) and one of 300 bytes."""
+    t = util.text(4097 + 300 + 1, seed=41)
+    return [[b""], [t[:1], b"", t[1:4098]], [t[4098:]]]
+
+
+@pytest.mark.parametrize("model,kernel", SEG_TABLE_CASES)
+def test_a_batch_per_block_frames_the_bytes_of_one_batch(ctx, later_batches, model, kernel):
+    """batch_blocks=1: every batch but the first starts at a non-zero segment, coded offset and stream position."""
+    want = b"".join(_want(model, later_batches))
+    got = ctx.compress_solid(model, later_batches, kernel=kernel, batch_blocks=1)
+    assert got == want
+    assert got == ctx.compress_solid(model, later_batches, kernel=kernel, batch_blocks=0)
+    _decodes(ctx, got, later_batches)
+
+
+@pytest.mark.parametrize("model,kernel", SEG_TABLE_CASES)
+def test_a_batch_per_block_with_a_retry_frames_the_same_bytes(ctx, later_batches, model, kernel):
+    """... and with slots of 64 bytes the block of three segments goes again: the retry's segment ends cut the same bytes."""
+    got = ctx.compress_solid(model, later_batches, kernel=kernel, batch_blocks=1, slot_bytes=64)
+    assert ctx.stats().launches > 3          # a launch per batch, and the retry
+    assert got == b"".join(_want(model, later_batches))
+    assert got == ctx.compress_solid(model, later_batches, kernel=kernel, batch_blocks=0, slot_bytes=64)

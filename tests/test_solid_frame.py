@@ -1,4 +1,4 @@
-"""The solid form of the frame table (zh_frame_table.cpp's build_solid_frame_table) without a GPU: tests/native/
+"""The frame table (zh_frame_table.cpp's build_frame_table) on blocks of several segments, without a GPU: tests/native/
 solid_frame_table_main.cpp, a stand-alone program built with -fsanitize=address,undefined, plays the table of hand-made
 blocks of several segments against a stream assembled byte by byte."""
 import os
@@ -9,7 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "zpaqsharp_amd", "csrc")
 
 WANT = ["ok one_segment", "ok one_segment_is_the_block_form", "ok empty_first_segment", "ok empty_last_segment", "ok empty_bodies",
-        "ok 120_segments", "ok filenames_0_and_300", "ok no_sha1", "ok no_tag_later_batch", "ok pieces"]
+        "ok 120_segments", "ok filenames_0_and_300", "ok no_sha1", "ok no_tag_later_batch", "ok pieces", "ok third_segment_does_not_fit"]
 
 
 def test_solid_frame_table_in_a_sanitized_program(tmp_path):

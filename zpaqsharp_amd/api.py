@@ -438,6 +438,72 @@ class Context:
         self.level_ms = {"analysis": (t1 - t0) * 1e3, "encode": (time.perf_counter() - t1) * 1e3}
         return b"".join(parts)
 
+    # the compressing entry points by (method form, solid form, device form)
+    _ENTRY = {(False, False, False): "zpaqhip_compress_blocks", (False, False, True): "zpaqhip_compress_blocks_device",
+              (True, False, False): "zpaqhip_compress_method_blocks", (True, False, True): "zpaqhip_compress_method_blocks_device",
+              (False, True, False): "zpaqhip_compress_solid_blocks", (False, True, True): "zpaqhip_compress_solid_blocks_device"}
+
+    def _entry(self, header: bytes, pcomp: bytes, *, src, in_off, n: int, opts, args=None, seg_first=None, orig=None, orig_off=None,
+               names=None, device: bool = False):
+        """What every compressing entry point takes in front of its output: (function, leading arguments, what they point
+        into).  `args` selects the method form (which has no `orig`), `seg_first` the solid form, `device` the device forms;
+        `src` and `orig` are addresses or uint8 arrays, the offsets uint64 arrays, `names` a flat list with an entry per
+        segment or None, `opts` (flags, kernel, batch_blocks, slot_bytes, enc_waves)."""
+        if names is not None:
+            if seg_first is None and len(names) != n:
+                raise ValueError("filenames needs one entry per block")
+            names = (C.c_char_p * max(1, len(names)))(*[(f.encode() if isinstance(f, str) else f) for f in names])
+        o = CompressOpts()
+        o.struct_size = C.sizeof(CompressOpts)
+        o.flags, o.kernel, o.batch_blocks, o.slot_bytes, o.enc_waves = opts
+        hdr = _as_u8(header)
+        pc = _as_u8(pcomp) if pcomp else None
+        keep = (o, hdr, pc, src, in_off, seg_first, orig, orig_off, names)
+
+        def ptr(x):
+            return x.ctypes.data if isinstance(x, np.ndarray) else x
+
+        front = [self._h]
+        if args is not None:
+            front.append((C.c_int32 * 9)(*args))
+        front += [ptr(hdr), hdr.size, ptr(pc), pc.size if pc is not None else 0, ptr(src), ptr(in_off)]
+        if seg_first is not None:
+            front.append(ptr(seg_first))
+        front.append(n)
+        if args is None:
+            front += [ptr(orig), ptr(orig_off)]
+        front.append(names)
+        return getattr(self._L, self._ENTRY[args is not None, seg_first is not None, device]), front, keep
+
+    def _run_host(self, entry, n: int, out_cap: int):
+        """A host entry point into a buffer of out_cap bytes, and once more when that was too small (ZPAQHIP_E_OUTPUT_FULL
+        tells the exact size): (stream bytes, block offsets, status of the first call)."""
+        fn, front, keep = entry
+        boffs = np.zeros(n + 1, np.uint64)
+        first = None
+        for _ in range(2):
+            out = np.empty(max(1, out_cap), np.uint8)
+            err, got = Err(), C.c_size_t(0)
+            rc = fn(*front, out.ctypes.data, out_cap, C.byref(got), boffs.ctypes.data, C.byref(keep[0]), C.byref(err))
+            first = rc if first is None else first
+            if rc == -20 and got.value > out_cap:
+                out_cap = got.value
+                continue
+            if rc:
+                _raise(err, rc)
+            return out[:got.value].tobytes(), boffs, first
+        _raise(err, rc)
+
+    def _run_device(self, entry, n: int, d_out: int, out_cap: int, hip_stream: int, raise_on_error: bool):
+        """A device entry point: (status, bytes needed, block offsets)."""
+        fn, front, keep = entry
+        boffs = np.zeros(n + 1, np.uint64)
+        err, got = Err(), C.c_size_t(0)
+        rc = fn(*front, d_out or None, out_cap, C.byref(got), boffs.ctypes.data, C.byref(keep[0]), hip_stream or None, C.byref(err))
+        if rc and rc != -20 and raise_on_error:
+            _raise(err, rc)
+        return rc, got.value, boffs
+
     def _compress(self, header: bytes, pcomp: bytes, coded, orig, filenames, flags: int, kernel: int, batch_blocks: int,
                   slot_bytes: int, out_cap: Optional[int] = None, args: Optional[List[int]] = None, enc_waves: int = 0):
         """zpaqhip_compress_blocks (zpaqhip_compress_method_blocks with `args`: `coded` is then the plaintext) on lists of
@@ -445,42 +511,11 @@ class Context:
         n = len(coded)
         cbuf, coffs = _cat(coded)
         obuf, ooffs = _cat(orig) if orig is not None else (None, None)
-        names = None
-        if filenames is not None:
-            if len(filenames) != n:
-                raise ValueError("filenames needs one entry per block")
-            names = (C.c_char_p * max(1, n))(*[(f.encode() if isinstance(f, str) else f) for f in filenames])
-        o = CompressOpts()
-        o.struct_size = C.sizeof(CompressOpts)
-        o.flags, o.kernel, o.batch_blocks, o.slot_bytes, o.enc_waves = flags, kernel, batch_blocks, slot_bytes, enc_waves
-        hdr = _as_u8(header)
-        pc = _as_u8(pcomp) if pcomp else None
-        boffs = np.zeros(n + 1, np.uint64)
+        entry = self._entry(header, pcomp, args=args, src=cbuf, in_off=coffs, orig=obuf, orig_off=ooffs, names=filenames, n=n,
+                            opts=(flags, kernel, batch_blocks, slot_bytes, enc_waves))
         if out_cap is None:
             out_cap = int(coffs[-1]) + int(coffs[-1]) // 8 + n * (len(header) + 128 + 4096) + 4096
-        first = None
-        for _ in range(2):
-            out = np.empty(max(1, out_cap), np.uint8)
-            err, got = Err(), C.c_size_t(0)
-            if args is not None:
-                rc = self._L.zpaqhip_compress_method_blocks(
-                    self._h, (C.c_int32 * 9)(*args), hdr.ctypes.data, hdr.size, pc.ctypes.data if pc is not None else None,
-                    pc.size if pc is not None else 0, cbuf.ctypes.data, coffs.ctypes.data, n, names, out.ctypes.data, out_cap,
-                    C.byref(got), boffs.ctypes.data, C.byref(o), C.byref(err))
-            else:
-                rc = self._L.zpaqhip_compress_blocks(self._h, hdr.ctypes.data, hdr.size, pc.ctypes.data if pc is not None else None,
-                                                     pc.size if pc is not None else 0, cbuf.ctypes.data, coffs.ctypes.data, n,
-                                                     obuf.ctypes.data if obuf is not None else None,
-                                                     ooffs.ctypes.data if ooffs is not None else None, names, out.ctypes.data,
-                                                     out_cap, C.byref(got), boffs.ctypes.data, C.byref(o), C.byref(err))
-            first = rc if first is None else first
-            if rc == -20 and got.value > out_cap:    # ZPAQHIP_E_OUTPUT_FULL: now the exact size is known
-                out_cap = got.value
-                continue
-            if rc:
-                _raise(err, rc)
-            return out[:got.value].tobytes(), boffs, first
-        _raise(err, rc)
+        return self._run_host(entry, n, out_cap)
 
     def compress_blocks_device(self, model, d_in: int, in_off: Sequence[int], d_out: int, out_cap: int, *, d_orig: int = 0,
                                orig_off: Optional[Sequence[int]] = None, filenames=None, sha1: bool = True, tag: bool = True,
@@ -523,31 +558,9 @@ class Context:
         ooffs = np.ascontiguousarray(orig_off, dtype=np.uint64) if orig_off is not None else None
         if ooffs is not None and ooffs.size != coffs.size:
             raise ValueError("orig_off needs one entry per entry of in_off")
-        names = None
-        if filenames is not None:
-            if len(filenames) != n:
-                raise ValueError("filenames needs one entry per block")
-            names = (C.c_char_p * max(1, n))(*[(f.encode() if isinstance(f, str) else f) for f in filenames])
-        o = CompressOpts()
-        o.struct_size = C.sizeof(CompressOpts)
-        o.flags, o.kernel, o.batch_blocks, o.slot_bytes, o.enc_waves = flags, kernel, batch_blocks, slot_bytes, enc_waves
-        hdr = _as_u8(header)
-        pc = _as_u8(pcomp) if pcomp else None
-        boffs = np.zeros(n + 1, np.uint64)
-        err, got = Err(), C.c_size_t(0)
-        pcp, pcn = (pc.ctypes.data, pc.size) if pc is not None else (None, 0)
-        if args is not None:
-            rc = self._L.zpaqhip_compress_method_blocks_device(
-                self._h, (C.c_int32 * 9)(*args), hdr.ctypes.data, hdr.size, pcp, pcn, d_in or None, coffs.ctypes.data, n, names,
-                d_out or None, out_cap, C.byref(got), boffs.ctypes.data, C.byref(o), hip_stream or None, C.byref(err))
-        else:
-            rc = self._L.zpaqhip_compress_blocks_device(
-                self._h, hdr.ctypes.data, hdr.size, pcp, pcn, d_in or None, coffs.ctypes.data, n, d_orig or None,
-                ooffs.ctypes.data if ooffs is not None else None, names, d_out or None, out_cap, C.byref(got), boffs.ctypes.data,
-                C.byref(o), hip_stream or None, C.byref(err))
-        if rc and rc != -20 and raise_on_error:
-            _raise(err, rc)
-        return rc, got.value, boffs
+        entry = self._entry(header, pcomp, args=args, src=d_in or None, in_off=coffs, orig=d_orig or None, orig_off=ooffs,
+                            names=filenames, n=n, opts=(flags, kernel, batch_blocks, slot_bytes, enc_waves), device=True)
+        return self._run_device(entry, n, d_out, out_cap, hip_stream, raise_on_error)
 
     def compress_solid(self, model, blocks, *, pre=None, filenames=None, sha1: bool = True, tag: bool = True, kernel: int = 0,
                        enc_waves: int = 0, batch_blocks: int = 0, slot_bytes: int = 0) -> bytes:
@@ -573,33 +586,14 @@ class Context:
             if pf != seg_first:
                 raise ValueError("pre needs the shape of blocks")
             coded, orig = [_as_u8(p) for p in flat], plain
-        names = self._solid_names(filenames, seg_first)
         n, ns = len(seg_first) - 1, len(coded)
         cbuf, coffs = _cat(coded)
         obuf, ooffs = _cat(orig) if orig is not None else (None, None)
-        sf = np.asarray(seg_first, np.uint64)
-        o = CompressOpts()
-        o.struct_size = C.sizeof(CompressOpts)
-        o.flags, o.kernel, o.batch_blocks, o.slot_bytes, o.enc_waves = compress_flags(sha1, tag), kernel, batch_blocks, slot_bytes, enc_waves
-        hdr = _as_u8(m.header)
-        pc = _as_u8(m.pcomp) if m.pcomp else None
-        boffs = np.zeros(n + 1, np.uint64)
+        entry = self._entry(m.header, m.pcomp or b"", src=cbuf, in_off=coffs, seg_first=np.asarray(seg_first, np.uint64), orig=obuf,
+                            orig_off=ooffs, names=self._solid_names(filenames, seg_first), n=n,
+                            opts=(compress_flags(sha1, tag), kernel, batch_blocks, slot_bytes, enc_waves))
         out_cap = int(coffs[-1]) + int(coffs[-1]) // 8 + n * (len(m.header) + 4096) + ns * 128 + 4096
-        for _ in range(2):
-            out = np.empty(max(1, out_cap), np.uint8)
-            err, got = Err(), C.c_size_t(0)
-            rc = self._L.zpaqhip_compress_solid_blocks(
-                self._h, hdr.ctypes.data, hdr.size, pc.ctypes.data if pc is not None else None, pc.size if pc is not None else 0,
-                cbuf.ctypes.data, coffs.ctypes.data, sf.ctypes.data, n, obuf.ctypes.data if obuf is not None else None,
-                ooffs.ctypes.data if ooffs is not None else None, names, out.ctypes.data, out_cap, C.byref(got), boffs.ctypes.data,
-                C.byref(o), C.byref(err))
-            if rc == -20 and got.value > out_cap:    # ZPAQHIP_E_OUTPUT_FULL: now the exact size is known
-                out_cap = got.value
-                continue
-            if rc:
-                _raise(err, rc)
-            return out[:got.value].tobytes()
-        _raise(err, rc)
+        return self._run_host(entry, n, out_cap)[0]
 
     @staticmethod
     def _solid_lists(blocks, what: str):
@@ -614,14 +608,14 @@ class Context:
 
     @staticmethod
     def _solid_names(filenames, seg_first):
-        """The per-segment names of a solid call as a C array (None: no names)."""
+        """The per-segment names of a solid call as a flat list (None: no names)."""
         if filenames is None:
             return None
         flat, ff = Context._solid_lists(filenames, "filenames") if len(filenames) and not isinstance(filenames[0], (bytes, str)) \
             else (list(filenames), None)
         if (ff is not None and ff != list(seg_first)) or len(flat) != seg_first[-1]:
             raise ValueError("filenames needs one entry per segment")
-        return (C.c_char_p * max(1, len(flat)))(*[(f.encode() if isinstance(f, str) else f) for f in flat])
+        return flat
 
     def compress_solid_device(self, model, d_in: int, in_off: Sequence[int], seg_first: Sequence[int], d_out: int, out_cap: int, *,
                               d_orig: int = 0, orig_off: Optional[Sequence[int]] = None, filenames=None, sha1: bool = True,
@@ -641,21 +635,10 @@ class Context:
         ooffs = np.ascontiguousarray(orig_off, dtype=np.uint64) if orig_off is not None else None
         if ooffs is not None and ooffs.size != coffs.size:
             raise ValueError("orig_off needs one entry per entry of in_off")
-        names = self._solid_names(filenames, [int(x) for x in sf])
-        o = CompressOpts()
-        o.struct_size = C.sizeof(CompressOpts)
-        o.flags, o.kernel, o.batch_blocks, o.slot_bytes, o.enc_waves = compress_flags(sha1, tag), kernel, batch_blocks, slot_bytes, enc_waves
-        hdr = _as_u8(m.header)
-        pc = _as_u8(m.pcomp) if m.pcomp else None
-        boffs = np.zeros(n + 1, np.uint64)
-        err, got = Err(), C.c_size_t(0)
-        rc = self._L.zpaqhip_compress_solid_blocks_device(
-            self._h, hdr.ctypes.data, hdr.size, pc.ctypes.data if pc is not None else None, pc.size if pc is not None else 0,
-            d_in or None, coffs.ctypes.data, sf.ctypes.data, n, d_orig or None, ooffs.ctypes.data if ooffs is not None else None,
-            names, d_out or None, out_cap, C.byref(got), boffs.ctypes.data, C.byref(o), hip_stream or None, C.byref(err))
-        if rc and rc != -20 and raise_on_error:
-            _raise(err, rc)
-        return rc, got.value, boffs
+        entry = self._entry(m.header, m.pcomp or b"", src=d_in or None, in_off=coffs, seg_first=sf, orig=d_orig or None,
+                            orig_off=ooffs, names=self._solid_names(filenames, [int(x) for x in sf]), n=n,
+                            opts=(compress_flags(sha1, tag), kernel, batch_blocks, slot_bytes, enc_waves), device=True)
+        return self._run_device(entry, n, d_out, out_cap, hip_stream, raise_on_error)
 
     @staticmethod
     def _verify_model(model_or_method):

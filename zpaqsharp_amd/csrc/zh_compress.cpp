@@ -1,11 +1,13 @@
 // zh_compress.cpp — zpaqhip_compress_blocks: Compressor.startBlock / startSegment / postProcess / compress / endSegment /
 // endBlock (Compressor.cs:27-299) for a batch of blocks, one segment each (LibZPAQ.cs:296-323 framing), coded on the GPU;
 // zpaqhip_compress_solid_blocks, the same with several segments per block (startSegment .. endSegment repeated);
-// and what zh_compress.h shares with the method path (zh_pre.cpp).
+// and what zh_compress.h shares with the method path (zh_pre.cpp).  There is one path: every call carries a segment table,
+// and a block of one segment is a solid block with n_seg == 1 (the identity table).  Still one segment per block only: the
+// method path (`pre`), the store layout and the window-parallel encoder.
 //
 // The host validates the header with the decoder's framing code and then, batch by batch (Call's steps below): plans the
 // batch from the device budget, stages the coded sequences (a host copy, or the pre-processing stage on the device),
-// takes the SHA-1s, picks an encoder per block (route_encode) and launches the encoders, re-encodes a block whose slot was
+// locates the plaintext, takes the SHA-1s, picks an encoder per block (route_encode) and launches the encoders, re-encodes a block whose slot was
 // too small with a worst-case slot (on the chain encoder if it ran there, else on the generic one), and writes tag, block,
 // segment and end framing around each slot's bytes.  Every coded byte comes out of a HIP kernel (zh_enc_cm.hip, zh_enc_chain.hip, zh_enc_generic.hip); there is
 // no CPU encoder here.
@@ -126,11 +128,6 @@ ChainPlan plan_chain(const ZhModel &m) {
 uint64_t auto_slot(uint64_t coded) { return coded + coded / 8 + 4096; }
 uint64_t worst_slot(uint64_t coded) { return 16 * coded + 4096; }    // 2 bytes per coded bit, plus the end of segment
 
-uint8_t *put(uint8_t *w, const std::string &s) {
-  memcpy(w, s.data(), s.size());
-  return w + s.size();
-}
-
 // One launch of the encoders over blocks of a batch: what the host lays out, the device buffers, and the results
 struct EncRun {
   std::vector<ZhEncBlock> desc;           // the CM blocks first (blockIdx = index), then the chain encoder's, then the generic
@@ -143,13 +140,22 @@ struct EncRun {
   DevMem slots, d_desc, d_res, queue, arena, chain_arena, la, lb, bases, P;   // (d_desc: desc, then segs; d_res: res, then seg_end)
 };
 
+// Where on the device the plaintext of a batch lies: segment k of the batch (in segment order) is seg[2k + 1] bytes at
+// base + seg[2k], the pairs sha1_segments takes
+struct PlainView {
+  const uint8_t *base = nullptr;
+  std::vector<uint64_t> seg;
+};
+
 struct Batch {                            // blocks [b0, b1) of the call
   size_t b0 = 0, b1 = 0;
   std::vector<uint64_t> boff, blen;       // the coded sequence of block b0 + j in d_in (store layout: its pre-processed bytes)
   uint64_t in_total = 0;
   DevMem d_in;
   PreBatch pre;
-  std::vector<uint32_t> digest;           // five words per block, in block order (the solid form: per segment)
+  PlainView plain;                        // what the size comments and SHA-1s describe (Call::locate)
+  DevMem d_orig;                          // ... when it came from the host: the batch's range of `orig`, uploaded once
+  std::vector<uint32_t> digest;           // five words per segment, in segment order
   EncRun first, redo;                     // every block with its own slot; the overflowed ones again with worst-case slots
   std::vector<size_t> slot_of;            // j -> index in `first`
   std::vector<int64_t> redo_of;           // index in `first` -> index in `redo`, or -1
@@ -157,18 +163,10 @@ struct Batch {                            // blocks [b0, b1) of the call
 };
 
 // One call of compress_impl: its arguments, what it keeps on the device for all batches, and the steps of a batch
-struct Call {
-  const uint8_t *hdr; size_t hdr_len;
-  const uint8_t *in; const uint64_t *in_off; size_t n_blocks;
-  const uint8_t *orig; const uint64_t *orig_off;
-  const char *const *filenames;
-  uint8_t *out; size_t out_cap; uint64_t *block_off;
-  DevPre *pre;
-  zpaqhip_err *err;
+struct Call : CompressCall {
   zpaqhip_compress_opts o;
-  bool dev_in = false, dev_out = false;   // the device form: `in` and `orig`, `out` are device memory; stage and frame differ
-  hipStream_t user_stream = nullptr;
-  DevSink *sink = nullptr;                // the device form appends to it instead of writing to `out`
+  const bool dev_in, dev_out;             // the device form: `in` and `orig`, `out` are device memory; stage and frame differ
+  DevSink *const sink;                    // the device form appends to it instead of writing to `out`
   uint32_t pack_launches = 0;             // zh_frame.hip's launches, of staging and of framing
   uint32_t verify_launches = 0;           // the verify pass's (opts.flags bit 5)
   ZhModel M;
@@ -184,17 +182,30 @@ struct Call {
   zpaqhip_stats st{};
   uint64_t pos = 0;                       // bytes of the stream so far
   bool any_cm = false, any_chain = false;
-  // the solid form: block i holds the segments [seg_first[i], seg_first[i + 1]); seg_in, seg_orig (optional) and filenames
-  // are per segment, in_off and orig_off above the blocks' view of them
-  const uint64_t *seg_first = nullptr, *seg_in = nullptr, *seg_orig = nullptr;
+  // The segment table: block i holds the segments [seg_first[i], seg_first[i + 1]); seg_in, seg_orig (NULL without `orig`)
+  // and filenames are per segment, in_off and orig_off the blocks' view of them.  The solid form brings its own; every
+  // other call gets the identity, one segment per block, over its in_off and orig_off.
+  std::vector<uint64_t> ident;
+  const uint64_t *seg_first, *seg_in, *seg_orig;
   DevMem d_model_chain;                   // a ZH_FAM_CM1 model as the lane-per-component encoder takes it
   int cus = 0;                            // compute units: the chain encoder's LDS lets one of its workgroups live on each
   ChainPlan chain;                        // ... with this many waves at most
 
+  explicit Call(const CompressCall &a)
+      : CompressCall(a), o(resolve_compress_opts(a.opts)), dev_in(a.dev), dev_out(a.dev), sink(a.dev ? a.dev->sink : nullptr),
+        seg_first(a.solid ? a.solid->seg_first : nullptr), seg_in(a.solid ? a.solid->in_off : a.in_off),
+        seg_orig(a.solid ? a.solid->orig_off : a.orig_off) {
+    if (sink) pos = sink->used;
+    if (!solid) {
+      ident.resize(n_blocks + 1);
+      for (size_t i = 0; i <= n_blocks; ++i) ident[i] = i;
+      seg_first = ident.data();
+    }
+  }
   bool want_sha() const { return (o.flags & 1) != 0; }
   bool want_verify() const { return (o.flags & kFlagVerify) != 0; }
-  size_t seg_lo(size_t i) const { return seg_first ? seg_first[i] : i; }
-  size_t n_seg(size_t i) const { return seg_first ? seg_first[i + 1] - seg_first[i] : 1; }
+  size_t seg_lo(size_t i) const { return seg_first[i]; }
+  size_t n_seg(size_t i) const { return seg_first[i + 1] - seg_first[i]; }
   uint64_t seg_plain(size_t s) const { return seg_orig ? seg_orig[s + 1] - seg_orig[s] : seg_in[s + 1] - seg_in[s]; }
   uint64_t in_len(size_t i) const { return in_off[i + 1] - in_off[i]; }
   uint64_t plain_len(size_t i) const { return orig ? orig_off[i + 1] - orig_off[i] : in_len(i); }
@@ -209,24 +220,23 @@ struct Call {
     return c + 24 * n_seg(i);
   }
 
-  int open(zpaqhip_ctx *ctx);
+  int open();
   int plan(Batch &B, size_t b0) const;
   int stage(Batch &B);
+  int locate(Batch &B) const;
   int digests(Batch &B) const;
-  int digests_solid(Batch &B) const;
   int verify(Batch &B);
   int encode(const Batch &B, EncRun &r);
   int encode_batch(Batch &B);
   int retry(Batch &B);
   int pack(const FrameTable &T, const Batch &B, uint8_t *d_dst, float *ms);
   int frame(Batch &B);
-  int frame_solid(Batch &B);
 };
 
 // the device, the model for the generic encoder and what the CM encoder needs of it, the budget
-int Call::open(zpaqhip_ctx *ctx) {
+int Call::open() {
   v = ctx_view(ctx);
-  if (user_stream) v.stream = user_stream;
+  if (dev && dev->stream) v.stream = dev->stream;
   HIPCHK(hipSetDevice(v.device));
   st.blocks = n_blocks;
   if (!store) {
@@ -245,7 +255,7 @@ int Call::open(zpaqhip_ctx *ctx) {
   HIPCHK(device_budget(v.mem_share, 0, &budget));
   arena_stride = align_up(M.arena_bytes, 256);
   chain = plan_chain(M);
-  if (seg_first && (M.kind & 255u) == ZH_FAM_CM1) {
+  if (solid && (M.kind & 255u) == ZH_FAM_CM1) {
     // a single CM is a chain of one component without ICM / ISSE units; that encoder reads a translated HCOMP's id from
     // bits 8-15 of the kind, where this family keeps something else: 0 there has it interpret the program
     ZhModel Mc = M;
@@ -311,67 +321,53 @@ int Call::stage(Batch &B) {
   return ZPAQHIP_OK;
 }
 
-// SHA-1 of what the size comment describes (Compressor.endSegment): the plaintext the pre-processing left on the device,
-// `orig`, or the coded bytes behind the prefix
-int Call::digests(Batch &B) const {
-  if (!want_sha()) return ZPAQHIP_OK;
-  if (seg_first) return digests_solid(B);
-  const size_t nb = B.nb(), np = dev_prefix.size();
-  std::vector<uint64_t> seg(2 * nb);
-  for (size_t j = 0; j < nb; ++j) seg[2 * j + 1] = plain_len(B.b0 + j);
+// Where the plaintext is that the size comments and SHA-1s of the batch describe (Compressor.endSegment), decided once for
+// digests and verify: the plaintext the pre-processing left on the device, the coded bytes behind the prefix (a block's
+// segments lie back to back there), `orig` where the caller has it on the device, or the batch's range of a host `orig`,
+// uploaded here as it is.  The segments then start wherever the caller's offsets put them: zh_sha1_dev.hip and the verify
+// pass take unaligned starts, as the device form has always given them.  (zh_sha1_dev.hip loads 16 bytes at a time only
+// from a 4-byte aligned start and single bytes otherwise: a host `orig`, which an earlier form of this upload aligned
+// block by block, now mostly takes the byte path.  Correct either way; the kernel's time on that path is not measured.)
+int Call::locate(Batch &B) const {
+  if (!want_sha() && !want_verify()) return ZPAQHIP_OK;
+  const size_t sa = seg_first[B.b0], sb = seg_first[B.b1], np = dev_prefix.size();
+  PlainView &P = B.plain;
+  P.seg.resize(2 * (sb - sa));
+  for (size_t s = sa; s < sb; ++s) P.seg[2 * (s - sa) + 1] = seg_plain(s);
   if (pre) {
-    for (size_t j = 0; j < nb; ++j) seg[2 * j] = in_off[B.b0 + j] - in_off[B.b0];
-    return sha1_segments(v, B.pre.plain, seg, B.digest, err);
+    P.base = B.pre.plain;
+    for (size_t s = sa; s < sb; ++s) P.seg[2 * (s - sa)] = seg_in[s] - seg_in[sa];
+  } else if (!orig) {
+    P.base = B.d_in.as<uint8_t>();
+    for (size_t j = 0; j < B.nb(); ++j)
+      for (size_t s = seg_lo(B.b0 + j); s < seg_lo(B.b0 + j + 1); ++s)
+        P.seg[2 * (s - sa)] = B.boff[j] + np + (seg_in[s] - seg_in[seg_lo(B.b0 + j)]);
+  } else if (dev_in) {
+    P.base = orig;
+    for (size_t s = sa; s < sb; ++s) P.seg[2 * (s - sa)] = seg_orig[s];
+  } else {
+    const uint64_t base = seg_orig[sa], bytes = seg_orig[sb] - base;
+    HIPCHK(B.d_orig.alloc(bytes + 16));
+    if (bytes) HIPCHK(hipMemcpy(B.d_orig.p, orig + base, bytes, hipMemcpyHostToDevice));
+    P.base = B.d_orig.as<uint8_t>();
+    for (size_t s = sa; s < sb; ++s) P.seg[2 * (s - sa)] = seg_orig[s] - base;
   }
-  if (!orig) {
-    for (size_t j = 0; j < nb; ++j) seg[2 * j] = B.boff[j] + np;
-    return sha1_segments(v, B.d_in.as<uint8_t>(), seg, B.digest, err);
-  }
-  if (dev_in) {                           // where the caller has it
-    for (size_t j = 0; j < nb; ++j) seg[2 * j] = orig_off[B.b0 + j];
-    return sha1_segments(v, orig, seg, B.digest, err);
-  }
-  uint64_t total = 0;
-  for (size_t j = 0; j < nb; ++j) { seg[2 * j] = total; total += align_up(seg[2 * j + 1], 16); }
-  std::vector<uint8_t> h_orig(total);
-  for (size_t j = 0; j < nb; ++j)
-    if (seg[2 * j + 1]) memcpy(h_orig.data() + seg[2 * j], orig + orig_off[B.b0 + j], seg[2 * j + 1]);
-  DevMem d_orig;
-  HIPCHK(d_orig.alloc(total));
-  HIPCHK(hipMemcpy(d_orig.p, h_orig.data(), total, hipMemcpyHostToDevice));
-  return sha1_segments(v, d_orig.as<uint8_t>(), seg, B.digest, err);
+  return ZPAQHIP_OK;
 }
 
-// ... and of the solid form: a digest per segment of the batch, over the same bytes
-int Call::digests_solid(Batch &B) const {
-  const size_t sa = seg_first[B.b0], sb = seg_first[B.b1], np = dev_prefix.size();
-  std::vector<uint64_t> seg(2 * (sb - sa));
-  for (size_t s = sa; s < sb; ++s) seg[2 * (s - sa) + 1] = seg_plain(s);
-  if (!orig) {                            // a block's segments lie back to back behind its prefix
-    for (size_t j = 0; j < B.nb(); ++j)
-      for (size_t s = seg_first[B.b0 + j]; s < seg_first[B.b0 + j + 1]; ++s)
-        seg[2 * (s - sa)] = B.boff[j] + np + (seg_in[s] - seg_in[seg_first[B.b0 + j]]);
-    return sha1_segments(v, B.d_in.as<uint8_t>(), seg, B.digest, err);
-  }
-  if (dev_in) {
-    for (size_t s = sa; s < sb; ++s) seg[2 * (s - sa)] = seg_orig[s];
-    return sha1_segments(v, orig, seg, B.digest, err);
-  }
-  const uint64_t base = seg_orig[sa], bytes = seg_orig[sb] - base;
-  for (size_t s = sa; s < sb; ++s) seg[2 * (s - sa)] = seg_orig[s] - base;
-  DevMem d_orig;
-  HIPCHK(d_orig.alloc(bytes + 16));
-  if (bytes) HIPCHK(hipMemcpy(d_orig.p, orig + base, bytes, hipMemcpyHostToDevice));
-  return sha1_segments(v, d_orig.as<uint8_t>(), seg, B.digest, err);
+// a SHA-1 per segment of the batch
+int Call::digests(Batch &B) const {
+  return want_sha() ? sha1_segments(v, B.plain.base, B.plain.seg, B.digest, err) : ZPAQHIP_OK;
 }
 
 // opts.flags bit 5 (Compressor.setVerify): the batch's coded sequences through the block's own post-processor, against the
-// plaintext the size comment and SHA-1 describe; the lowest failing block ends the call
+// plaintext the size comment and SHA-1 describe; the lowest failing block ends the call.  (One segment per block: the
+// solid entry points refuse the flag.)
 int Call::verify(Batch &B) {
   if (!want_verify()) return ZPAQHIP_OK;
-  const size_t nb = B.nb(), np = dev_prefix.size();
+  const size_t nb = B.nb();
   VerifyIn vin;
-  DevMem d_stage, d_orig;
+  DevMem d_stage;
   if (store) {                            // (the store layout keeps the selector on the host: a copy with it in front)
     if (const int rc = verify_stage(v, sel, B.d_in.as<uint8_t>(), B.boff, B.blen, d_stage, vin, &verify_launches, err)) return rc;
   } else {
@@ -379,24 +375,10 @@ int Call::verify(Batch &B) {
     vin.off = B.boff;
     vin.len = B.blen;
   }
-  vin.poff.resize(nb);
-  vin.plen.resize(nb);
-  for (size_t j = 0; j < nb; ++j) vin.plen[j] = plain_len(B.b0 + j);
-  if (pre) {
-    vin.d_plain = B.pre.plain;
-    for (size_t j = 0; j < nb; ++j) vin.poff[j] = in_off[B.b0 + j] - in_off[B.b0];
-  } else if (!orig) {                     // the coded bytes behind the prefix are what the segment describes
-    vin.d_plain = B.d_in.as<uint8_t>();
-    for (size_t j = 0; j < nb; ++j) vin.poff[j] = B.boff[j] + np;
-  } else if (dev_in) {
-    vin.d_plain = orig;
-    for (size_t j = 0; j < nb; ++j) vin.poff[j] = orig_off[B.b0 + j];
-  } else {
-    const uint64_t base = orig_off[B.b0], bytes = orig_off[B.b1] - base;
-    HIPCHK(d_orig.alloc(bytes + 16));
-    if (bytes) HIPCHK(hipMemcpy(d_orig.p, orig + base, bytes, hipMemcpyHostToDevice));
-    vin.d_plain = d_orig.as<uint8_t>();
-    for (size_t j = 0; j < nb; ++j) vin.poff[j] = orig_off[B.b0 + j] - base;
+  vin.d_plain = B.plain.base;
+  for (size_t j = 0; j < nb; ++j) {
+    vin.poff.push_back(B.plain.seg[2 * j]);
+    vin.plen.push_back(B.plain.seg[2 * j + 1]);
   }
   std::vector<zpaqhip_verify_result> rec;
   uint64_t wrote = 0;
@@ -544,18 +526,16 @@ int Call::encode_batch(Batch &B) {
     r.slot_total += align_up(d.slot_cap, 256);
     d.scr_off = r.scr_total;
     if (k < r.n_cm) r.scr_total += align_up(d.n, 4);
-    // its segments: the whole coded sequence, or the solid form's, back to back with the prefix in the first
-    const size_t i = r.block[k], ns = n_seg(i);
+    // its segments, back to back with the prefix in the first; with pre a block is one segment of the length the
+    // pre-processing gave it
+    const size_t i = r.block[k];
     d.seg0 = (uint32_t)r.segs.size();
-    d.n_seg = (uint32_t)ns;
-    if (!seg_first) r.segs.push_back({d.in_off, d.n});
-    else {
-      uint64_t at = d.in_off;
-      for (size_t s = seg_first[i]; s < seg_first[i + 1]; ++s) {
-        const uint64_t len = seg_in[s + 1] - seg_in[s] + (s == seg_first[i] ? dev_prefix.size() : 0);
-        r.segs.push_back({at, len});
-        at += len;
-      }
+    d.n_seg = (uint32_t)n_seg(i);
+    uint64_t at = d.in_off;
+    for (size_t s = seg_lo(i); s < seg_lo(i + 1); ++s) {
+      const uint64_t len = pre ? d.n : seg_in[s + 1] - seg_in[s] + (s == seg_lo(i) ? dev_prefix.size() : 0);
+      r.segs.push_back({at, len});
+      at += len;
     }
   }
   return encode(B, r);
@@ -624,25 +604,32 @@ int Call::pack(const FrameTable &T, const Batch &B, uint8_t *d_dst, float *ms) {
   return ZPAQHIP_OK;
 }
 
-// framing around each block's coded bytes, in block order: the frame table says what goes where; the host form copies by
-// it, the device form hands it to the packing kernel
+// framing around each block's coded bytes, in block order: an entry of the frame table per segment, cut out of the
+// block's slot at the ends the encoder recorded (the retry's when the block went again; store layout: the block's
+// pre-processed bytes, whole); the host form copies by the table, the device form hands it to the packing kernel
 int Call::frame(Batch &B) {
-  if (seg_first) return frame_solid(B);
-  std::vector<FrameItem> items;
-  items.reserve(B.nb());
+  std::vector<TableBlock> items(B.nb());
+  const size_t sa = seg_first[B.b0];
   for (size_t j = 0; j < B.nb(); ++j) {
     const size_t i = B.b0 + j, k = store ? 0 : B.slot_of[j];
     const int64_t redo = store ? -1 : B.redo_of[k];
-    BlockFrame f((o.flags & 2) != 0, store ? 2 : 1, hdr, hdr_len, filenames ? filenames[i] : nullptr, plain_len(i),
-                 want_sha() ? &B.digest[5 * j] : nullptr);
-    if (store) items.push_back({std::move(f), ZH_FRAME_SRC_PRE, B.boff[j], B.blen[j]});
-    else if (redo >= 0) items.push_back({std::move(f), ZH_FRAME_SRC_REDO, B.redo.desc[redo].slot_off, B.redo.res[redo].len});
-    else items.push_back({std::move(f), ZH_FRAME_SRC_FIRST, B.first.desc[k].slot_off, B.first.res[k].len});
+    const EncRun &r = redo >= 0 ? B.redo : B.first;
+    TableBlock &it = items[j];
+    it.src = store ? ZH_FRAME_SRC_PRE : redo >= 0 ? ZH_FRAME_SRC_REDO : ZH_FRAME_SRC_FIRST;
+    it.src_off = store ? B.boff[j] : r.desc[redo >= 0 ? (size_t)redo : k].slot_off;
+    for (size_t s = seg_lo(i); s < seg_lo(i + 1); ++s)
+      it.seg.push_back({filenames ? filenames[s] : nullptr, seg_plain(s), want_sha() ? &B.digest[5 * (s - sa)] : nullptr,
+                        store ? B.blen[j] : r.seg_end[r.desc[redo >= 0 ? (size_t)redo : k].seg0 + (s - seg_lo(i))]});
     st.in_bytes += plain_len(i);
   }
   const uint64_t pos0 = pos;
   FrameTable T;
-  pos = build_frame_table(items, store ? &sel : nullptr, pos0, sink ? ~0ull : out_cap, T, block_off ? block_off + B.b0 : nullptr);
+  pos = build_frame_table((o.flags & 2) != 0, store ? 2 : 1, hdr, hdr_len, items, store ? &sel : nullptr, pos0, sink ? ~0ull : out_cap, T,
+                          block_off ? block_off + B.b0 : nullptr);
+  if (pos == kFrameRefused) {             // (not reached: the store layout needs pre, which the solid entry points refuse)
+    set_err(err, ZPAQHIP_E_ARG, (int)B.b0, -1, "the store layout takes one segment per block");
+    return ZPAQHIP_E_ARG;
+  }
   if (sink) {                             // room for the batch behind what the sink holds
     if (sink->reserve(pos, pos0, v.stream) != hipSuccess) {
       (void)hipGetLastError();
@@ -658,68 +645,25 @@ int Call::frame(Batch &B) {
     return rc;
   }
   // the batch's slots (store layout: its pre-processed bytes) in one copy, unless nothing more fits in `out` (the call
-  // then only counts the bytes it needs)
+  // then only counts the bytes it needs); a retry's slot is fetched on its own
   const DevMem &d_src = store ? B.d_in : B.first.slots;
   std::vector<uint8_t> h_src;
   if (pos0 < out_cap) {
     h_src.resize(store ? B.in_total : B.first.slot_total);
     HIPCHK(hipMemcpy(h_src.data(), d_src.p, h_src.size(), hipMemcpyDeviceToHost));
   }
-  for (size_t n = 0; n < T.entry.size(); ++n) {
-    const ZhFrameEntry &e = T.entry[n];
-    const BlockFrame &f = items[T.item[n]].f;
-    uint8_t *w = put(out + e.dst_off, f.head);
-    uint64_t body = e.body_len;
-    if (store) {
-      write_store_body(w, sel, h_src.data() + e.src_off, e.body_len);
-      body = store_body_len(sel.size() + e.body_len);
-    } else if (e.src == ZH_FRAME_SRC_REDO) HIPCHK(hipMemcpy(w, B.redo.slots.as<uint8_t>() + e.src_off, body, hipMemcpyDeviceToHost));
-    else if (body) memcpy(w, h_src.data() + e.src_off, body);
-    put(w + body, f.tail);
-  }
-  return ZPAQHIP_OK;
-}
-
-// ... and of the solid form: an entry per segment, cut out of the block's slot at the ends the encoder recorded (the retry's
-// when the block went again); heads and tails come from the table's blob
-int Call::frame_solid(Batch &B) {
-  std::vector<SolidItem> items(B.nb());
-  const size_t sa = seg_first[B.b0];
-  for (size_t j = 0; j < B.nb(); ++j) {
-    const size_t i = B.b0 + j, k = B.slot_of[j];
-    const int64_t redo = B.redo_of[k];
-    const EncRun &r = redo >= 0 ? B.redo : B.first;
-    const ZhEncBlock &d = r.desc[redo >= 0 ? (size_t)redo : k];
-    SolidItem &it = items[j];
-    it.src = redo >= 0 ? ZH_FRAME_SRC_REDO : ZH_FRAME_SRC_FIRST;
-    it.src_off = d.slot_off;
-    for (size_t s = seg_first[i]; s < seg_first[i + 1]; ++s)
-      it.seg.push_back({filenames ? filenames[s] : nullptr, seg_plain(s), want_sha() ? &B.digest[5 * (s - sa)] : nullptr,
-                        r.seg_end[d.seg0 + (s - seg_first[i])]});
-    st.in_bytes += plain_len(i);
-  }
-  const uint64_t pos0 = pos;
-  FrameTable T;
-  pos = build_solid_frame_table((o.flags & 2) != 0, hdr, hdr_len, items, pos0, out_cap, T, block_off ? block_off + B.b0 : nullptr);
-  if (dev_out) {
-    float ms = 0;
-    const int rc = pack(T, B, out, &ms);
-    st.kernel_ms += ms;
-    return rc;
-  }
-  std::vector<uint8_t> h_src;
-  if (pos0 < out_cap) {
-    h_src.resize(B.first.slot_total);
-    HIPCHK(hipMemcpy(h_src.data(), B.first.slots.p, h_src.size(), hipMemcpyDeviceToHost));
-  }
   for (const ZhFrameEntry &e : T.entry) {
     uint8_t *w = out + e.dst_off;
     memcpy(w, T.blob.data() + e.head_off, e.head_len);
     w += e.head_len;
-    if (e.src == ZH_FRAME_SRC_REDO) {
-      if (e.body_len) HIPCHK(hipMemcpy(w, B.redo.slots.as<uint8_t>() + e.src_off, e.body_len, hipMemcpyDeviceToHost));
-    } else if (e.body_len) memcpy(w, h_src.data() + e.src_off, e.body_len);
-    memcpy(w + e.body_len, T.blob.data() + e.tail_off, e.tail_len);
+    uint64_t body = e.body_len;
+    if (store) {
+      write_store_body(w, sel, h_src.data() + e.src_off, body);
+      body = store_body_len(sel.size() + body);
+    } else if (e.src == ZH_FRAME_SRC_REDO) {
+      if (body) HIPCHK(hipMemcpy(w, B.redo.slots.as<uint8_t>() + e.src_off, body, hipMemcpyDeviceToHost));
+    } else if (body) memcpy(w, h_src.data() + e.src_off, body);
+    memcpy(w + body, T.blob.data() + e.tail_off, e.tail_len);
   }
   return ZPAQHIP_OK;
 }
@@ -746,8 +690,11 @@ extern "C" int zpaqhip_compress_blocks(zpaqhip_ctx *ctx, const uint8_t *hdr, siz
                                        const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
                                        uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
                                        const zpaqhip_compress_opts *opts, zpaqhip_err *err) {
-  return compress_impl(ctx, hdr, hdr_len, pcomp, pcomp_len, in, in_off, n_blocks, orig, orig_off, filenames, out, out_cap, out_len,
-                       block_off, opts, nullptr, err);
+  CompressCall a;
+  a.ctx = ctx; a.hdr = hdr; a.hdr_len = hdr_len; a.pcomp = pcomp; a.pcomp_len = pcomp_len;
+  a.in = in; a.in_off = in_off; a.n_blocks = n_blocks; a.orig = orig; a.orig_off = orig_off; a.filenames = filenames;
+  a.out = out; a.out_cap = out_cap; a.out_len = out_len; a.block_off = block_off; a.opts = opts; a.err = err;
+  return compress_impl(a);
 }
 
 extern "C" int zpaqhip_compress_blocks_device(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp,
@@ -756,23 +703,28 @@ extern "C" int zpaqhip_compress_blocks_device(zpaqhip_ctx *ctx, const uint8_t *h
                                               void *d_out, size_t out_cap, size_t *out_len, uint64_t *block_off,
                                               const zpaqhip_compress_opts *opts, void *hip_stream, zpaqhip_err *err) {
   const DeviceEnds dev{(hipStream_t)hip_stream};
-  return compress_impl(ctx, hdr, hdr_len, pcomp, pcomp_len, (const uint8_t *)d_in, in_off, n_blocks, (const uint8_t *)d_orig, orig_off,
-                       filenames, (uint8_t *)d_out, out_cap, out_len, block_off, opts, nullptr, err, &dev);
+  CompressCall a;
+  a.ctx = ctx; a.hdr = hdr; a.hdr_len = hdr_len; a.pcomp = pcomp; a.pcomp_len = pcomp_len;
+  a.in = (const uint8_t *)d_in; a.in_off = in_off; a.n_blocks = n_blocks; a.orig = (const uint8_t *)d_orig; a.orig_off = orig_off;
+  a.filenames = filenames; a.out = (uint8_t *)d_out; a.out_cap = out_cap; a.out_len = out_len; a.block_off = block_off;
+  a.opts = opts; a.err = err; a.dev = &dev;
+  return compress_impl(a);
 }
 
 namespace {
 
-// The solid entry points: the checks of the segment tables, the blocks' view of the per-segment offsets, compress_impl
-int solid_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len, const uint8_t *in,
-               const uint64_t *in_off, const uint64_t *seg_first, size_t n_blocks, const uint8_t *orig, const uint64_t *orig_off,
-               const char *const *filenames, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
-               const zpaqhip_compress_opts *opts, zpaqhip_err *err, const DeviceEnds *dev) {
-  if (!ctx || !hdr || !out_len || (!out && out_cap) || (n_blocks && (!in_off || !seg_first)) || (orig && !orig_off)) {
+// The solid entry points: the checks of the segment tables, the blocks' view of the per-segment offsets, compress_impl.
+// `a` comes with the per-segment in_off and orig_off.
+int solid_impl(CompressCall a, const uint64_t *seg_first) {
+  zpaqhip_err *const err = a.err;
+  const size_t n_blocks = a.n_blocks;
+  const uint64_t *const in_off = a.in_off, *const orig_off = a.orig_off;
+  if (!a.ctx || !a.hdr || !a.out_len || (!a.out && a.out_cap) || (n_blocks && (!in_off || !seg_first)) || (a.orig && !orig_off)) {
     set_err(err, ZPAQHIP_E_ARG, -1, -1);
     return ZPAQHIP_E_ARG;
   }
-  *out_len = 0;
-  if (resolve_compress_opts(opts).flags & ~3u) {
+  *a.out_len = 0;
+  if (resolve_compress_opts(a.opts).flags & ~3u) {
     set_err(err, ZPAQHIP_E_ARG, -1, -1, "solid blocks take bits 0 and 1 of flags only (no method opt-ins, no verify)");
     return ZPAQHIP_E_ARG;
   }
@@ -786,19 +738,21 @@ int solid_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8
       return ZPAQHIP_E_ARG;
     }
     for (uint64_t s = seg_first[i]; s < seg_first[i + 1]; ++s)
-      if (in_off[s + 1] < in_off[s] || (orig && orig_off[s + 1] < orig_off[s])) {
+      if (in_off[s + 1] < in_off[s] || (a.orig && orig_off[s + 1] < orig_off[s])) {
         set_err(err, ZPAQHIP_E_ARG, (int)i, (int)(s - seg_first[i]), "segment offsets must not decrease");
         return ZPAQHIP_E_ARG;
       }
   }
-  std::vector<uint64_t> b_in(n_blocks + 1, 0), b_orig(orig ? n_blocks + 1 : 0, 0);
+  std::vector<uint64_t> b_in(n_blocks + 1, 0), b_orig(a.orig ? n_blocks + 1 : 0, 0);
   for (size_t i = 0; i <= n_blocks && n_blocks; ++i) {
     b_in[i] = in_off[seg_first[i]];
-    if (orig) b_orig[i] = orig_off[seg_first[i]];
+    if (a.orig) b_orig[i] = orig_off[seg_first[i]];
   }
-  const SolidSegs solid{seg_first, in_off, orig ? orig_off : nullptr};
-  return compress_impl(ctx, hdr, hdr_len, pcomp, pcomp_len, in, b_in.data(), n_blocks, orig, orig ? b_orig.data() : nullptr, filenames,
-                       out, out_cap, out_len, block_off, opts, nullptr, err, dev, &solid);
+  const SolidSegs solid{seg_first, in_off, a.orig ? orig_off : nullptr};
+  a.in_off = b_in.data();
+  a.orig_off = a.orig ? b_orig.data() : nullptr;
+  a.solid = &solid;
+  return compress_impl(a);
 }
 
 }  // namespace
@@ -808,8 +762,11 @@ extern "C" int zpaqhip_compress_solid_blocks(zpaqhip_ctx *ctx, const uint8_t *hd
                                              const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
                                              uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
                                              const zpaqhip_compress_opts *opts, zpaqhip_err *err) {
-  return solid_impl(ctx, hdr, hdr_len, pcomp, pcomp_len, in, in_off, seg_first, n_blocks, orig, orig_off, filenames, out, out_cap,
-                    out_len, block_off, opts, err, nullptr);
+  CompressCall a;
+  a.ctx = ctx; a.hdr = hdr; a.hdr_len = hdr_len; a.pcomp = pcomp; a.pcomp_len = pcomp_len;
+  a.in = in; a.in_off = in_off; a.n_blocks = n_blocks; a.orig = orig; a.orig_off = orig_off; a.filenames = filenames;
+  a.out = out; a.out_cap = out_cap; a.out_len = out_len; a.block_off = block_off; a.opts = opts; a.err = err;
+  return solid_impl(a, seg_first);
 }
 
 extern "C" int zpaqhip_compress_solid_blocks_device(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp,
@@ -819,66 +776,56 @@ extern "C" int zpaqhip_compress_solid_blocks_device(zpaqhip_ctx *ctx, const uint
                                                     size_t out_cap, size_t *out_len, uint64_t *block_off,
                                                     const zpaqhip_compress_opts *opts, void *hip_stream, zpaqhip_err *err) {
   const DeviceEnds dev{(hipStream_t)hip_stream};
-  return solid_impl(ctx, hdr, hdr_len, pcomp, pcomp_len, (const uint8_t *)d_in, in_off, seg_first, n_blocks, (const uint8_t *)d_orig,
-                    orig_off, filenames, (uint8_t *)d_out, out_cap, out_len, block_off, opts, err, &dev);
+  CompressCall a;
+  a.ctx = ctx; a.hdr = hdr; a.hdr_len = hdr_len; a.pcomp = pcomp; a.pcomp_len = pcomp_len;
+  a.in = (const uint8_t *)d_in; a.in_off = in_off; a.n_blocks = n_blocks; a.orig = (const uint8_t *)d_orig; a.orig_off = orig_off;
+  a.filenames = filenames; a.out = (uint8_t *)d_out; a.out_cap = out_cap; a.out_len = out_len; a.block_off = block_off;
+  a.opts = opts; a.err = err; a.dev = &dev;
+  return solid_impl(a, seg_first);
 }
 
-int zh::compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
-                      const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
-                      const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
-                      uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
-                      const zpaqhip_compress_opts *opts, DevPre *pre, zpaqhip_err *err, const DeviceEnds *dev, const SolidSegs *solid) {
-  if (!ctx || !hdr || !out_len || (!out && out_cap) || (n_blocks && !in_off) || (orig && !orig_off) || (pcomp_len && !pcomp) ||
-      pcomp_len > 65535) {
+int zh::compress_impl(const CompressCall &a) {
+  zpaqhip_err *const err = a.err;
+  if (!a.ctx || !a.hdr || !a.out_len || (!a.out && a.out_cap) || (a.n_blocks && !a.in_off) || (a.orig && !a.orig_off) ||
+      (a.pcomp_len && !a.pcomp) || a.pcomp_len > 65535) {
     set_err(err, ZPAQHIP_E_ARG, -1, -1);
     return ZPAQHIP_E_ARG;
   }
-  *out_len = 0;
-  if (resolve_compress_opts(opts).enc_waves > ZH_ENC_CHAIN_MAX_WAVES) {
+  *a.out_len = 0;
+  if (resolve_compress_opts(a.opts).enc_waves > ZH_ENC_CHAIN_MAX_WAVES) {
     set_err(err, ZPAQHIP_E_ARG, -1, -1, "enc_waves is 0 (automatic) or 1 to 4");
     return ZPAQHIP_E_ARG;
   }
-  for (size_t i = 0; i < n_blocks; ++i)
-    if (in_off[i + 1] < in_off[i] || (orig && orig_off[i + 1] < orig_off[i]) || (!in && in_off[i + 1] > in_off[i])) {
+  for (size_t i = 0; i < a.n_blocks; ++i)
+    if (a.in_off[i + 1] < a.in_off[i] || (a.orig && a.orig_off[i + 1] < a.orig_off[i]) || (!a.in && a.in_off[i + 1] > a.in_off[i])) {
       set_err(err, ZPAQHIP_E_ARG, (int)i, -1, "block offsets must not decrease");
       return ZPAQHIP_E_ARG;
     }
-  Call c{hdr, hdr_len, in, in_off, n_blocks, orig, orig_off, filenames, out, out_cap, block_off, pre, err, resolve_compress_opts(opts)};
-  if (solid) {
-    c.seg_first = solid->seg_first;
-    c.seg_in = solid->in_off;
-    c.seg_orig = solid->orig_off;
-  }
-  if (dev) {
-    c.dev_in = c.dev_out = true;
-    c.user_stream = dev->stream;
-    c.sink = dev->sink;
-    if (c.sink) c.pos = c.sink->used;
-  }
-  int rc = build_model(hdr, hdr_len, c.M, c.code, err);
+  Call c(a);
+  int rc = build_model(a.hdr, a.hdr_len, c.M, c.code, err);
   if (rc) return rc;
   c.store = c.M.n == 0;
-  if (c.store && !pre) {
+  if (c.store && !a.pre) {
     set_err(err, ZPAQHIP_E_ARG, -1, -1, "compress_blocks codes modelled blocks only (n >= 1)");
     return ZPAQHIP_E_ARG;
   }
   // The store layout splices the selector in on the host: the pre-processing then launches no prefix kernel, which
   // st.launches would count on this path.
-  c.sel = selector_prefix(pcomp, pcomp_len);
+  c.sel = selector_prefix(a.pcomp, a.pcomp_len);
   if (!c.store) c.dev_prefix = c.sel;
-  if ((rc = c.open(ctx))) return rc;
-  for (size_t b0 = 0; b0 < n_blocks;) {
+  if ((rc = c.open())) return rc;
+  for (size_t b0 = 0; b0 < a.n_blocks;) {
     Batch B;
-    if ((rc = c.plan(B, b0)) || (rc = c.stage(B)) || (rc = c.digests(B)) || (rc = c.verify(B))) return rc;
+    if ((rc = c.plan(B, b0)) || (rc = c.stage(B)) || (rc = c.locate(B)) || (rc = c.digests(B)) || (rc = c.verify(B))) return rc;
     if (!c.store && ((rc = c.encode_batch(B)) || (rc = c.retry(B)))) return rc;
     if ((rc = c.frame(B))) return rc;
     b0 = B.b1;
   }
   // A known wart, kept for zpaqhip_last_stats' sake: the store layout counts the pre-processing launches, the encoders' path
   // counts its own only.
-  if (c.store) c.st.launches = pre->launches;
+  if (c.store) c.st.launches = a.pre->launches;
   c.st.launches += c.pack_launches + c.verify_launches;
   c.st.kernel_kind = c.store ? 0 : c.any_chain ? 3 : c.any_cm ? 2 : 1;
   if (c.sink) c.sink->used = c.pos;
-  return finish_call(c.v, c.st, c.pos, n_blocks, block_off, c.sink ? ~(size_t)0 : out_cap, out_len, err);
+  return finish_call(c.v, c.st, c.pos, a.n_blocks, a.block_off, c.sink ? ~(size_t)0 : a.out_cap, a.out_len, err);
 }

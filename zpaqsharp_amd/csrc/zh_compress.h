@@ -114,10 +114,6 @@ class DevPre {
   DevMem starts_, arena_;                 // slot routes: the slot starts of every launch; zh_pre.cpp's SortArena
 };
 
-// The batch loop.  Without `pre`, block i's coded bytes are in[in_off[i], in_off[i+1]) and `orig`, when given, is what the
-// size comment and SHA-1 describe.  With `pre` (the method path) `in` is the plaintext and `orig` NULL; a header with n = 0
-// then gets the store layout instead of an encoder.  `dev`, when given, is the device form: `in`, `orig` and `out` are then
-// device pointers on the context's device, `pre` was made with in_dev, and the work runs on dev->stream when that is set.
 // A stream in device memory that a call owns and several compress_impl runs append to (the scratch of a mixed call): it
 // grows to what the runs turn out to need, keeping what it holds.
 struct DevSink {
@@ -131,15 +127,30 @@ struct DevSink {
 // there) and nothing is ever too small.
 struct DeviceEnds { hipStream_t stream = nullptr; DevSink *sink = nullptr; };
 // The solid form (zpaqhip_compress_solid_blocks): block i holds the segments [seg_first[i], seg_first[i + 1]), whose coded
-// bytes, described bytes and names the per-segment `in_off`, `orig_off` (NULL without `orig`) and compress_impl's
-// `filenames` give; compress_impl's own in_off / orig_off are then the blocks' view of them (in_off[seg_first[i]]).  Without
-// `pre` and without a sink only.
+// bytes, described bytes and names the per-segment `in_off`, `orig_off` (NULL without `orig`) and the call's `filenames`
+// give; the call's own in_off / orig_off are then the blocks' view of them (in_off[seg_first[i]]).  Without `pre` and
+// without a sink only.
 struct SolidSegs { const uint64_t *seg_first, *in_off, *orig_off; };
-int compress_impl(zpaqhip_ctx *ctx, const uint8_t *hdr, size_t hdr_len, const uint8_t *pcomp, size_t pcomp_len,
-                  const uint8_t *in, const uint64_t *in_off, size_t n_blocks,
-                  const uint8_t *orig, const uint64_t *orig_off, const char *const *filenames,
-                  uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *block_off,
-                  const zpaqhip_compress_opts *opts, DevPre *pre, zpaqhip_err *err, const DeviceEnds *dev = nullptr,
-                  const SolidSegs *solid = nullptr);
+
+// The batch loop and its arguments.  Without `pre`, block i's coded bytes are in[in_off[i], in_off[i+1]) and `orig`, when
+// given, is what the size comment and SHA-1 describe.  With `pre` (the method path) `in` is the plaintext and `orig` NULL; a
+// header with n = 0 then gets the store layout instead of an encoder.  `dev`, when given, is the device form: `in`, `orig`
+// and `out` are then device pointers on the context's device, `pre` was made with in_dev, and the work runs on dev->stream
+// when that is set.  Without `solid` every block is one segment.
+struct CompressCall {
+  zpaqhip_ctx *ctx = nullptr;
+  const uint8_t *hdr = nullptr; size_t hdr_len = 0;
+  const uint8_t *pcomp = nullptr; size_t pcomp_len = 0;
+  const uint8_t *in = nullptr; const uint64_t *in_off = nullptr; size_t n_blocks = 0;
+  const uint8_t *orig = nullptr; const uint64_t *orig_off = nullptr;
+  const char *const *filenames = nullptr;
+  uint8_t *out = nullptr; size_t out_cap = 0; size_t *out_len = nullptr; uint64_t *block_off = nullptr;
+  const zpaqhip_compress_opts *opts = nullptr;
+  DevPre *pre = nullptr;
+  zpaqhip_err *err = nullptr;
+  const DeviceEnds *dev = nullptr;
+  const SolidSegs *solid = nullptr;
+};
+int compress_impl(const CompressCall &a);
 
 }  // namespace zh

@@ -1,7 +1,7 @@
 // zh_frame.h — block framing: the bytes around a block's coded data (BlockFrame), the store layout, and the frame table
 // of a batch, which says where every block's head, body and tail go in the stream.  The host forms of the compressing entry
 // points copy by it on the host; the device forms upload it and zh_frame.hip packs the stream on the GPU.  Nothing here
-// needs HIP: zh_frame_table.cpp builds alone (tests/native/frame_table_main.cpp links it under the sanitizers).
+// needs HIP: zh_frame_table.cpp builds alone (the programs under tests/native link it under the sanitizers).
 #pragma once
 #include <stdint.h>
 
@@ -49,10 +49,8 @@ std::vector<uint8_t> selector_prefix(const uint8_t *pcomp, size_t pcomp_len);
 // with the size comment in `head`, end of segment (with the SHA-1 when `digest` gives its five words) and of block in `tail`.
 struct BlockFrame {
   std::string head, tail;
-  BlockFrame(bool tag, uint8_t level, const uint8_t *hdr, size_t hdr_len, const char *filename, uint64_t plain_len,
-             const uint32_t *digest);
-  // One segment of a block that holds several (Compressor.startSegment .. endSegment, repeated): tag and block header go
-  // in front of the `first` segment's head only, the end of block behind the `last` one's tail only.
+  // One segment of a block (Compressor.startSegment .. endSegment, repeated for a block that holds several): tag and block
+  // header go in front of the `first` segment's head only, the end of block behind the `last` one's tail only.
   BlockFrame(bool tag, uint8_t level, const uint8_t *hdr, size_t hdr_len, const char *filename, uint64_t plain_len,
              const uint32_t *digest, bool first, bool last);
 };
@@ -61,46 +59,39 @@ struct BlockFrame {
 uint64_t store_body_len(uint64_t decoded);
 void write_store_body(uint8_t *w, const std::vector<uint8_t> &sel, const uint8_t *pre, uint64_t pre_len);
 
-struct FrameItem {                        // one block of a batch as the framing sees it
-  BlockFrame f;
-  uint32_t src;                           // where its body lies, and how many bytes (store layout: the pre-processed bytes)
-  uint64_t src_off, src_len;
-};
-
-struct FrameTable {
-  std::vector<ZhFrameEntry> entry;        // the blocks that fit under out_cap, in block order
-  std::vector<size_t> item;               // entry[e] frames item[e] of the batch
-  std::vector<uint8_t> blob;              // the selector (store layout), then head and tail of every entry
-  uint64_t sel_len = 0;
-  uint32_t pieces = 1;
-};
-
-// The frame table of a batch whose first block starts at stream offset `pos`: block_pos[j] (optional) is where item j
-// starts, dst_off the same for the blocks that fit in whole under out_cap; one that does not fit is left out, later ones
-// that fit are in.  `sel` non-NULL selects the store layout.  Returns the stream offset behind the batch.
-uint64_t build_frame_table(const std::vector<FrameItem> &items, const std::vector<uint8_t> *sel, uint64_t pos, uint64_t out_cap,
-                           FrameTable &T, uint64_t *block_pos);
-
-// The solid form: a block of several segments whose coded bytes lie back to back in one slot.  Segment s of a block has the
-// bytes [seg[s - 1].end, seg[s].end) of the slot (from 0 for the first): `end` is the encoder's count right behind the
-// segment's end-of-segment bit (ZhEncLaunch::seg_end).
-struct SolidSeg {
+// One block of a batch as the framing sees it: its segments' coded bytes lie back to back at src_off of the buffer `src`
+// selects.  Segment s has the bytes [seg[s - 1].end, seg[s].end) of them (from 0 for the first): `end` is the encoder's count
+// right behind the segment's end-of-segment bit (ZhEncLaunch::seg_end), or, for the one segment of a block that no encoder
+// cut, the length of the whole (store layout: of the pre-processed bytes).
+struct TableSeg {
   const char *filename;                   // NULL = empty
   uint64_t plain_len;                     // the size comment
   const uint32_t *digest;                 // five words, or NULL = no SHA-1
   uint64_t end;
 };
-struct SolidItem {                        // one block of a batch
-  uint32_t src;                           // where its slot lies
+struct TableBlock {
+  uint32_t src;
   uint64_t src_off;
-  std::vector<SolidSeg> seg;              // at least one
+  std::vector<TableSeg> seg;              // at least one
 };
-// The frame table of such a batch: an entry per segment, head || body || tail as for build_frame_table, the first
-// segment's head behind the tag and the block header, the last one's tail in front of the end of block (BlockFrame writes
-// them all).  block_pos[j] (optional) is where block j starts; a block's entries are in the table when the WHOLE block
-// fits under out_cap, else none of them is; T.item[e] is the block of entry e.  Returns the stream offset behind the batch.
-uint64_t build_solid_frame_table(bool tag, const uint8_t *hdr, size_t hdr_len, const std::vector<SolidItem> &items, uint64_t pos,
-                                 uint64_t out_cap, FrameTable &T, uint64_t *block_pos);
+
+struct FrameTable {
+  std::vector<ZhFrameEntry> entry;        // the segments of the blocks that fit under out_cap, in stream order
+  std::vector<size_t> item;               // entry[e] frames a segment of item[e] of the batch
+  std::vector<uint8_t> blob;              // the selector (store layout), then head and tail of every entry
+  uint64_t sel_len = 0;
+  uint32_t pieces = 1;                    // 64 KiB pieces of the longest sel_len + body_len
+};
+
+// The frame table of a batch whose first block starts at stream offset `pos`: an entry per segment, head || body || tail,
+// the first segment's head behind the tag and the block header (with `level`), the last one's tail in front of the end of
+// block (BlockFrame writes them all).  block_pos[j] (optional) is where block j starts; a block's entries are in the table
+// when the WHOLE block fits under out_cap, else none of them is.  `sel` non-NULL selects the store layout, which is one
+// segment per block: a block of several is refused (kFrameRefused comes back, T is empty).  Returns the stream offset
+// behind the batch.
+constexpr uint64_t kFrameRefused = ~0ull;
+uint64_t build_frame_table(bool tag, uint8_t level, const uint8_t *hdr, size_t hdr_len, const std::vector<TableBlock> &items,
+                           const std::vector<uint8_t> *sel, uint64_t pos, uint64_t out_cap, FrameTable &T, uint64_t *block_pos);
 
 // The gather table of a mixed call (zpaqhip_compress_mixed_blocks_device): item i is block i of the call, framed already,
 // `len` bytes at `src_off` of the call's scratch stream, where the blocks lie group by group.  The stream has them in input

@@ -14,9 +14,6 @@ std::vector<uint8_t> zh::selector_prefix(const uint8_t *pcomp, size_t pcomp_len)
 }
 
 zh::BlockFrame::BlockFrame(bool tag, uint8_t level, const uint8_t *hdr, size_t hdr_len, const char *filename, uint64_t plain_len,
-                           const uint32_t *digest) : BlockFrame(tag, level, hdr, hdr_len, filename, plain_len, digest, true, true) {}
-
-zh::BlockFrame::BlockFrame(bool tag, uint8_t level, const uint8_t *hdr, size_t hdr_len, const char *filename, uint64_t plain_len,
                            const uint32_t *digest, bool first, bool last) : tail(4, '\0') {
   static constexpr uint8_t kTag[13] = {0x37, 0x6b, 0x53, 0x74, 0xa0, 0x31, 0x83, 0xd3, 0x8c, 0xb2, 0x28, 0xb0, 0xd3};   // Compressor.cs:27-43
   if (first) {
@@ -53,57 +50,30 @@ void zh::write_store_body(uint8_t *w, const std::vector<uint8_t> &sel, const uin
   }
 }
 
-uint64_t zh::build_frame_table(const std::vector<FrameItem> &items, const std::vector<uint8_t> *sel, uint64_t pos, uint64_t out_cap,
-                               FrameTable &T, uint64_t *block_pos) {
+uint64_t zh::build_frame_table(bool tag, uint8_t level, const uint8_t *hdr, size_t hdr_len, const std::vector<TableBlock> &items,
+                               const std::vector<uint8_t> *sel, uint64_t pos, uint64_t out_cap, FrameTable &T, uint64_t *block_pos) {
   T = FrameTable();
   if (sel) {
+    for (const TableBlock &it : items)
+      if (it.seg.size() != 1) return kFrameRefused;
     T.blob = *sel;
     T.sel_len = sel->size();
   }
   for (size_t j = 0; j < items.size(); ++j) {
-    const FrameItem &it = items[j];
-    const uint64_t decoded = T.sel_len + it.src_len, body = sel ? store_body_len(decoded) : it.src_len;
-    const uint64_t need = it.f.head.size() + body + it.f.tail.size();
-    if (block_pos) block_pos[j] = pos;
-    if (need <= out_cap && pos <= out_cap - need) {
-      ZhFrameEntry e;
-      memset(&e, 0, sizeof e);
-      e.dst_off = pos;
-      e.src = it.src;
-      e.src_off = it.src_off;
-      e.body_len = it.src_len;
-      e.store = sel ? 1 : 0;
-      e.head_off = T.blob.size();
-      e.head_len = (uint32_t)it.f.head.size();
-      T.blob.insert(T.blob.end(), it.f.head.begin(), it.f.head.end());
-      e.tail_off = T.blob.size();
-      e.tail_len = (uint32_t)it.f.tail.size();
-      T.blob.insert(T.blob.end(), it.f.tail.begin(), it.f.tail.end());
-      T.entry.push_back(e);
-      T.item.push_back(j);
-      T.pieces = (uint32_t)std::max<uint64_t>(T.pieces, (decoded + ZH_FRAME_PIECE - 1) / ZH_FRAME_PIECE);
-    }
-    pos += need;
-  }
-  return pos;
-}
-
-uint64_t zh::build_solid_frame_table(bool tag, const uint8_t *hdr, size_t hdr_len, const std::vector<SolidItem> &items, uint64_t pos,
-                                     uint64_t out_cap, FrameTable &T, uint64_t *block_pos) {
-  T = FrameTable();
-  for (size_t j = 0; j < items.size(); ++j) {
-    const SolidItem &it = items[j];
+    const TableBlock &it = items[j];
     const size_t ns = it.seg.size(), e0 = T.entry.size(), blob0 = T.blob.size();
     uint64_t need = 0, from = 0;
+    uint32_t pieces = T.pieces;
     for (size_t s = 0; s < ns; ++s) {
-      const SolidSeg &sg = it.seg[s];
-      const BlockFrame f(tag, 1, hdr, hdr_len, sg.filename, sg.plain_len, sg.digest, s == 0, s + 1 == ns);
+      const TableSeg &sg = it.seg[s];
+      const BlockFrame f(tag, level, hdr, hdr_len, sg.filename, sg.plain_len, sg.digest, s == 0, s + 1 == ns);
       ZhFrameEntry e;
       memset(&e, 0, sizeof e);
       e.dst_off = pos + need;
       e.src = it.src;
       e.src_off = it.src_off + from;
       e.body_len = sg.end - from;
+      e.store = sel ? 1 : 0;
       e.head_off = T.blob.size();
       e.head_len = (uint32_t)f.head.size();
       T.blob.insert(T.blob.end(), f.head.begin(), f.head.end());
@@ -112,14 +82,14 @@ uint64_t zh::build_solid_frame_table(bool tag, const uint8_t *hdr, size_t hdr_le
       T.blob.insert(T.blob.end(), f.tail.begin(), f.tail.end());
       T.entry.push_back(e);
       T.item.push_back(j);
-      need += f.head.size() + e.body_len + f.tail.size();
+      const uint64_t decoded = T.sel_len + e.body_len;
+      need += f.head.size() + (sel ? store_body_len(decoded) : e.body_len) + f.tail.size();
+      pieces = (uint32_t)std::max<uint64_t>(pieces, (decoded + ZH_FRAME_PIECE - 1) / ZH_FRAME_PIECE);
       from = sg.end;
     }
     if (block_pos) block_pos[j] = pos;
-    if (need <= out_cap && pos <= out_cap - need) {
-      for (size_t n = e0; n < T.entry.size(); ++n)
-        T.pieces = (uint32_t)std::max<uint64_t>(T.pieces, (T.entry[n].body_len + ZH_FRAME_PIECE - 1) / ZH_FRAME_PIECE);
-    } else {                              // the whole block or nothing of it
+    if (need <= out_cap && pos <= out_cap - need) T.pieces = pieces;
+    else {                                // the whole block or nothing of it
       T.entry.resize(e0);
       T.item.resize(e0);
       T.blob.resize(blob0);

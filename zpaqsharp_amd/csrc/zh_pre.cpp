@@ -560,8 +560,11 @@ int compress_method_impl(zpaqhip_ctx *ctx, const int32_t *args, const uint8_t *h
   if (rc) return rc;
   if ((rc = check_blocks(M, in, in_off, n_blocks, err))) return rc;
   DevPre P(M, in, in_off, dev != nullptr);
-  return compress_impl(ctx, hdr, hdr_len, pcomp, pcomp_len, in, in_off, n_blocks, nullptr, nullptr, filenames, out, out_cap, out_len,
-                       block_off, opts, &P, err, dev);
+  CompressCall a;
+  a.ctx = ctx; a.hdr = hdr; a.hdr_len = hdr_len; a.pcomp = pcomp; a.pcomp_len = pcomp_len;
+  a.in = in; a.in_off = in_off; a.n_blocks = n_blocks; a.filenames = filenames;
+  a.out = out; a.out_cap = out_cap; a.out_len = out_len; a.block_off = block_off; a.opts = opts; a.pre = &P; a.err = err; a.dev = dev;
+  return compress_impl(a);
 }
 
 }  // namespace
@@ -681,8 +684,11 @@ extern "C" int zpaqhip_compress_mixed_blocks_device(zpaqhip_ctx *ctx, const zpaq
     DevPre P(M[g], (const uint8_t *)d_in, len_off.data(), true, src_off.data());
     const DeviceEnds dev{stream, &sink};
     size_t end = 0;
-    const int rc = compress_impl(ctx, m.hdr, m.hdr_len, m.pcomp, m.pcomp_len, (const uint8_t *)d_in, len_off.data(), ng, nullptr,
-                                 nullptr, filenames ? names.data() : nullptr, nullptr, 0, &end, at.data(), opts, &P, err, &dev);
+    CompressCall a;
+    a.ctx = ctx; a.hdr = m.hdr; a.hdr_len = m.hdr_len; a.pcomp = m.pcomp; a.pcomp_len = m.pcomp_len;
+    a.in = (const uint8_t *)d_in; a.in_off = len_off.data(); a.n_blocks = ng; a.filenames = filenames ? names.data() : nullptr;
+    a.out_len = &end; a.block_off = at.data(); a.opts = opts; a.pre = &P; a.err = err; a.dev = &dev;
+    const int rc = compress_impl(a);
     if (rc) {
       if (err && err->block >= 0 && (size_t)err->block < ng) err->block = (int32_t)ids[g][err->block];
       return rc;
